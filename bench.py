@@ -1,6 +1,6 @@
 """bench.py -- PCG iterations/s and SpMV GB/s vs the HBM roofline on a 1M-DoF Poisson CSR system.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 A step = one pass of the hot path over one batch: every rank solves `--systems-per-gpu` (default 1)
 1M-DoF pressure-Poisson systems (3-D 7-point, 100^3, Jacobi-preconditioned fp64 PCG, rtol 1e-8 on
@@ -11,6 +11,16 @@ sides as grouped point-to-point sends), system s goes to rank s mod N, every ran
 the result records are GATHERED (all_gather).  The timed region (the solves) is bracketed by barrier + synchronize and the MAX
 over ranks is taken; `scatter_ms` / `gather_ms` are reported beside `value`, never inside it.  `--config4`: BASELINE config 4 as
 stated (64 x 256^3 over 8 GPUs, 8 per GPU).  Rank 0 prints ONE JSON line.  `value` = PCG iterations of all ranks / that time.
+
+A plain run sets up, warms up, times the steps and prints the headline line (`metric`, `value`, `unit`, `higher_is_better`,
+`dtype`, `ms_per_step`, the configuration and the scatter / gather times).  `--full` adds the rest of the measurement:
+the rooflines of the timed kernels and their measured ceilings, the 256^3 HBM-bound system, the per-rank records, the CPU
+baseline (`--no-cpu-baseline` drops it) and the secondary workloads (`--no-extra` drops them).
+
+`--dump-outputs DIR`: after the timed steps, what the last step returned to its caller, as float64 .npy files --
+`records.npy` (one row per system of the batch, in batch order: iterations, status, final <r,r>/<b,b>) and `x_system<s>.npy`
+per system s (written by the rank that solved it).  Within 64 MB in all: a solution larger than its share is written as the
+entries at a fixed sorted sample of indices (numpy default_rng(0), the same for every run of the same arguments).
 """
 
 from __future__ import annotations
@@ -213,8 +223,13 @@ def parse_args():
     # abbreviation of its --nnodes / --nproc-per-node and refuses the command line)
     ap.add_argument("--grid", "--n", dest="n", type=int, default=100, help="grid points per side (3-D 100 -> 1,000,000 DoF)")
     ap.add_argument("--precond", default="jacobi", choices=["jacobi", "none", "ic0"])
-    ap.add_argument("--no-extra", action="store_true", help="skip the secondary workloads")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: rooflines, measured ceilings, the 256^3 system, per-rank records, the CPU baseline "
+                         "and the secondary workloads")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (records, solutions) as .npy files into DIR")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the secondary workloads")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise torch.distributed and run the scatter / gather even with ONE rank (under torch.distributed.run): "
                          "exercises the RCCL path of this script on a one-GPU box")
@@ -301,6 +316,25 @@ def measured_stream_ceilings() -> dict:
     return out
 
 
+DUMP_BUDGET_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(out_dir: pathlib.Path, table, ids, results, count: int, torch) -> None:
+    """`--dump-outputs`: the last timed step's results as float64 .npy files.  `table` (rank 0 only): the batch's records in batch
+    order; `ids` / `results`: this rank's systems and what their solves returned.  Every solution gets an equal share of the
+    budget (what the records take aside); a larger one is sampled at sorted indices drawn by default_rng(0)."""
+    out_dir.mkdir(parents=True, exist_ok=True)
+    if table is not None:
+        np.save(out_dir / "records.npy", np.ascontiguousarray(table[:, :3], dtype=np.float64))
+    share = (DUMP_BUDGET_BYTES - 24 * count - 256 * (count + 1)) // (8 * count)      # (256: an .npy header and more)
+    for sid, r in zip(ids, results):
+        x = r.x
+        if x.numel() > share:
+            idx = np.sort(np.random.default_rng(0).choice(x.numel(), share, replace=False))
+            x = x[torch.from_numpy(idx).to(x.device)]
+        np.save(out_dir / f"x_system{sid}.npy", x.detach().to(torch.float64).cpu().numpy())
+
+
 def main() -> None:
     args = parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -383,6 +417,7 @@ def main() -> None:
     system = handles[0]
     from deeppreconditioning_amd.batch import solve_batch
     last_records = np.zeros((len(rhs), 4))
+    last_results = []
 
     def step() -> int:
         if len(rhs) == 1:
@@ -397,6 +432,8 @@ def main() -> None:
                 results += solve_batch(hs, chunk, n_streams=len(chunk))
         for i, r in enumerate(results):
             last_records[i] = (r.iterations, r.status, r.final_res, r.seconds)
+        if args.dump_outputs:
+            last_results[:] = results
         return sum(r.iterations for r in results)
 
     # Device wake-up, part of the setup (not a step, not timed): while torch was imported and the systems were built the GPU sat
@@ -419,6 +456,7 @@ def main() -> None:
     tot = torch.tensor([float(iters_local)], device=red_dev, dtype=torch.float64)
     tmax = torch.tensor([elapsed], device=red_dev, dtype=torch.float64)
     per_rank = None
+    table = last_records
     if dist is not None:
         dist.all_reduce(tot, op=dist.ReduceOp.SUM)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -431,6 +469,9 @@ def main() -> None:
         comm["gathered_records"] = {"systems": int(table.shape[0]), "iterations": [int(v) for v in table[:, 0]],
                                     "status": [int(v) for v in table[:, 1]],
                                     "max_final_res": float(table[:, 2].max()) if table.size else None}
+    if args.dump_outputs:
+        dump_outputs(pathlib.Path(args.dump_outputs), table if rank == 0 else None, my_ids, last_results, count, torch)
+    if dist is not None and args.full:
         # one record per rank (its own clock and its own SpMV roofline), gathered the same way
         ms_r = system.spmv_dot_bench(repeats=100)
         gbs_r = loop_kernel_bytes(system) / (ms_r * 1e-3) / 1e9
@@ -443,17 +484,6 @@ def main() -> None:
 
     if rank == 0:
         n, nnz = system.n, system.nnz
-        check = system.solve(poisson.rhs(n, 0))
-        # ---- roofline of the dominant kernel: the SpMV+<p,Ap> launch inside the PCG iteration ----
-        ms = system.spmv_dot_bench(repeats=200)     # HIP events on the launch stream, 200 launches
-        info = system.info()
-        b_alg = loop_kernel_bytes(system)
-        achieved = b_alg / (ms * 1e-3) / 1e9
-        traffic = None
-        pmc = ROOT / "profiles" / "pmc_traffic.json"
-        pmc_all = json.loads(pmc.read_text()) if pmc.exists() else {}
-        traffic = pmc_all.get(f"spmv_{args.dim}d_{args.n}")
-        ceilings = measured_stream_ceilings()
         line = {
             "metric": "pcg_iterations_per_sec", "value": round(total_iters / t, 1), "unit": "iterations/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -462,112 +492,135 @@ def main() -> None:
             "backend": comm["backend"], "ranks": comm["ranks"], "scatter_mode": comm["scatter_mode"],
             "scatter_ms": comm["scatter_ms"], "gather_ms": comm["gather_ms"],
             "config": {"workload": f"poisson{args.dim}d_{args.n}_{args.precond}_pcg_fp64", "dof": n, "nnz": nnz,
-                       "rtol_sq": 1e-8, "max_iter": 1024, "iterations_per_solve": check.iterations,
-                       "final_res": check.final_res, "systems_per_gpu_per_step": args.systems_per_gpu,
+                       "rtol_sq": 1e-8, "max_iter": 1024, "iterations_per_solve": int(last_records[0, 0]),
+                       "final_res": float(last_records[0, 2]), "systems_per_gpu_per_step": args.systems_per_gpu,
                        "batch": ("BASELINE config 4: 64 x poisson3d(256), 8 per GPU on 8 GPUs" if args.config4 else None),
                        "systems_in_batch": count,
                        "parallelism": f"independent systems sharded s mod {world}, no data-path collective"
                                       + (f"; {args.systems_per_gpu} systems per GPU, {min(4, len(rhs))} interleaved on streams"
                                          if args.systems_per_gpu > 1 else "")},
-            "roofline": {"bound": "hbm", "kernel": (f"k_spmv_{info['spmv_kernel']}<FUSE> (p = z + beta p, x += alpha p, q = A p, <p,q>)"
-                                    if info["two_kernel_updates"] else
-                                    f"k_spmv_{info['spmv_kernel']}<CTL,DOT> (SpMV + <p,Ap>)"),
-                         "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
-                         "algorithmic_bytes_per_launch": b_alg, "us_per_launch": round(ms * 1e3, 3),
-                         # PMC counters need rocprofv3, so `traffic` comes from a tracked file: say which run made it
-                         "traffic_source": pmc_all.get("_source", "profiles/pmc_traffic.json (rocprofv3 --pmc passes of "
-                                                                  "tools/pmc_run.py, corrected as profiles/*_pmc_summary.md states)"),
-                         "measured_stream_gbs": ceilings,
-                         # against a plain stream of the same regime: inside the Infinity Cache the 11:1 stream of the
-                         # SpMV's own size, beyond it the best HBM-bound stream
-                         "frac_of_measured_ceiling": round(achieved / (ceilings["cache_resident_spmv_like_11r1w_96MB"]
-                                                                      if b_alg < 200e6 else
-                                                                      max(v for k, v in ceilings.items() if isinstance(v, float)
-                                                                          and not k.startswith("cache_resident"))), 4)},
         }
-        chip = system.chip_info()
-        if chip["chip_by_default"] and args.precond in ("jacobi", "none"):
-            line["roofline"] = chip_roofline(system, poisson.rhs(n, 0), check, line["roofline"], pmc_all.get(f"chip_{args.dim}d_{args.n}"),
-                                             pmc_all.get(f"chip_{args.dim}d_{args.n}_l2_counters"), stencil_offsets(args.dim, args.n))
-            if world == 1 and args.systems_per_gpu == 1:
-                # what a solve costs beyond its kernel -- the Python call, the slot pre-fill, the memset, the gather of b and the syncs around the
-                # launch (all inside `value`'s wall clock, none of it inside the kernel's duration)
-                line["roofline"]["per_solve_time_outside_the_kernel_us"] = round(line["ms_per_step"] * 1e3 - line["roofline"]["us_per_launch"], 1)
-        if per_rank is not None:
-            line["per_rank"] = per_rank
+        if dist is not None:
             line["gathered_records"] = comm["gathered_records"]
-            line["roofline"]["per_rank_frac"] = [r["roofline_frac"] for r in per_rank]
-        if args.precond == "jacobi" and not info["two_kernel_updates"] and not chip["chip_by_default"]:
-            # the whole PCG update of the timed solve against the same peak: K1 + K2 (q, r, dinv read; r written) + K3 (r, dinv, p read;
-            # p written; every other update also p', x read and x written) = B_spmv + 9.5 n x 8 bytes, over wall time per update
-            b_upd = b_alg + int(9.5 * 8 * n)
-            us_upd = t / max(total_iters, 1.0) * world * 1e6
-            line["roofline"]["whole_update"] = {"algorithmic_bytes": b_upd, "us": round(us_upd, 2),
-                                                "achieved": round(b_upd / (us_upd * 1e-6) / 1e9, 1),
-                                                "frac": round(b_upd / (us_upd * 1e-6) / 1e9 / HBM_PEAK_GBS, 4)}
-        if "regime" not in line["roofline"]:
-            line["roofline"]["regime"] = ("cache_resident_1M: the ~150 MB working set of the headline system lives in the 256 MiB "
-                                          "Infinity Cache, so `achieved` is fabric, not DRAM, bandwidth; the HBM-bound figure is "
-                                          "`hbm_bound_256cubed` below")
-        if world == 1:
-            # the same kernel on a system far beyond the Infinity Cache (BASELINE config 4's 256^3: 1.74 GB per SpMV)
-            # (the time of this kernel moves 274-303 us with where the system's arrays happen to land in HBM -- tools/c4_variance_probe.py,
-            # tools/c4_offset_probe.py: physical placement, nothing a virtual offset changes -- so the system is created three times
-            # on fresh allocations and the MEDIAN placement is reported, all three samples beside it)
-            from deeppreconditioning_amd.operators import release_cached_memory
-            samples = []
-            for _ in range(3):
-                s4 = poisson.poisson_system(3, 256)
-                s4.set_preconditioner(D.Jacobi())
-                samples.append(s4.spmv_dot_bench(repeats=40))
-                s4.close()
-                del s4
-                release_cached_memory()
-                torch.cuda.empty_cache()
-            s4 = poisson.poisson_system(3, 256)
-            s4.set_preconditioner(D.Jacobi())
-            samples.append(s4.spmv_dot_bench(repeats=40))
-            samples_sorted = sorted(samples)
-            ms4 = 0.5 * (samples_sorted[1] + samples_sorted[2])          # median of the four placements
-            b4_alg = loop_kernel_bytes(s4)
-            line["roofline"]["hbm_bound_256cubed"] = {
-                "kernel": f"k_spmv_{s4.info()['spmv_kernel']}<CTL,DOT>", "achieved": round(b4_alg / (ms4 * 1e-3) / 1e9, 1),
-                "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(b4_alg / (ms4 * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                "traffic": pmc_all.get("spmv_3d_256"), "algorithmic_bytes_per_launch": b4_alg,
-                "us_per_launch": round(ms4 * 1e3, 2), "dof": s4.n, "nnz": s4.nnz,
-                "frac_of_measured_spmv_like_stream": round(b4_alg / (ms4 * 1e-3) / 1e9 /
-                                                           max(ceilings["spmv_like_11r1w"], ceilings["spmv_like_11r1w_nt"],
-                                                               ceilings["spmv_like_11r1w_walk"], ceilings["spmv_like_11r1w_walk_nt"]), 4),
-                "non_temporal_streams": bool(s4.info().get("spmv_nt", False)),
-                "us_per_launch_by_placement": [round(v * 1e3, 2) for v in samples],
-                "placement": "median of four creations of the system on fresh allocations"}
-            # the same kernel INSIDE the PCG loop (K2 / K3 stream 1.5 GB through the Infinity Cache between two SpMVs, so p is not
-            # resident when K1 starts): wall time per update of a 48-update solve, measured live; the in-loop K1 time itself needs the
-            # profiler -- the median of the committed kernel trace of tools/trace_run_c4.py is quoted beside it
-            b4 = poisson.rhs(s4.n, 0)
-            s4.solve(b4, max_iter=8, want_history=False)
-            r4 = s4.solve(b4, max_iter=48, want_history=False)
-            in_loop = {"pcg_us_per_update": round(r4.seconds / max(r4.iterations, 1) * 1e6, 1), "updates": r4.iterations}
-            tr = next((t for t in (ROOT / "profiles" / f"r0{k}_kernel_trace_256cubed_summary.txt" for k in (5, 4)) if t.exists()), None)
-            if tr is not None:
-                for ln in tr.read_text().splitlines():
-                    if ln.startswith("k_spmv_tile") and "median" in ln:
-                        in_loop["k1_us_median_in_loop_rocprof"] = float(ln.split("median")[1].split("us")[0])
-                        in_loop["k1_frac_in_loop_rocprof"] = round(b4_alg / (in_loop["k1_us_median_in_loop_rocprof"] * 1e-6) / 1e9 / HBM_PEAK_GBS, 4)
-                        in_loop["source"] = f"profiles/{tr.name} (rocprofv3 --kernel-trace of tools/trace_run_c4.py)"
-                        break
-            line["roofline"]["hbm_bound_256cubed"]["in_loop"] = in_loop
-            s4.close()
-            del s4
-        if world == 1 and not args.no_cpu_baseline:
-            line["cpu_baseline"] = cpu_baseline(args.dim, args.n)
-        if world == 1 and not args.no_extra:
-            line["extra"] = extra_workloads(D, poisson, torch)
+        if args.full:
+            full_report(line, args, system, world, per_rank, comm, total_iters, t, D, poisson, torch)
         print(json.dumps(line), flush=True)
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def full_report(line, args, system, world, per_rank, comm, total_iters, t, D, poisson, torch) -> None:
+    """`--full`: what the line carries beyond the headline -- the roofline of the timed kernel against its measured ceilings, the
+    256^3 HBM-bound system, the per-rank records, the CPU baseline and the secondary workloads (rank 0, after the timed steps)."""
+    n, nnz = system.n, system.nnz
+    check = system.solve(poisson.rhs(n, 0))
+    # ---- roofline of the dominant kernel: the SpMV+<p,Ap> launch inside the PCG iteration ----
+    ms = system.spmv_dot_bench(repeats=200)     # HIP events on the launch stream, 200 launches
+    info = system.info()
+    b_alg = loop_kernel_bytes(system)
+    achieved = b_alg / (ms * 1e-3) / 1e9
+    traffic = None
+    pmc = ROOT / "profiles" / "pmc_traffic.json"
+    pmc_all = json.loads(pmc.read_text()) if pmc.exists() else {}
+    traffic = pmc_all.get(f"spmv_{args.dim}d_{args.n}")
+    ceilings = measured_stream_ceilings()
+    line["config"]["iterations_per_solve"] = check.iterations
+    line["config"]["final_res"] = check.final_res
+    line["roofline"] = {"bound": "hbm", "kernel": (f"k_spmv_{info['spmv_kernel']}<FUSE> (p = z + beta p, x += alpha p, q = A p, <p,q>)"
+                                       if info["two_kernel_updates"] else
+                                       f"k_spmv_{info['spmv_kernel']}<CTL,DOT> (SpMV + <p,Ap>)"),
+                            "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                            "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
+                            "algorithmic_bytes_per_launch": b_alg, "us_per_launch": round(ms * 1e3, 3),
+                            # PMC counters need rocprofv3, so `traffic` comes from a tracked file: say which run made it
+                            "traffic_source": pmc_all.get("_source", "profiles/pmc_traffic.json (rocprofv3 --pmc passes of "
+                                                                     "tools/pmc_run.py, corrected as profiles/*_pmc_summary.md states)"),
+                            "measured_stream_gbs": ceilings,
+                            # against a plain stream of the same regime: inside the Infinity Cache the 11:1 stream of the
+                            # SpMV's own size, beyond it the best HBM-bound stream
+                            "frac_of_measured_ceiling": round(achieved / (ceilings["cache_resident_spmv_like_11r1w_96MB"]
+                                                                         if b_alg < 200e6 else
+                                                                         max(v for k, v in ceilings.items() if isinstance(v, float)
+                                                                             and not k.startswith("cache_resident"))), 4)}
+    chip = system.chip_info()
+    if chip["chip_by_default"] and args.precond in ("jacobi", "none"):
+        line["roofline"] = chip_roofline(system, poisson.rhs(n, 0), check, line["roofline"], pmc_all.get(f"chip_{args.dim}d_{args.n}"),
+                                         pmc_all.get(f"chip_{args.dim}d_{args.n}_l2_counters"), stencil_offsets(args.dim, args.n))
+        if world == 1 and args.systems_per_gpu == 1:
+            # what a solve costs beyond its kernel -- the Python call, the slot pre-fill, the memset, the gather of b and the syncs around the
+            # launch (all inside `value`'s wall clock, none of it inside the kernel's duration)
+            line["roofline"]["per_solve_time_outside_the_kernel_us"] = round(line["ms_per_step"] * 1e3 - line["roofline"]["us_per_launch"], 1)
+    if per_rank is not None:
+        line["per_rank"] = per_rank
+        line["gathered_records"] = comm["gathered_records"]
+        line["roofline"]["per_rank_frac"] = [r["roofline_frac"] for r in per_rank]
+    if args.precond == "jacobi" and not info["two_kernel_updates"] and not chip["chip_by_default"]:
+        # the whole PCG update of the timed solve against the same peak: K1 + K2 (q, r, dinv read; r written) + K3 (r, dinv, p read;
+        # p written; every other update also p', x read and x written) = B_spmv + 9.5 n x 8 bytes, over wall time per update
+        b_upd = b_alg + int(9.5 * 8 * n)
+        us_upd = t / max(total_iters, 1.0) * world * 1e6
+        line["roofline"]["whole_update"] = {"algorithmic_bytes": b_upd, "us": round(us_upd, 2),
+                                            "achieved": round(b_upd / (us_upd * 1e-6) / 1e9, 1),
+                                            "frac": round(b_upd / (us_upd * 1e-6) / 1e9 / HBM_PEAK_GBS, 4)}
+    if "regime" not in line["roofline"]:
+        line["roofline"]["regime"] = ("cache_resident_1M: the ~150 MB working set of the headline system lives in the 256 MiB "
+                                      "Infinity Cache, so `achieved` is fabric, not DRAM, bandwidth; the HBM-bound figure is "
+                                      "`hbm_bound_256cubed` below")
+    if world == 1:
+        # the same kernel on a system far beyond the Infinity Cache (BASELINE config 4's 256^3: 1.74 GB per SpMV)
+        # (the time of this kernel moves 274-303 us with where the system's arrays happen to land in HBM -- tools/c4_variance_probe.py,
+        # tools/c4_offset_probe.py: physical placement, nothing a virtual offset changes -- so the system is created three times
+        # on fresh allocations and the MEDIAN placement is reported, all three samples beside it)
+        from deeppreconditioning_amd.operators import release_cached_memory
+        samples = []
+        for _ in range(3):
+            s4 = poisson.poisson_system(3, 256)
+            s4.set_preconditioner(D.Jacobi())
+            samples.append(s4.spmv_dot_bench(repeats=40))
+            s4.close()
+            del s4
+            release_cached_memory()
+            torch.cuda.empty_cache()
+        s4 = poisson.poisson_system(3, 256)
+        s4.set_preconditioner(D.Jacobi())
+        samples.append(s4.spmv_dot_bench(repeats=40))
+        samples_sorted = sorted(samples)
+        ms4 = 0.5 * (samples_sorted[1] + samples_sorted[2])          # median of the four placements
+        b4_alg = loop_kernel_bytes(s4)
+        line["roofline"]["hbm_bound_256cubed"] = {
+            "kernel": f"k_spmv_{s4.info()['spmv_kernel']}<CTL,DOT>", "achieved": round(b4_alg / (ms4 * 1e-3) / 1e9, 1),
+            "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(b4_alg / (ms4 * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+            "traffic": pmc_all.get("spmv_3d_256"), "algorithmic_bytes_per_launch": b4_alg,
+            "us_per_launch": round(ms4 * 1e3, 2), "dof": s4.n, "nnz": s4.nnz,
+            "frac_of_measured_spmv_like_stream": round(b4_alg / (ms4 * 1e-3) / 1e9 /
+                                                       max(ceilings["spmv_like_11r1w"], ceilings["spmv_like_11r1w_nt"],
+                                                           ceilings["spmv_like_11r1w_walk"], ceilings["spmv_like_11r1w_walk_nt"]), 4),
+            "non_temporal_streams": bool(s4.info().get("spmv_nt", False)),
+            "us_per_launch_by_placement": [round(v * 1e3, 2) for v in samples],
+            "placement": "median of four creations of the system on fresh allocations"}
+        # the same kernel INSIDE the PCG loop (K2 / K3 stream 1.5 GB through the Infinity Cache between two SpMVs, so p is not
+        # resident when K1 starts): wall time per update of a 48-update solve, measured live; the in-loop K1 time itself needs the
+        # profiler -- the median of the committed kernel trace of tools/trace_run_c4.py is quoted beside it
+        b4 = poisson.rhs(s4.n, 0)
+        s4.solve(b4, max_iter=8, want_history=False)
+        r4 = s4.solve(b4, max_iter=48, want_history=False)
+        in_loop = {"pcg_us_per_update": round(r4.seconds / max(r4.iterations, 1) * 1e6, 1), "updates": r4.iterations}
+        tr = next((t for t in (ROOT / "profiles" / f"r0{k}_kernel_trace_256cubed_summary.txt" for k in (5, 4)) if t.exists()), None)
+        if tr is not None:
+            for ln in tr.read_text().splitlines():
+                if ln.startswith("k_spmv_tile") and "median" in ln:
+                    in_loop["k1_us_median_in_loop_rocprof"] = float(ln.split("median")[1].split("us")[0])
+                    in_loop["k1_frac_in_loop_rocprof"] = round(b4_alg / (in_loop["k1_us_median_in_loop_rocprof"] * 1e-6) / 1e9 / HBM_PEAK_GBS, 4)
+                    in_loop["source"] = f"profiles/{tr.name} (rocprofv3 --kernel-trace of tools/trace_run_c4.py)"
+                    break
+        line["roofline"]["hbm_bound_256cubed"]["in_loop"] = in_loop
+        s4.close()
+        del s4
+    if world == 1 and not args.no_cpu_baseline:
+        line["cpu_baseline"] = cpu_baseline(args.dim, args.n)
+    if world == 1 and not args.no_extra:
+        line["extra"] = extra_workloads(D, poisson, torch)
 
 
 def mesh_workloads(D, poisson, torch, solve_twice, pmc_all) -> dict:

@@ -2144,7 +2144,7 @@ def _run_bench(extra_args, port_env=None):
     # exactly the driver's command line (torch.distributed.run, one rank per GPU), with --backend gloo because both
     # ranks sit on the box's single GPU (RCCL refuses two ranks on one device)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), str(root / "bench.py"), "--gpus", "2", "--backend", "gloo", "--no-extra",
+           "--master-port", str(port), str(root / "bench.py"), "--gpus", "2", "--backend", "gloo", "--full", "--no-extra",
            "--no-cpu-baseline"] + extra_args
     proc = subprocess.run(cmd, capture_output=True, text=True, cwd=root, env=env, timeout=900)
     assert proc.returncode == 0, proc.stdout[-2000:] + proc.stderr[-4000:]
@@ -2170,7 +2170,7 @@ def test_bench_script_runs_its_collectives_on_rccl_with_one_rank(golden):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), str(root / "bench.py"), "--gpus", "1", "--force-dist", "--no-extra", "--no-cpu-baseline",
+           "--master-port", str(port), str(root / "bench.py"), "--gpus", "1", "--force-dist", "--full", "--no-extra", "--no-cpu-baseline",
            "--steps", "2", "--warmup", "1", "--grid", "64", "--systems-per-gpu", "2"]
     proc = subprocess.run(cmd, capture_output=True, text=True, cwd=root, env=env, timeout=900)
     assert proc.returncode == 0, proc.stdout[-2000:] + proc.stderr[-4000:]
@@ -2262,6 +2262,46 @@ def test_bench_script_config4_shape_at_two_ranks(golden):
     assert abs(total - 2 * 2 * 8 * it) < 0.05 * 2 * 2 * 8 * it, total
     assert "roofline" in line
     _check_scatter_gather_keys(line, systems=16, it=it, mode="specs")
+
+
+def test_bench_plain_run_and_dumped_outputs(golden, tmp_path):
+    """A plain `bench.py` run (no --full) prints the headline line only, and `--dump-outputs` writes what its last timed step
+    returned: the records and the solution, the same from run to run with the same arguments, and the solution solves the system."""
+    import json
+    import pathlib
+    import subprocess
+    import sys
+    root = pathlib.Path(__file__).resolve().parent.parent
+    env = {**__import__("os").environ, "PYTHONPATH": str(root)}
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
+        env.pop(k, None)
+    it = int(golden["pcg_poisson3d_64_jacobi/iters"])
+    outs = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        cmd = [sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--grid", "64",
+               "--dump-outputs", str(d)]
+        proc = subprocess.run(cmd, capture_output=True, text=True, cwd=root, env=env, timeout=600)
+        assert proc.returncode == 0, proc.stdout[-2000:] + proc.stderr[-4000:]
+        lines = [l for l in proc.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, lines
+        line = json.loads(lines[0])
+        assert line["metric"] == "pcg_iterations_per_sec" and line["unit"] == "iterations/s" and line["higher_is_better"] is True
+        assert line["dtype"] == "f64" and line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0
+        assert abs(line["value"] * line["ms_per_step"] * 1e-3 * 3 - 3 * it) < 0.01 * 3 * it
+        assert line["config"]["iterations_per_solve"] == it
+        assert not {"roofline", "cpu_baseline", "extra", "per_rank"} & set(line)
+        assert sorted(p.name for p in d.iterdir()) == ["records.npy", "x_system0.npy"]
+        outs.append((np.load(d / "records.npy"), np.load(d / "x_system0.npy")))
+    (rec, x), (rec2, x2) = outs
+    assert rec.dtype == np.float64 and rec.shape == (1, 3) and rec[0, 0] == it and rec[0, 1] == 0 and rec[0, 2] < 1e-8
+    assert np.array_equal(rec, rec2) and np.array_equal(x, x2)
+    A = O.poisson3d(64)
+    b = O.rhs(A.shape[0], 0)
+    assert x.dtype == np.float64 and x.shape == (A.shape[0],)
+    r = b - A @ x
+    assert np.dot(r, r) / np.dot(b, b) < 2e-8
+    np.testing.assert_allclose(x, CO.pcg(A, b, "jacobi", dinv=O.jacobi_dinv(A))[3], rtol=1e-6, atol=1e-9 * np.abs(x).max())
 
 
 def test_reordering_checks_its_input_pattern(D):

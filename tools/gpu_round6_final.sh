@@ -12,10 +12,10 @@ timeout 900 bash tools/pmc_chip.sh $tag > $out/${tag}_pmc_chip.log 2>&1; echo "p
 timeout 1200 bash tools/pmc_chip_l2.sh $tag > $out/${tag}_pmc_chip_l2.log 2>&1; echo "pmc_chip_l2 rc=$?"
 cp profiles/pmc_traffic.json profiles/${tag}_chip_traffic.md profiles/${tag}_chip_kernel_stats.csv profiles/${tag}_chip_l2_counters.md $out/ 2>/dev/null
 fi
-timeout 1500 python bench.py > $out/${tag}_bench.json 2> $out/${tag}_bench.err; echo "bench rc=$?"
+timeout 1500 python bench.py --full > $out/${tag}_bench.json 2> $out/${tag}_bench.err; echo "bench rc=$?"
 cd /tmp && export TMPDIR=/tmp
 rm -rf $out/${tag}_stats
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $out/${tag}_stats -- python3 $repo/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-extra > $out/${tag}_stats.log 2>&1
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $out/${tag}_stats -- python3 $repo/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-extra > $out/${tag}_stats.log 2>&1
 find $out/${tag}_stats -type f ! -name '*kernel_stats.csv' -delete
 cd $repo
 tail -c 300 $out/${tag}_bench.err; python3 - <<P

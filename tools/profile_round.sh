@@ -5,10 +5,10 @@ tag=${1:-r01}
 export PYTHONPATH=$PWD
 out=$PWD/gpurun_out
 mkdir -p $out
-python bench.py > $out/${tag}_bench.json 2> $out/${tag}_bench.err
+python bench.py --full > $out/${tag}_bench.json 2> $out/${tag}_bench.err
 cd /tmp && export TMPDIR=/tmp
 rm -rf $out/${tag}_stats
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/${tag}_stats -- python3 $OLDPWD/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-extra > $out/${tag}_stats.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/${tag}_stats -- python3 $OLDPWD/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-extra > $out/${tag}_stats.log 2>&1
 rm -rf $out/${tag}_stats_c4
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/${tag}_stats_c4 -- python3 $OLDPWD/tools/trace_run_c4.py > $out/${tag}_stats_c4.log 2>&1
 for c in "FETCH_SIZE" "WRITE_SIZE" "TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum TCC_EA0_RDREQ_64B_sum TCC_EA0_RDREQ_128B_sum"; do
