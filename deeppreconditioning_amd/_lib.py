@@ -67,6 +67,9 @@ SIGNATURES = {
     "dpcg_release_cached_memory": (_int, []),
     "dpcg_update_values": (_int, [_p, _p, _int, _int, _p]),
     "dpcg_stream_bench": (_int, [_int, _int, _int, _i64, _int, C.POINTER(C.c_float), C.POINTER(_i64), _p]),
+    "dpcg_spectrum": (_int, [_p, _int, _dbl, C.c_uint64, _p, C.POINTER(_int), C.POINTER(_dbl), C.POINTER(_dbl),
+                             C.POINTER(_dbl), C.POINTER(_dbl), _p, _p]),
+    "dpcg_tridiag_ritz": (_int, [_int, _p, _p, _p, _p]),
     "dpcg_solve": (_int, [_p, _p, _p, _p, _dbl, _dbl, _int, _int, _p, C.POINTER(_int), C.POINTER(_dbl),
                           C.POINTER(_dbl), _p, _p, _p]),
     "dpcg_solve_batch": (_int, [_int, _p, _p, _p, _p, _dbl, _dbl, _int, _int, _int, _p, _p, _p, _p]),

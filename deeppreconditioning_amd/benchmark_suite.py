@@ -15,6 +15,7 @@ from dataclasses import dataclass, field
 import numpy as np
 import torch
 
+from ._lib import BREAKDOWN, DpcgError
 from .cg import preconditioned_conjugate_gradient
 from .io import coo_to_csr_device
 from .model import lower_factor_csr, tril_batch_from_csr
@@ -68,12 +69,15 @@ class BenchmarkSuite:
     model: torch.nn.Module | None
     techniques: tuple[str, ...] = ("vanilla", "jacobi", "incomplete_cholesky", "incomplete_cholesky_solve", "learned")
     results_directory: pathlib.Path = pathlib.Path("./assets/results/")
-    kappa_max_n: int = 3000   # cond(M A) needs dense N x N matrices (test.py:111-113): only for small systems
+    kappa_max_n: int = 3000   # cond(M A) needs dense N x N matrices (test.py:111-113): beyond, a Lanczos estimate of the spectrum
     results: dict = field(default_factory=dict)
 
     def __post_init__(self):
         for p in PARAMETERS:
             setattr(self, p, {name: [] for name in self.techniques})
+        # per technique and sample where its kappa came from: "dense" (cond of the dense M A, test.py:111-113), "lanczos"
+        # (lambda_max / lambda_min of M A, device estimate beyond kappa_max_n) or "unconverged" (kappa is NaN)
+        self.kappa_sources = {name: [] for name in self.techniques}
 
     # -- test.py:61-68 without densifying: mirror the strict lower triangle, compress on the device ----------
     def _reconstruct_system(self, system_tril, original_size: int) -> CsrSystem:
@@ -111,16 +115,26 @@ class BenchmarkSuite:
 
     def _density_and_kappa(self, system: CsrSystem, n: int, want_spectrum: bool = False):
         """100 * nnz(M) / n^2 (test.py:107-109), cond(M A) (test.py:111-113) and, for the first sample, the singular
-        values of M A (test.py:115-117) -- reporting only, dense N x N, small n only."""
+        values of M A (test.py:115-117) -- reporting only, dense N x N, small n only -- and where the kappa came from.
+        Beyond kappa_max_n: kappa = lambda_max / lambda_min of M A by the device Lanczos estimator (CsrSystem.spectrum_bounds;
+        the same number as the dense cond() only when M = c I), NaN when it did not converge; the density stays NaN."""
         if n > self.kappa_max_n:
-            return float("nan"), float("nan"), None
+            try:
+                sb = system.spectrum_bounds(rtol=1e-4, max_steps=min(n, 2000))
+            except DpcgError as exc:     # M found not positive definite: no number (as the dense path would give an indefinite M A)
+                if exc.status != BREAKDOWN:
+                    raise
+                return float("nan"), float("nan"), None, "unconverged"
+            if sb.converged:
+                return float("nan"), sb.kappa, None, "lanczos"
+            return float("nan"), float("nan"), None, "unconverged"
         eye = torch.eye(n, dtype=torch.float64, device=system.device)
         M = torch.stack([system.precond_apply(eye[:, j]) for j in range(n)], dim=1)
         A = torch.stack([system @ eye[:, j] for j in range(n)], dim=1)
         density = 100.0 * float((M != 0).sum()) / (n * n)
         MA = M @ A
         spectrum = torch.linalg.svdvals(MA).tolist() if want_spectrum else None
-        return density, float(torch.linalg.cond(MA)), spectrum
+        return density, float(torch.linalg.cond(MA)), spectrum, "dense"
 
     def run(self) -> None:
         """test.py:119-155."""
@@ -137,7 +151,8 @@ class BenchmarkSuite:
                 torch.cuda.synchronize()
                 setup = time.perf_counter() - start if name != "vanilla" else 0.0      # test.py:135
                 duration, iteration, info = preconditioned_conjugate_gradient(system, rhs, system._precond)
-                density, kappa, spectrum = self._density_and_kappa(system, n, want_spectrum=index == 0)
+                density, kappa, spectrum, source = self._density_and_kappa(system, n, want_spectrum=index == 0)
+                self.kappa_sources[name].append(source)
                 if spectrum is not None:
                     eigenvalues[name] = spectrum
                 self._record(name, kappas=kappa, densities=density, iterations=iteration, setups=setup, durations=duration,
@@ -173,6 +188,8 @@ class BenchmarkSuite:
         write("comparability.csv", ["technique", "comparable_with_the_reference"],                # not in the reference: see COMPARABILITY
               ([t, COMPARABILITY.get(t, "unknown technique")] for t in self.techniques))
         write("totals.csv", self.techniques, zip(*(self.totals[t] for t in self.techniques)))
+        if any(src == "lanczos" for srcs in self.kappa_sources.values() for src in srcs):   # not in the reference: see _density_and_kappa
+            write("kappa_sources.csv", self.techniques, zip(*(self.kappa_sources[t] for t in self.techniques)))
 
 
 def main(params_path="params.yaml", checkpoint="./assets/checkpoints/best.pt", root=None, *,

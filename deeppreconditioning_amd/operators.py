@@ -382,6 +382,25 @@ class SolveResult:
     err_history: np.ndarray | None = None
 
 
+@dataclass
+class SpectrumBounds:
+    """Extreme eigenvalues of M A from `CsrSystem.spectrum_bounds` (a Lanczos process on the device, dpcg_spectrum).
+
+    kappa = lambda_max / lambda_min: the quantity that governs PCG convergence.  It equals the reference's cond(M @ A)
+    (test.py:111-113, a singular-value ratio) only when M = c I.  err_min / err_max bound the distance from each Ritz value
+    to an eigenvalue of M A; alpha / beta are the diagonal and off-diagonals of the Lanczos tridiagonal T_k
+    (beta[k-1] = beta_{k+1}, the residual coupling)."""
+    lambda_min: float
+    lambda_max: float
+    kappa: float
+    steps: int
+    converged: bool
+    err_min: float
+    err_max: float
+    alpha: np.ndarray
+    beta: np.ndarray
+
+
 _REORDER_MODES = {None: L.REORDER_NONE, False: L.REORDER_NONE, "none": L.REORDER_NONE, "auto": L.REORDER_AUTO,
                   "rcm": L.REORDER_ALWAYS, True: L.REORDER_ALWAYS, "regions": L.REORDER_REGIONS}
 
@@ -636,6 +655,46 @@ class CsrSystem:
         k = iters.value
         return SolveResult(x, k, status, res.value, sec.value, hist[: k + 1] if hist is not None else np.empty(0),
                            err[: k + 1] if err is not None else None)
+
+    def spectrum_bounds(self, *, max_steps: int = 1000, rtol: float = 1e-6, seed: int = 0) -> SpectrumBounds:
+        """Extreme eigenvalues of M A for the attached preconditioner M (M = I without one) and kappa = lambda_max / lambda_min,
+        at any size (dpcg_spectrum: Lanczos in the M inner product, fully reorthogonalised, basis resident on the device;
+        test.py:111-113 forms M A densely instead).  M must be symmetric positive definite: when the process finds it is not,
+        this raises DpcgError (status 2) instead of returning a number.  An OperatorPreconditioner works (one host call per
+        step: slow) -- keeping it symmetric positive definite is the caller's promise.  The result does not depend on the
+        handle's numbering; the same seed gives the same bits.  Memory: 2 x (min(max_steps, n) + 1) x n doubles."""
+        m = max(1, min(int(max_steps), self.n))
+        alpha = np.zeros(m)
+        beta = np.zeros(m)
+        k = C.c_int(0)
+        tmin, tmax, emin, emax = C.c_double(), C.c_double(), C.c_double(), C.c_double()
+        with torch.cuda.device(self.device):
+            status = L.check(L.lib().dpcg_spectrum(self._h, int(max_steps), float(rtol), int(seed) & (2**64 - 1), _stream(),
+                                                   C.byref(k), C.byref(tmin), C.byref(tmax), C.byref(emin), C.byref(emax),
+                                                   _np_ptr(alpha), _np_ptr(beta)))
+        if isinstance(self._precond, OperatorPreconditioner) and self._precond.error is not None:
+            err, self._precond.error = self._precond.error, None
+            raise err
+        if status == L.BREAKDOWN:
+            raise L.DpcgError(status, L.lib().dpcg_last_error().decode(errors="replace"))
+        steps = k.value
+        kappa = tmax.value / tmin.value if tmin.value > 0 else float("nan")
+        return SpectrumBounds(tmin.value, tmax.value, kappa, steps, status == L.OK, emin.value, emax.value,
+                              alpha[:steps].copy(), beta[:steps].copy())
+
+
+def tridiag_ritz(alpha, beta):
+    """(theta, bottom) of the symmetric tridiagonal tridiag(beta, alpha, beta): eigenvalues ascending and the last component of
+    each unit eigenvector (host only, dpcg_tridiag_ritz: implicit QL)."""
+    a = np.ascontiguousarray(alpha, dtype=np.float64)
+    b = np.ascontiguousarray(beta, dtype=np.float64)
+    k = a.size
+    if b.size < k - 1:
+        raise ValueError("beta needs len(alpha) - 1 entries")
+    theta = np.empty(k)
+    bottom = np.empty(k)
+    L.check(L.lib().dpcg_tridiag_ritz(k, _np_ptr(a), _np_ptr(b) if k > 1 else None, _np_ptr(theta), _np_ptr(bottom)))
+    return theta, bottom
 
 
 def dot(a: torch.Tensor, b: torch.Tensor) -> float:

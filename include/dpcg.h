@@ -257,6 +257,27 @@ int dpcg_spmv_dot_bench(dpcg_handle_t h, const double *x, double *y, int repeats
 int dpcg_stream_bench(int n_read, int write, int nontemporal, int64_t out_bytes, int repeats, float *ms_per_launch,
                       int64_t *bytes_per_launch, dpcg_stream_t stream);
 
+/* ---- spectrum of M A: test.py:111-113 (kappa = cond(M @ A)) at any size -------------------------------------------
+ * The reference forms M A densely and takes cond() of it; this runs a Lanczos process in the M inner product on the device
+ * (M A is similar to the symmetric M^{1/2} A M^{1/2}), with full reorthogonalisation (CGS2) against a basis resident in HBM,
+ * for whatever symmetric positive definite M the handle applies (Jacobi, CSR, L L^T multiplied or solved, a callback).  The
+ * start vector is a counter-based hash of (seed, the caller's row index): results do not depend on the handle's numbering and
+ * two calls give the same bits.  Out: *steps, the extreme Ritz values theta_min / theta_max (eigenvalues of M A; kappa =
+ * theta_max / theta_min -- lambda_max / lambda_min, which equals the reference's singular-value ratio only when M = c I),
+ * their error bounds err = beta_{k+1} |s_k| (s_k: last component of the Ritz vector in T_k); alpha, beta (host, >= min(max_steps,
+ * n) doubles each, or NULL): the diagonal and the off-diagonals of T_k, beta[k-1] = beta_{k+1}.  At most min(max_steps, n)
+ * steps; stops when both bounds are <= rtol |theta|, when beta reaches 0 or after n steps (exact: DPCG_OK), else DPCG_MAX_ITER.
+ * DPCG_BREAKDOWN: <w, M w> <= 0 beyond rounding (M is not positive definite) or a non-finite value; no number is returned.
+ * DPCG_ERR_NOMEM: the basis, 2 x (max_steps + 1) x n doubles, does not fit.  Synchronises `stream` every 16 steps and on return;
+ * leaves the handle's solve state alone (its own buffers, from the block cache). */
+int dpcg_spectrum(dpcg_handle_t h, int max_steps, double rtol, uint64_t seed, dpcg_stream_t stream, int *steps,
+                  double *theta_min, double *theta_max, double *err_min, double *err_max,
+                  double *alpha, double *beta);
+/* Host only: eigenvalues theta[0..k) (ascending) of the symmetric tridiagonal with diagonal alpha[0..k) and off-diagonal
+ * beta[0..k-1) (beta may be NULL when k = 1), and bottom[i] = the last component of theta[i]'s unit eigenvector (sign
+ * arbitrary).  Implicit QL with Wilkinson shifts. */
+int dpcg_tridiag_ritz(int k, const double *alpha, const double *beta, double *theta, double *bottom);
+
 /* ---- the solve: cg.py:50-90 (PCG) and cg.py:20-47 (CG = PCG with M = I, test on r) ----------- */
 /*
  * b, x0 (may be NULL = zeros, cg.py:58), x (out, may be NULL): device fp64[n].  x is written in stream order: valid for
