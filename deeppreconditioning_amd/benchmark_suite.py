@@ -19,7 +19,7 @@ from ._lib import BREAKDOWN, DpcgError
 from .cg import preconditioned_conjugate_gradient
 from .io import coo_to_csr_device
 from .model import lower_factor_csr, tril_batch_from_csr
-from .operators import IC0, ICT, ICholT, CsrSystem, Identity, Jacobi, LLtMultiply
+from .operators import IC0, ICT, ICholT, CsrSystem, Identity, Jacobi, LLtMultiply, SmoothedAggregation
 
 PARAMETERS = ["kappas", "densities", "iterations", "setups", "durations", "totals", "successes"]  # test.py:180
 
@@ -39,6 +39,9 @@ COMPARABILITY = {
     "incomplete_cholesky_multicolor": "not in the reference: IC(0) of the system in multicolour order, applied by triangular solves "
                                       "(another elimination order: another preconditioner; the fastest of the IC variants here)",
     "learned": "comparable given the same checkpoint; spconv's weight layout is assumed KRSC (unpinned)",
+    "algebraic_multigrid": "same family as pyamg's smoothed_aggregation_solver(A).aspreconditioner(cycle='V') (test.py:95-98): "
+                           "symmetric strength, MIS(2) aggregation, Jacobi-smoothed prolongator, Galerkin levels, exact coarse solve; "
+                           "smoothed by damped Jacobi instead of Gauss-Seidel; pyamg absent: unpinned; applied, not materialised",
 }
 
 
@@ -107,6 +110,8 @@ class BenchmarkSuite:
             return IC0("solve")
         if name == "incomplete_cholesky_multicolor":    # ... in multicolour order (opt-in: not among the default techniques)
             return IC0("solve", ordering="multicolor")
+        if name == "algebraic_multigrid":           # test.py:95-98 (opt-in): smoothed aggregation, one V-cycle per update
+            return SmoothedAggregation()
         if name == "learned":                       # test.py:100-105
             with torch.no_grad():
                 out = self.model(system_tril)

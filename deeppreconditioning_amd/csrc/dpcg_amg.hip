@@ -1,0 +1,1051 @@
+// Smoothed-aggregation algebraic multigrid (DPCG_PRECOND_AMG, include/dpcg.h): the hierarchy is built on the device and applied
+// as a V(nu, nu) cycle with damped-Jacobi smoothing inside the multi-launch PCG loop (graph capture included).  The reference's
+// harness names this technique `algebraic_multigrid` (pyamg's smoothed_aggregation_solver(A).aspreconditioner(cycle="V")).
+//
+// Setup of level l (A_l, n_l rows; level 0 = the handle's matrix; rules that look at a row index use the CALLER's index):
+//   strength   j strong for i when j != i, a_ij != 0 and |a_ij| >= theta sqrt(|a_ii a_jj|)  (k_amg_diag, k_amg_strength)
+//   MIS(2)     tuples (state, splitmix64(seed, caller index), caller index), OUT < UNDECIDED < IN; a round takes the tuple
+//              maximum over the closed strong neighbourhood twice (k_mis_max, reading the previous round's states only) and
+//              then decides (k_mis_update): own tuple -> IN, an IN maximum -> OUT.  Rounds until nobody is undecided.
+//   aggregates roots numbered by ascending caller index (flag by caller index + scan); neighbours of a root join it
+//              (k_agg_near: the root is unique); the rest join their step-1-assigned strong neighbour of largest |a_ij|,
+//              ties to the smaller caller index (k_agg_far)
+//   T          one entry per row, 1/sqrt(|aggregate|)
+//   P          (I - omega D^-1 A) T, omega = (4/3) / rho, rho = theta_max + err_max of a 30-step Lanczos estimate of the
+//              spectrum of D^-1 A (dpcg_spectrum on a handle that borrows A_l): the product A T by the row-wise SpGEMM with
+//              the (I - omega D^-1) epilogue fused
+//   A_{l+1}    P^T (A P): two row-wise SpGEMMs (k_spgemm), P^T by a stable sort of P's entries by column
+// Stop at max_coarse rows, at max_levels, or when coarsening stalls (n_c > 0.9 n).  The coarsest level is inverted densely on
+// the host (Cholesky) and applied by a GEMV.
+//
+// SpGEMM (k_spgemm): one wave per output row.  The row's products are expanded in a fixed order (entries of X's row, then of the
+// Y row each selects), keyed (column << 32 | product index), bitonic-sorted in LDS (or, for rows of more than kSgCap products, in
+// a global scratch segment of their own), and compressed: the first product of every column sums the run after it in product
+// order.  A symbolic pass writes the row lengths, a scan gives the row pointers, the numeric pass writes sorted columns.  No
+// float atomics: two setups give the same bits.
+//
+// Apply (launch_amg_apply), per level: k_amg_row<PRE> (x = omega D^-1 b and r = b - A x in one pass), nu - 1 k_amg_row<SWEEP>,
+// k_amg_row<PLAIN> (b_{l+1} = P^T r); k_amg_gemv on the coarsest level; then k_amg_row<ACC> (x += P x_{l+1}) and nu
+// k_amg_row<POST> (x += omega D^-1 (b - A x)) -- on level 0 the last one writes z and the partials of <r, z> for PCG.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "dpcg_device.h"
+#include "dpcg_host.h"
+#include "dpcg_prims.h"
+
+namespace dpcg {
+
+struct AmgLevel {
+    CsrDev A;                         // level 0: a view of the handle's matrix (not owned); coarser levels: owned
+    double *dinv = nullptr;           // 1 / a_ii
+    uint8_t *strong = nullptr;        // per entry of A: strong connection
+    int8_t *roots = nullptr;          // MIS(2) result (1 = root)
+    int32_t *agg = nullptr;           // aggregate of each row (this level's numbering)
+    CsrDev P, Pt, AP;                 // owned; empty on the coarsest level
+    int32_t *pt_order = nullptr;      // entry of P^T -> entry of P (the stable sort by column)
+    int64_t nc = 0;                   // rows of the next level
+    double rho = 0.0, omega = 0.0;
+    int tpr_a = 2, tpr_p = 2, tpr_pt = 2;
+    double *b = nullptr, *xa = nullptr, *xb = nullptr, *ra = nullptr, *rb = nullptr;   // work vectors (b: levels >= 1)
+};
+
+struct AmgState {
+    double theta = 0.0;
+    int max_levels = 10, max_coarse = 500, sweeps = 1;
+    uint64_t seed = 0;
+    std::vector<AmgLevel> lv;         // lv.back(): the coarsest level (dense solve)
+    double *cinv = nullptr;           // dense inverse of the coarsest matrix, row-major
+    int64_t nco = 0;
+    int reused_levels = 0;            // levels whose structures a re-attach took over from the parked hierarchy
+};
+
+namespace {
+
+constexpr int kSgCap = 1024;          // products of a row sorted in LDS (16 KiB per one-wave workgroup)
+constexpr int kApplyMaxGrid = kMaxSpmvGrid;
+constexpr int kRhoSteps = 30;         // Lanczos steps of the spectral-radius estimate
+
+enum MisState : int8_t { MIS_OUT = 0, MIS_UND = 1, MIS_IN = 2 };
+
+__device__ __forceinline__ uint64_t amg_hash(uint64_t seed, uint64_t i) {   // splitmix64 finaliser of a counter (as k_lz_start)
+    uint64_t x = seed * 0x9E3779B97F4A7C15ull + (i + 1) * 0xBF58476D1CE4E5B9ull;
+    x ^= x >> 30;
+    x *= 0xBF58476D1CE4E5B9ull;
+    x ^= x >> 27;
+    x *= 0x94D049BB133111EBull;
+    x ^= x >> 31;
+    return x;
+}
+
+inline int grid_of(int64_t n, int per_block = kBlock) {
+    int64_t g = (n + per_block - 1) / per_block;
+    return (int)std::max<int64_t>(1, std::min<int64_t>(g, 65536));
+}
+
+// ---- setup kernels ---------------------------------------------------------------------------------------------
+// dinv[i] = 1 / a_ii; *bad |= 1 when a diagonal is missing, zero, negative or not finite
+__global__ __launch_bounds__(kBlock) void k_amg_diag(int64_t n, const int32_t *__restrict__ rp, const int32_t *__restrict__ ci,
+                                                     const double *__restrict__ v, double *__restrict__ dinv,
+                                                     double *__restrict__ diag, int *bad) {
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+        double d = 0.0;
+        for (int k = rp[i]; k < rp[i + 1]; ++k)
+            if (ci[k] == i) d = v[k];
+        if (!(d > 0.0) || !isfinite(d)) {
+            atomicOr(bad, 1);
+            dinv[i] = 0.0;
+        } else {
+            dinv[i] = 1.0 / d;
+        }
+        if (diag) diag[i] = d;
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_amg_strength(int64_t n, const int32_t *__restrict__ rp, const int32_t *__restrict__ ci,
+                                                         const double *__restrict__ v, const double *__restrict__ diag, double theta,
+                                                         uint8_t *__restrict__ strong) {
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride)
+        for (int k = rp[i]; k < rp[i + 1]; ++k) {
+            const int j = ci[k];
+            const double dij = diag[i] * diag[j];
+            strong[k] = (j != i && v[k] != 0.0 && fabs(v[k]) >= theta * sqrt(fabs(dij))) ? 1 : 0;
+        }
+}
+
+__global__ __launch_bounds__(kBlock) void k_mis_init(int64_t n, uint64_t seed, const int32_t *__restrict__ perm,
+                                                     int8_t *__restrict__ st, uint64_t *__restrict__ hsh, int32_t *__restrict__ cid) {
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+        const int32_t c = perm ? perm[i] : (int32_t)i;
+        st[i] = MIS_UND;
+        cid[i] = c;
+        hsh[i] = amg_hash(seed, (uint64_t)c);
+    }
+}
+
+__device__ __forceinline__ bool tuple_gt(int a, int b, const int8_t *st, const uint64_t *hsh, const int32_t *cid) {
+    if (st[a] != st[b]) return st[a] > st[b];
+    if (hsh[a] != hsh[b]) return hsh[a] > hsh[b];
+    return cid[a] > cid[b];
+}
+
+// out[i] = the node of largest tuple among {in[i]} and {in[j] : j strong neighbour of i} (in = null: the nodes themselves)
+__global__ __launch_bounds__(kBlock) void k_mis_max(int64_t n, const int32_t *__restrict__ rp, const int32_t *__restrict__ ci,
+                                                    const uint8_t *__restrict__ strong, const int8_t *__restrict__ st,
+                                                    const uint64_t *__restrict__ hsh, const int32_t *__restrict__ cid,
+                                                    const int32_t *__restrict__ in, int32_t *__restrict__ out) {
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+        int best = in ? in[i] : (int)i;
+        for (int k = rp[i]; k < rp[i + 1]; ++k) {
+            const int j = ci[k];
+            if (j == i || (strong && !strong[k])) continue;
+            const int c = in ? in[j] : j;
+            if (tuple_gt(c, best, st, hsh, cid)) best = c;
+        }
+        out[i] = best;
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_mis_update(int64_t n, const int8_t *__restrict__ st, const int32_t *__restrict__ m2,
+                                                       int8_t *__restrict__ st_new, int *undecided) {
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    int left = 0;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+        int8_t s = st[i];
+        if (s == MIS_UND) {
+            const int J = m2[i];
+            if (J == i) s = MIS_IN;
+            else if (st[J] == MIS_IN) s = MIS_OUT;
+            else left = 1;
+        }
+        st_new[i] = s;
+    }
+    if (left) atomicAdd(undecided, 1);
+}
+
+__global__ __launch_bounds__(kBlock) void k_root_flags(int64_t n, const int8_t *__restrict__ st, const int32_t *__restrict__ cid,
+                                                       int8_t *__restrict__ roots, int32_t *__restrict__ flag_by_cid) {
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+        roots[i] = st[i] == MIS_IN ? 1 : 0;
+        flag_by_cid[cid[i]] = st[i] == MIS_IN ? 1 : 0;
+    }
+}
+
+// roots: their number; neighbours of a root: the root's (unique: roots are >= 3 hops apart); others -1
+__global__ __launch_bounds__(kBlock) void k_agg_near(int64_t n, const int32_t *__restrict__ rp, const int32_t *__restrict__ ci,
+                                                     const uint8_t *__restrict__ strong, const int8_t *__restrict__ roots,
+                                                     const int32_t *__restrict__ cid, const int32_t *__restrict__ rank_by_cid,
+                                                     int32_t *__restrict__ agg1) {
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+        int a = -1;
+        if (roots[i]) {
+            a = rank_by_cid[cid[i]];
+        } else {
+            for (int k = rp[i]; k < rp[i + 1]; ++k) {
+                const int j = ci[k];
+                if (j == i || (strong && !strong[k])) continue;
+                if (roots[j]) { a = rank_by_cid[cid[j]]; break; }
+            }
+        }
+        agg1[i] = a;
+    }
+}
+
+// the rest: the aggregate of the step-1-assigned strong neighbour of largest |a_ij| (ties: smaller caller index)
+__global__ __launch_bounds__(kBlock) void k_agg_far(int64_t n, const int32_t *__restrict__ rp, const int32_t *__restrict__ ci,
+                                                    const double *__restrict__ v, const uint8_t *__restrict__ strong,
+                                                    const int32_t *__restrict__ cid, const int32_t *__restrict__ agg1,
+                                                    int32_t *__restrict__ agg, int *bad) {
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+        int a = agg1[i];
+        if (a < 0) {
+            double best = -1.0;
+            int bc = 0x7fffffff;
+            for (int k = rp[i]; k < rp[i + 1]; ++k) {
+                const int j = ci[k];
+                if (j == i || (strong && !strong[k]) || agg1[j] < 0) continue;
+                const double w = fabs(v[k]);
+                if (w > best || (w == best && cid[j] < bc)) { best = w; bc = cid[j]; a = agg1[j]; }
+            }
+            if (a < 0) atomicOr(bad, 2);
+        }
+        agg[i] = a < 0 ? 0 : a;
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_agg_size(int64_t n, const int32_t *__restrict__ agg, int32_t *__restrict__ size) {
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) atomicAdd(&size[agg[i]], 1);   // (integers)
+}
+
+// T as CSR: one entry per row
+__global__ __launch_bounds__(kBlock) void k_tentative(int64_t n, const int32_t *__restrict__ agg, const int32_t *__restrict__ size,
+                                                      int32_t *__restrict__ rp, int32_t *__restrict__ ci, double *__restrict__ v) {
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i <= n; i += stride) {
+        rp[i] = (int32_t)i;
+        if (i < n) {
+            ci[i] = agg[i];
+            v[i] = 1.0 / sqrt((double)size[agg[i]]);
+        }
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_diff_i32(int64_t n, const int32_t *__restrict__ a, const int32_t *__restrict__ b, int *diff) {
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride)
+        if (a[i] != b[i]) atomicOr(diff, 1);
+}
+
+// ---- row-wise SpGEMM C = X Y ------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void k_sg_products(int64_t m, const int32_t *__restrict__ xrp, const int32_t *__restrict__ xci,
+                                                        const int32_t *__restrict__ yrp, int32_t *__restrict__ cnt,
+                                                        int32_t *__restrict__ long_pad) {
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < m; i += stride) {
+        int64_t c = 0;
+        for (int k = xrp[i]; k < xrp[i + 1]; ++k) c += yrp[xci[k] + 1] - yrp[xci[k]];
+        cnt[i] = (int32_t)std::min<int64_t>(c, 0x7fffffff);
+        int64_t p = 1;
+        while (p < c) p <<= 1;
+        long_pad[i] = c > kSgCap ? (int32_t)std::min<int64_t>(p, 0x40000000) : 0;
+    }
+}
+
+enum SgMode { SG_COUNT = 0, SG_NUMERIC = 1 };
+enum SgEpi { SG_PLAIN = 0, SG_SMOOTH = 1 };   // SG_SMOOTH: c_ij = [j == agg_i] t_i - (omega dinv_i) (X Y)_ij  (P from A and T)
+
+template <int MODE, int EPI>
+__global__ __launch_bounds__(64) void k_spgemm(int64_t m, const int32_t *__restrict__ xrp, const int32_t *__restrict__ xci,
+                                               const double *__restrict__ xv, const int32_t *__restrict__ yrp,
+                                               const int32_t *__restrict__ yci, const double *__restrict__ yv,
+                                               const int32_t *__restrict__ cnt, const int32_t *__restrict__ long_off,
+                                               uint64_t *__restrict__ gkey, double *__restrict__ gval,
+                                               const int32_t *__restrict__ crp, int32_t *__restrict__ cci, double *__restrict__ cv,
+                                               int32_t *__restrict__ rowlen, const int32_t *__restrict__ agg,
+                                               const double *__restrict__ tval, const double *__restrict__ dinv, double omega) {
+    __shared__ uint64_t skey[kSgCap];
+    __shared__ double sval[kSgCap];
+    const int lane = threadIdx.x;
+    for (int64_t i = blockIdx.x; i < m; i += gridDim.x) {
+        const int c = cnt[i];
+        uint64_t *key = skey;
+        double *val = sval;
+        if (c > kSgCap) {
+            key = gkey + long_off[i];
+            val = gval + long_off[i];
+        }
+        int m2 = 1;
+        while (m2 < c) m2 <<= 1;
+        // expand in product order
+        int base = 0;
+        for (int kk = xrp[i]; kk < xrp[i + 1]; ++kk) {
+            const int k = xci[kk];
+            const double xk = MODE == SG_NUMERIC ? xv[kk] : 0.0;
+            const int y0 = yrp[k], len = yrp[k + 1] - y0;
+            for (int t = lane; t < len; t += 64) {
+                key[base + t] = ((uint64_t)(uint32_t)yci[y0 + t] << 32) | (uint32_t)(base + t);
+                if (MODE == SG_NUMERIC) val[base + t] = xk * yv[y0 + t];
+            }
+            base += len;
+        }
+        for (int t = c + lane; t < m2; t += 64) key[t] = ~0ull;
+        __syncthreads();
+        // bitonic sort of key (val carried along)
+        for (int size = 2; size <= m2; size <<= 1) {
+            for (int half = size >> 1; half > 0; half >>= 1) {
+                for (int t = lane; t < m2; t += 64) {
+                    const int u = t ^ half;
+                    if (u > t) {
+                        const bool up = (t & size) == 0;
+                        const uint64_t a = key[t], b = key[u];
+                        if ((a > b) == up) {
+                            key[t] = b;
+                            key[u] = a;
+                            if (MODE == SG_NUMERIC) {
+                                const double va = val[t];
+                                val[t] = val[u];
+                                val[u] = va;
+                            }
+                        }
+                    }
+                }
+                __syncthreads();
+            }
+        }
+        // compress: one output entry per distinct column
+        int off = 0;
+        const int out0 = MODE == SG_NUMERIC ? crp[i] : 0;
+        for (int j0 = 0; j0 < c; j0 += 64) {
+            const int j = j0 + lane;
+            const bool head = j < c && (j == 0 || (key[j] >> 32) != (key[j - 1] >> 32));
+            const unsigned long long mask = __ballot(head);
+            if (MODE == SG_NUMERIC && head) {
+                const int pos = off + __popcll(mask & ((1ull << lane) - 1ull));
+                const uint32_t col = (uint32_t)(key[j] >> 32);
+                double sum = val[j];
+                for (int q = j + 1; q < c && (uint32_t)(key[q] >> 32) == col; ++q) sum += val[q];
+                double out = sum;
+                if (EPI == SG_SMOOTH) out = ((int)col == agg[i] ? tval[i] : 0.0) - (omega * dinv[i]) * sum;
+                cci[out0 + pos] = (int32_t)col;
+                cv[out0 + pos] = out;
+            }
+            off += __popcll(mask);
+        }
+        if (MODE == SG_COUNT && lane == 0) rowlen[i] = off;
+        __syncthreads();
+    }
+}
+
+__global__ void k_set_last(int32_t *rp, int64_t n) { rp[n] = 0; }
+
+// ---- apply kernels ------------------------------------------------------------------------------------------------------
+enum AmgOp { OP_PRE = 0, OP_SWEEP = 1, OP_POST = 2, OP_ACC = 3, OP_PLAIN = 4 };
+
+// One row per TPR lanes.  y_j is what the row gathers:
+//   PRE    y_j = omega dinv_j b_j;         x_i = y_i,  r_i = b_i - sum a_ij y_j
+//   SWEEP  y_j = x_j + omega dinv_j r_j;   x'_i = y_i, r'_i = b_i - sum a_ij y_j
+//   POST   y_j = x_j;                      x'_i = x_i + omega dinv_i (b_i - sum a_ij y_j)   [part: <b, x'> per workgroup]
+//   ACC    y_j = u_j;                      x'_i = x_i + sum a_ij y_j          (a = P)
+//   PLAIN  y_j = u_j;                      x'_i = sum a_ij y_j                (a = P^T)
+template <int OP, int TPR>
+__global__ __launch_bounds__(kBlock) void k_amg_row(int64_t n, const int32_t *__restrict__ rp, const int32_t *__restrict__ ci,
+                                                    const double *__restrict__ av, const double *__restrict__ dinv, double omega,
+                                                    const double *__restrict__ b, const double *__restrict__ xin,
+                                                    const double *__restrict__ rin, const double *__restrict__ u,
+                                                    double *__restrict__ xout, double *__restrict__ rout, double *__restrict__ part,
+                                                    const int *__restrict__ done) {
+    if (done && *done) return;        // (in the PCG loop: the updates enqueued beyond convergence cost a launch each, not a cycle)
+    constexpr int RPB = kBlock / TPR;
+    const int sub = threadIdx.x % TPR;
+    double acc = 0.0;
+    for (int64_t row0 = (int64_t)blockIdx.x * RPB; row0 < n; row0 += (int64_t)gridDim.x * RPB) {
+        const int64_t i = row0 + threadIdx.x / TPR;
+        double s = 0.0;
+        if (i < n) {
+            for (int k = rp[i] + sub; k < rp[i + 1]; k += TPR) {
+                const int j = ci[k];
+                double y;
+                if (OP == OP_PRE) y = omega * dinv[j] * b[j];
+                else if (OP == OP_SWEEP) y = xin[j] + omega * dinv[j] * rin[j];
+                else if (OP == OP_POST) y = xin[j];
+                else y = u[j];
+                s += av[k] * y;
+            }
+        }
+#pragma unroll
+        for (int w = 1; w < TPR; w <<= 1) s += __shfl_xor(s, w, TPR);
+        if (i < n && sub == 0) {
+            if (OP == OP_PRE) {
+                xout[i] = omega * dinv[i] * b[i];
+                rout[i] = b[i] - s;
+            } else if (OP == OP_SWEEP) {
+                xout[i] = xin[i] + omega * dinv[i] * rin[i];
+                rout[i] = b[i] - s;
+            } else if (OP == OP_POST) {
+                const double x = xin[i] + omega * dinv[i] * (b[i] - s);
+                xout[i] = x;
+                if (part) acc += b[i] * x;
+            } else if (OP == OP_ACC) {
+                xout[i] = xin[i] + s;
+            } else {
+                xout[i] = s;
+            }
+        }
+    }
+    if (OP == OP_POST && part) {   // fixed-order workgroup sum (rows are owned by lanes sub == 0; the others hold 0)
+        __shared__ double red[kBlock / 64];
+        const double w = wave_sum(acc);
+        if ((threadIdx.x & 63) == 63) red[threadIdx.x >> 6] = w;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            double t = 0.0;
+            for (int q = 0; q < kBlock / 64; ++q) t += red[q];
+            part[blockIdx.x] = t;
+        }
+    }
+}
+
+// x = C b, C dense row-major (nc x nc): one wave per row, fixed-order sums
+__global__ __launch_bounds__(kBlock) void k_amg_gemv(int64_t nc, const double *__restrict__ C, const double *__restrict__ b,
+                                                     double *__restrict__ x, const int *__restrict__ done) {
+    if (done && *done) return;
+    const int lane = threadIdx.x & 63;
+    for (int64_t i = ((int64_t)blockIdx.x * kBlock + threadIdx.x) >> 6; i < nc; i += ((int64_t)gridDim.x * kBlock) >> 6) {
+        double s = 0.0;
+        for (int64_t j = lane; j < nc; j += 64) s += C[i * nc + j] * b[j];
+        s = wave_sum(s);
+        if (lane == 63) x[i] = s;
+    }
+}
+
+int tpr_for(const CsrDev &A) {
+    const double mean = A.n > 0 ? (double)A.nnz / (double)A.n : 1.0;
+    int tpr = 2;                      // the planner's rule for its CSR-vector kernel (make_plan)
+    while (tpr < 64 && 2 * tpr < mean) tpr *= 2;
+    return tpr;
+}
+
+template <int OP>
+void launch_row(const CsrDev &A, int tpr, const double *dinv, double omega, const double *b, const double *xin, const double *rin,
+                const double *u, double *xout, double *rout, double *part, int *grid_out, hipStream_t s, const int *done) {
+    const int rpb = kBlock / tpr;
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((A.n + rpb - 1) / rpb, kApplyMaxGrid));
+    if (grid_out) *grid_out = grid;
+#define AMG_ROW(T)                                                                                                           \
+    case T:                                                                                                                  \
+        hipLaunchKernelGGL((k_amg_row<OP, T>), dim3(grid), dim3(kBlock), 0, s, A.n, A.rowptr, A.col, A.val, dinv, omega, b, \
+                           xin, rin, u, xout, rout, part, done);                                                             \
+        break;
+    switch (tpr) { AMG_ROW(2) AMG_ROW(4) AMG_ROW(8) AMG_ROW(16) AMG_ROW(32) default: AMG_ROW(64) }
+#undef AMG_ROW
+}
+
+// ---- host helpers ---------------------------------------------------------------------------------------------------
+template <typename T>
+int read1(const T *dev, T *host, hipStream_t s) {
+    DPCG_HIP(hipMemcpyAsync(host, dev, sizeof(T), hipMemcpyDeviceToHost, s));
+    DPCG_HIP(hipStreamSynchronize(s));
+    return DPCG_OK;
+}
+
+void free_level(AmgLevel &L, bool keep_a) {
+    if (!keep_a) free_csr(L.A);
+    dev_free(L.dinv);
+    dev_free(L.strong);
+    dev_free(L.roots);
+    dev_free(L.agg);
+    free_csr(L.P);
+    free_csr(L.Pt);
+    free_csr(L.AP);
+    dev_free(L.pt_order);
+    dev_free(L.b); dev_free(L.xa); dev_free(L.xb); dev_free(L.ra); dev_free(L.rb);
+    L = AmgLevel();
+}
+
+// scoped temporaries of the setup (freed on every return path)
+struct Tmp {
+    std::vector<void *> blocks;
+    template <typename T>
+    int alloc(T **p, int64_t count) {
+        DPCG_TRY(dev_alloc(p, count));
+        blocks.push_back(*p);
+        return DPCG_OK;
+    }
+    ~Tmp() {
+        for (void *p : blocks) cached_free(p);
+    }
+};
+
+// an owned CSR matrix that is freed unless released (a Galerkin product in flight between two levels)
+struct CsrOwner {
+    CsrDev c;
+    ~CsrOwner() { free_csr(c); }
+};
+
+// C = X Y (X: m rows, Y: ncols columns).  C.rowptr / C.col given (same pattern as before): numeric pass only.
+int spgemm(const CsrDev &X, const CsrDev &Y, int64_t ncols, CsrDev &C, int epi, const int32_t *agg, const double *tval,
+           const double *dinv, double omega, hipStream_t s) {
+    const int64_t m = X.n;
+    Tmp t;
+    int32_t *cnt = nullptr, *lpad = nullptr, *loff = nullptr;
+    DPCG_TRY(t.alloc(&cnt, m));
+    DPCG_TRY(t.alloc(&lpad, m + 1));
+    DPCG_TRY(t.alloc(&loff, m + 1));
+    hipLaunchKernelGGL(k_sg_products, dim3(grid_of(m)), dim3(kBlock), 0, s, m, X.rowptr, X.col, Y.rowptr, cnt, lpad);
+    hipLaunchKernelGGL(k_set_last, dim3(1), dim3(1), 0, s, lpad, m);
+    DPCG_TRY(exclusive_scan_i32(lpad, loff, m + 1, s));
+    int32_t scratch = 0;
+    DPCG_TRY(read1(loff + m, &scratch, s));
+    if (scratch < 0) {
+        set_error("dpcg_set_precond_amg: the long rows of a Galerkin product need more than 2^31 scratch entries");
+        return DPCG_ERR_INVALID;
+    }
+    uint64_t *gkey = nullptr;
+    double *gval = nullptr;
+    DPCG_TRY(t.alloc(&gkey, std::max<int64_t>(1, scratch)));
+    DPCG_TRY(t.alloc(&gval, std::max<int64_t>(1, scratch)));
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(m, 1 << 20));
+    const bool symbolic = C.rowptr == nullptr;
+    if (symbolic) {
+        C = CsrDev();
+        C.n = m;
+        C.owned = true;
+        int32_t *len = nullptr;
+        DPCG_TRY(t.alloc(&len, m + 1));
+        DPCG_TRY(dev_alloc(&C.rowptr, m + 1));
+        hipLaunchKernelGGL((k_spgemm<SG_COUNT, SG_PLAIN>), dim3(grid), dim3(64), 0, s, m, X.rowptr, X.col, X.val, Y.rowptr, Y.col,
+                           Y.val, cnt, loff, gkey, gval, nullptr, nullptr, nullptr, len, nullptr, nullptr, nullptr, 0.0);
+        hipLaunchKernelGGL(k_set_last, dim3(1), dim3(1), 0, s, len, m);
+        DPCG_TRY(exclusive_scan_i32(len, C.rowptr, m + 1, s));
+        int32_t nnz = 0;
+        DPCG_TRY(read1(C.rowptr + m, &nnz, s));
+        if (nnz < 0) {
+            set_error("dpcg_set_precond_amg: a Galerkin product has more than 2^31 entries");
+            return DPCG_ERR_INVALID;
+        }
+        C.nnz = nnz;
+        DPCG_TRY(dev_alloc(&C.col, std::max<int64_t>(1, nnz)));
+        DPCG_TRY(dev_alloc(&C.val, std::max<int64_t>(1, nnz)));
+    }
+    (void)ncols;
+    if (epi == SG_SMOOTH)
+        hipLaunchKernelGGL((k_spgemm<SG_NUMERIC, SG_SMOOTH>), dim3(grid), dim3(64), 0, s, m, X.rowptr, X.col, X.val, Y.rowptr, Y.col,
+                           Y.val, cnt, loff, gkey, gval, C.rowptr, C.col, C.val, nullptr, agg, tval, dinv, omega);
+    else
+        hipLaunchKernelGGL((k_spgemm<SG_NUMERIC, SG_PLAIN>), dim3(grid), dim3(64), 0, s, m, X.rowptr, X.col, X.val, Y.rowptr, Y.col,
+                           Y.val, cnt, loff, gkey, gval, C.rowptr, C.col, C.val, nullptr, nullptr, nullptr, nullptr, 0.0);
+    DPCG_CHECK_LAUNCH();
+    DPCG_HIP(hipStreamSynchronize(s));
+    return DPCG_OK;
+}
+
+// P^T (nc x n) by a stable sort of P's entries by column; `order` (entry of P^T -> entry of P) kept for a values-only refresh
+int transpose_p(const CsrDev &P, int64_t nc, CsrDev &Pt, int32_t **order_io, hipStream_t s) {
+    const int64_t nnz = P.nnz;
+    Tmp t;
+    int32_t *row_of = nullptr;
+    DPCG_TRY(t.alloc(&row_of, nnz));
+    launch_row_of(P.n, P.rowptr, row_of, s);
+    if (!*order_io) {
+        int32_t *iota = nullptr;
+        uint32_t *keys = nullptr;
+        DPCG_TRY(t.alloc(&iota, nnz));
+        DPCG_TRY(t.alloc(&keys, nnz));
+        DPCG_TRY(dev_alloc(order_io, nnz));
+        launch_iota(nnz, iota, s);
+        DPCG_TRY(sort_pairs_u32_i32(reinterpret_cast<const uint32_t *>(P.col), keys, iota, *order_io, nnz,
+                                    bits_for((uint64_t)std::max<int64_t>(1, nc - 1)), s));
+        free_csr(Pt);
+        Pt.n = nc;
+        Pt.nnz = nnz;
+        Pt.owned = true;
+        DPCG_TRY(dev_alloc(&Pt.rowptr, nc + 1));
+        DPCG_TRY(dev_alloc(&Pt.col, nnz));
+        DPCG_TRY(dev_alloc(&Pt.val, nnz));
+        launch_group_offsets(nnz, keys, (int)nc, Pt.rowptr, s);
+    }
+    launch_transpose_gather(nnz, *order_io, row_of, P.val, Pt.col, Pt.val, s);
+    DPCG_HIP(hipStreamSynchronize(s));
+    return DPCG_OK;
+}
+
+// rho = theta_max + err_max of a kRhoSteps-step Lanczos estimate of the spectrum of D^-1 A_l, on a handle that borrows A_l
+int estimate_rho(const CsrDev &A, const int32_t *perm, uint64_t seed, double *rho, hipStream_t s) {
+    dpcg_handle_t t = nullptr;
+    DPCG_TRY(dpcg_create(&t, A.n, A.nnz, A.rowptr, A.col, A.val, DPCG_F64, DPCG_DEVICE, 0, (dpcg_stream_t)s));
+    int st = dpcg_set_precond_jacobi(t, nullptr, DPCG_DEVICE, (dpcg_stream_t)s);
+    int steps = 0;
+    double tmin = 0, tmax = 0, emin = 0, emax = 0;
+    if (st >= 0) {
+        t->perm = const_cast<int32_t *>(perm);       // (the start vector hashes the caller's row index)
+        st = dpcg_spectrum(t, kRhoSteps, 0.0, seed, (dpcg_stream_t)s, &steps, &tmin, &tmax, &emin, &emax, nullptr, nullptr);
+        t->perm = nullptr;
+    }
+    dpcg_destroy(t);
+    if (st < 0) return st;
+    if (st == DPCG_BREAKDOWN || !(tmax > 0.0) || !std::isfinite(tmax + emax)) {
+        set_error("dpcg_set_precond_amg: the spectral-radius estimate of D^-1 A broke down (A is not symmetric positive definite)");
+        return DPCG_ERR_PIVOT;
+    }
+    *rho = tmax + emax;
+    return DPCG_OK;
+}
+
+// Dense inverse of the coarsest matrix by Cholesky on the host
+int coarse_inverse(const CsrDev &A, int level, double **cinv, hipStream_t s) {
+    const int64_t n = A.n;
+    std::vector<int32_t> rp(n + 1), ci(A.nnz);
+    std::vector<double> v(A.nnz);
+    DPCG_HIP(hipMemcpyAsync(rp.data(), A.rowptr, (n + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    DPCG_HIP(hipMemcpyAsync(ci.data(), A.col, A.nnz * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    DPCG_HIP(hipMemcpyAsync(v.data(), A.val, A.nnz * sizeof(double), hipMemcpyDeviceToHost, s));
+    DPCG_HIP(hipStreamSynchronize(s));
+    std::vector<double> L((size_t)n * n, 0.0);
+    for (int64_t i = 0; i < n; ++i)
+        for (int k = rp[i]; k < rp[i + 1]; ++k) L[(size_t)i * n + ci[k]] += v[k];
+    for (int64_t j = 0; j < n; ++j) {                  // in place, lower triangle
+        double d = L[(size_t)j * n + j];
+        for (int64_t k = 0; k < j; ++k) d -= L[(size_t)j * n + k] * L[(size_t)j * n + k];
+        if (!(d > 0.0) || !std::isfinite(d)) {
+            char buf[200];
+            snprintf(buf, sizeof(buf), "dpcg_set_precond_amg: the coarsest matrix (level %d, %lld rows) is not positive definite "
+                     "(pivot %lld)", level, (long long)n, (long long)j);
+            set_error(buf);
+            return DPCG_ERR_PIVOT;
+        }
+        d = std::sqrt(d);
+        L[(size_t)j * n + j] = d;
+        for (int64_t i = j + 1; i < n; ++i) {
+            double a = L[(size_t)i * n + j];
+            for (int64_t k = 0; k < j; ++k) a -= L[(size_t)i * n + k] * L[(size_t)j * n + k];
+            L[(size_t)i * n + j] = a / d;
+        }
+    }
+    // W = L^-1 (lower triangular) row by row, W[i, :] = (e_i - sum_{k<i} L_ik W[k, :]) / L_ii, and C = W^T W accumulated row by
+    // row of W: every inner loop runs along a contiguous row (n^3 / 6 multiply-adds each; a few seconds at the 4096-row limit)
+    std::vector<double> W((size_t)n * n, 0.0);
+    for (int64_t i = 0; i < n; ++i) {
+        double *wi = &W[(size_t)i * n];
+        wi[i] = 1.0;
+        for (int64_t k = 0; k < i; ++k) {
+            const double a = L[(size_t)i * n + k];
+            if (a == 0.0) continue;
+            const double *wk = &W[(size_t)k * n];
+            for (int64_t j = 0; j <= k; ++j) wi[j] -= a * wk[j];
+        }
+        const double d = L[(size_t)i * n + i];
+        for (int64_t j = 0; j <= i; ++j) wi[j] /= d;
+    }
+    std::vector<double> C((size_t)n * n, 0.0);        // lower triangle of W^T W, then mirrored
+    for (int64_t k = 0; k < n; ++k) {
+        const double *wk = &W[(size_t)k * n];
+        for (int64_t i = 0; i <= k; ++i) {
+            const double a = wk[i];
+            if (a == 0.0) continue;
+            double *ci = &C[(size_t)i * n];
+            for (int64_t j = 0; j <= i; ++j) ci[j] += a * wk[j];
+        }
+    }
+    for (int64_t i = 0; i < n; ++i)
+        for (int64_t j = 0; j < i; ++j) C[(size_t)j * n + i] = C[(size_t)i * n + j];
+    DPCG_TRY(dev_alloc(cinv, n * n));
+    DPCG_HIP(hipMemcpyAsync(*cinv, C.data(), (size_t)n * n * sizeof(double), hipMemcpyHostToDevice, s));
+    DPCG_HIP(hipStreamSynchronize(s));
+    return DPCG_OK;
+}
+
+int alloc_work(AmgLevel &L, bool coarse, int sweeps) {
+    const int64_t n = L.A.n;
+    DPCG_TRY(dev_alloc(&L.b, n));
+    DPCG_TRY(dev_alloc(&L.xa, n));
+    if (coarse) return DPCG_OK;
+    DPCG_TRY(dev_alloc(&L.xb, n));
+    DPCG_TRY(dev_alloc(&L.ra, n));
+    if (sweeps > 1) DPCG_TRY(dev_alloc(&L.rb, n));
+    return DPCG_OK;
+}
+
+void free_state(AmgState *S) {
+    if (!S) return;
+    for (AmgLevel &L : S->lv) free_level(L, false);
+    S->lv.clear();
+    dev_free(S->cinv);
+}
+
+int level_error(int status, int level, const char *what) {
+    char buf[256];
+    snprintf(buf, sizeof(buf), "dpcg_set_precond_amg: level %d: %s", level, what);
+    set_error(buf);
+    return status;
+}
+
+// MIS(2) of the strong graph of level L: L.roots (1 = root)
+int mis2(AmgLevel &L, const int32_t *perm, uint64_t seed, int *flags, int8_t *st, uint64_t *hsh, int32_t *cid, hipStream_t s) {
+    const int64_t n = L.A.n;
+    Tmp t;
+    int8_t *st2 = nullptr;
+    int32_t *m1 = nullptr, *m2 = nullptr;
+    DPCG_TRY(t.alloc(&st2, n));
+    DPCG_TRY(t.alloc(&m1, n));
+    DPCG_TRY(t.alloc(&m2, n));
+    const int g = grid_of(n);
+    for (int round = 0;; ++round) {
+        if (round > 100000) return invalid("dpcg_set_precond_amg: MIS(2) did not terminate");
+        hipLaunchKernelGGL(k_mis_max, dim3(g), dim3(kBlock), 0, s, n, L.A.rowptr, L.A.col, L.strong, st, hsh, cid, nullptr, m1);
+        hipLaunchKernelGGL(k_mis_max, dim3(g), dim3(kBlock), 0, s, n, L.A.rowptr, L.A.col, L.strong, st, hsh, cid, m1, m2);
+        DPCG_HIP(hipMemsetAsync(flags, 0, sizeof(int), s));
+        hipLaunchKernelGGL(k_mis_update, dim3(g), dim3(kBlock), 0, s, n, st, m2, st2, flags);
+        DPCG_HIP(hipMemcpyAsync(st, st2, (size_t)n, hipMemcpyDeviceToDevice, s));
+        int left = 0;
+        DPCG_TRY(read1(flags, &left, s));
+        if (!left) break;
+    }
+    (void)perm;
+    (void)seed;
+    DPCG_CHECK_LAUNCH();
+    return DPCG_OK;
+}
+
+// Build the hierarchy; `old` (may be null): a parked hierarchy of the same pattern and parameters, whose pattern-only parts are taken
+// over: level by level, while the aggregates come out the same as the parked ones, the structures of P, A P, P^T (with its sort order)
+// and A_{l+1}; only their values are computed again.  (The aggregates themselves are recomputed: the far rule looks at values, and an
+// entry that cancels to zero leaves the strength graph.)
+int build(dpcg_system *h, AmgState &S, AmgState *old, hipStream_t s) {
+    PhaseTimer pt(s);
+    Tmp keep;
+    int *flags = nullptr;
+    DPCG_TRY(keep.alloc(&flags, 2));
+    bool reuse = old != nullptr;
+    CsrOwner next_owner;                            // A_{l+1} as the Galerkin product of level l left it (freed on an error return)
+    CsrDev &nextA = next_owner.c;
+    for (int l = 0;; ++l) {
+        S.lv.emplace_back();
+        AmgLevel &L = S.lv.back();
+        AmgLevel *O = (reuse && l < (int)old->lv.size()) ? &old->lv[l] : nullptr;
+        if (l == 0) {
+            L.A = h->A;
+            L.A.owned = false;
+            L.A.val32 = nullptr;
+        } else {
+            L.A = nextA;
+            nextA = CsrDev();
+        }
+        const int64_t n = L.A.n;
+        const int g = grid_of(n);
+        Tmp t;
+        double *diag = nullptr;
+        DPCG_TRY(dev_alloc(&L.dinv, n));
+        DPCG_TRY(t.alloc(&diag, n));
+        DPCG_HIP(hipMemsetAsync(flags, 0, 2 * sizeof(int), s));
+        hipLaunchKernelGGL(k_amg_diag, dim3(g), dim3(kBlock), 0, s, n, L.A.rowptr, L.A.col, L.A.val, L.dinv, diag, flags);
+        int bad = 0;
+        DPCG_TRY(read1(flags, &bad, s));
+        if (bad) return level_error(DPCG_ERR_PIVOT, l, "a diagonal entry is missing, zero, negative or not finite");
+        bool coarsest = n <= S.max_coarse || l == S.max_levels - 1;
+        int32_t *cid = nullptr, *flag_by_cid = nullptr, *rank = nullptr;
+        int64_t nc = 0;
+        if (!coarsest) {
+            DPCG_TRY(dev_alloc(&L.strong, std::max<int64_t>(1, L.A.nnz)));
+            hipLaunchKernelGGL(k_amg_strength, dim3(g), dim3(kBlock), 0, s, n, L.A.rowptr, L.A.col, L.A.val, diag, S.theta, L.strong);
+            int8_t *st = nullptr;
+            uint64_t *hsh = nullptr;
+            DPCG_TRY(t.alloc(&st, n));
+            DPCG_TRY(t.alloc(&hsh, n));
+            DPCG_TRY(t.alloc(&cid, n));
+            const int32_t *perm = l == 0 ? h->perm : nullptr;
+            hipLaunchKernelGGL(k_mis_init, dim3(g), dim3(kBlock), 0, s, n, (unsigned long long)S.seed, perm, st, hsh, cid);
+            DPCG_TRY(t.alloc(&flag_by_cid, n + 1));
+            DPCG_TRY(t.alloc(&rank, n + 1));
+            DPCG_TRY(dev_alloc(&L.roots, n));
+            DPCG_TRY(mis2(L, perm, S.seed, flags, st, hsh, cid, s));
+            hipLaunchKernelGGL(k_root_flags, dim3(g), dim3(kBlock), 0, s, n, st, cid, L.roots, flag_by_cid);
+            hipLaunchKernelGGL(k_set_last, dim3(1), dim3(1), 0, s, flag_by_cid, n);
+            DPCG_TRY(exclusive_scan_i32(flag_by_cid, rank, n + 1, s));
+            int32_t nc32 = 0;
+            DPCG_TRY(read1(rank + n, &nc32, s));
+            nc = nc32;
+            if (nc <= 0 || (double)nc > 0.9 * (double)n) coarsest = true;      // coarsening stalls
+            pt.mark("amg: strength + MIS(2)");
+        }
+        if (coarsest) {
+            dev_free(L.strong);
+            dev_free(L.roots);
+            if (n > 4096) {
+                char buf[200];
+                snprintf(buf, sizeof(buf), "the coarsest level has %lld rows (at most 4096 are solved densely): raise max_levels or "
+                         "max_coarse's reach", (long long)n);
+                return level_error(DPCG_ERR_INVALID, l, buf);
+            }
+            DPCG_TRY(coarse_inverse(L.A, l, &S.cinv, s));
+            S.nco = n;
+            DPCG_TRY(alloc_work(L, true, S.sweeps));
+            pt.mark("amg: coarse inverse");
+            break;
+        }
+        L.nc = nc;
+        // aggregates
+        int32_t *agg1 = nullptr;
+        DPCG_TRY(t.alloc(&agg1, n));
+        DPCG_TRY(dev_alloc(&L.agg, n));
+        hipLaunchKernelGGL(k_agg_near, dim3(g), dim3(kBlock), 0, s, n, L.A.rowptr, L.A.col, L.strong, L.roots, cid, rank, agg1);
+        DPCG_HIP(hipMemsetAsync(flags, 0, sizeof(int), s));
+        hipLaunchKernelGGL(k_agg_far, dim3(g), dim3(kBlock), 0, s, n, L.A.rowptr, L.A.col, L.A.val, L.strong, cid, agg1, L.agg, flags);
+        DPCG_TRY(read1(flags, &bad, s));
+        if (bad) return level_error(DPCG_ERR_STATE, l, "a row was left without an aggregate");
+        bool same = false;
+        if (O && O->agg && O->nc == nc && O->P.rowptr) {
+            DPCG_HIP(hipMemsetAsync(flags, 0, sizeof(int), s));
+            hipLaunchKernelGGL(k_diff_i32, dim3(g), dim3(kBlock), 0, s, n, L.agg, O->agg, flags);
+            int diff = 1;
+            DPCG_TRY(read1(flags, &diff, s));
+            same = diff == 0 && l + 1 < (int)old->lv.size() && old->lv[l + 1].A.rowptr;
+        }
+        if (same) {                                 // the pattern of P, A P, P^T and A_{l+1} is the parked one: values only
+            ++S.reused_levels;
+            L.P = O->P; O->P = CsrDev();
+            L.AP = O->AP; O->AP = CsrDev();
+            L.Pt = O->Pt; O->Pt = CsrDev();
+            L.pt_order = O->pt_order; O->pt_order = nullptr;
+            nextA = old->lv[l + 1].A; old->lv[l + 1].A = CsrDev();
+        } else {
+            reuse = false;
+        }
+        // tentative prolongator and the spectral radius of D^-1 A
+        CsrDev T;
+        int32_t *size = nullptr;
+        DPCG_TRY(t.alloc(&size, nc));
+        DPCG_TRY(t.alloc(&T.rowptr, n + 1));
+        DPCG_TRY(t.alloc(&T.col, n));
+        DPCG_TRY(t.alloc(&T.val, n));
+        T.n = n;
+        T.nnz = n;
+        DPCG_HIP(hipMemsetAsync(size, 0, (size_t)nc * sizeof(int32_t), s));
+        hipLaunchKernelGGL(k_agg_size, dim3(g), dim3(kBlock), 0, s, n, L.agg, size);
+        hipLaunchKernelGGL(k_tentative, dim3(grid_of(n + 1)), dim3(kBlock), 0, s, n, L.agg, size, T.rowptr, T.col, T.val);
+        pt.mark("amg: aggregates");
+        DPCG_TRY(estimate_rho(L.A, l == 0 ? h->perm : nullptr, S.seed, &L.rho, s));
+        L.omega = (4.0 / 3.0) / L.rho;
+        pt.mark("amg: rho (Lanczos)");
+        // P = (I - omega D^-1 A) T, A P, P^T, A_{l+1} = P^T (A P)
+        DPCG_TRY(spgemm(L.A, T, nc, L.P, SG_SMOOTH, L.agg, T.val, L.dinv, L.omega, s));
+        DPCG_TRY(spgemm(L.A, L.P, nc, L.AP, SG_PLAIN, nullptr, nullptr, nullptr, 0.0, s));
+        DPCG_TRY(transpose_p(L.P, nc, L.Pt, &L.pt_order, s));
+        DPCG_TRY(spgemm(L.Pt, L.AP, nc, nextA, SG_PLAIN, nullptr, nullptr, nullptr, 0.0, s));
+        pt.mark("amg: Galerkin product");
+        L.tpr_a = tpr_for(L.A);
+        L.tpr_p = tpr_for(L.P);
+        L.tpr_pt = tpr_for(L.Pt);
+        DPCG_TRY(alloc_work(L, false, S.sweeps));
+        if (l == 0) dev_free(L.b);                  // (level 0's right-hand side is the caller's r)
+    }
+    return DPCG_OK;
+}
+
+}  // namespace
+}  // namespace dpcg
+
+void free_amg(AmgState *&S) {
+    if (!S) return;
+    free_state(S);
+    delete S;
+    S = nullptr;
+}
+
+int amg_launches(const AmgState *S) {
+    if (!S) return 0;
+    return (int)(S->lv.size() - 1) * (2 + 2 * S->sweeps) + 1;
+}
+
+int amg_rz_partials(const AmgState *S) {
+    if (!S || S->lv.size() < 2) return 0;
+    const AmgLevel &L = S->lv[0];
+    const int rpb = kBlock / L.tpr_a;
+    return (int)std::max<int64_t>(1, std::min<int64_t>((L.A.n + rpb - 1) / rpb, kApplyMaxGrid));
+}
+
+int64_t amg_nnz(const AmgState *S) {
+    if (!S) return 0;
+    int64_t t = 0;
+    for (const AmgLevel &L : S->lv) t += L.A.nnz + 2 * L.P.nnz;
+    return t;
+}
+
+// z = M r by one V(nu, nu) cycle; r, z in the handle's numbering (distinct buffers).  part_rz: the last post-smoothing pass of
+// level 0 leaves its per-workgroup partials of <r, z> there (*n_part_rz of them).  done (may be null): the solve's `done` word --
+// every kernel returns at once once it is set.
+int amg_apply(dpcg_system *h, const double *r, double *z, hipStream_t s, double *part_rz, int *n_part_rz, const int *done) {
+    AmgState &S = *h->amg;
+    const int Lc = (int)S.lv.size() - 1;
+    const int nu = S.sweeps;
+    if (n_part_rz) *n_part_rz = 0;
+    if (Lc == 0) {
+        hipLaunchKernelGGL(k_amg_gemv, dim3(grid_of(S.nco * 64)), dim3(kBlock), 0, s, S.nco, S.cinv, r, z, done);
+        return DPCG_OK;
+    }
+    std::vector<double *> x(Lc), alt(Lc);
+    for (int l = 0; l < Lc; ++l) {                    // down: pre-smoothing, residual, restriction
+        AmgLevel &L = S.lv[l];
+        const double *B = l == 0 ? r : L.b;
+        double *xc = L.xa, *xo = L.xb, *rc = L.ra, *ro = L.rb;
+        launch_row<OP_PRE>(L.A, L.tpr_a, L.dinv, L.omega, B, nullptr, nullptr, nullptr, xc, rc, nullptr, nullptr, s, done);
+        for (int k = 1; k < nu; ++k) {
+            launch_row<OP_SWEEP>(L.A, L.tpr_a, L.dinv, L.omega, B, xc, rc, nullptr, xo, ro, nullptr, nullptr, s, done);
+            std::swap(xc, xo);
+            std::swap(rc, ro);
+        }
+        launch_row<OP_PLAIN>(L.Pt, L.tpr_pt, nullptr, 0.0, nullptr, nullptr, nullptr, rc, S.lv[l + 1].b, nullptr, nullptr, nullptr, s, done);
+        x[l] = xc;
+        alt[l] = xo;
+    }
+    hipLaunchKernelGGL(k_amg_gemv, dim3(grid_of(S.nco * 64)), dim3(kBlock), 0, s, S.nco, S.cinv, S.lv[Lc].b, S.lv[Lc].xa, done);
+    const double *xcoarse = S.lv[Lc].xa;
+    for (int l = Lc - 1; l >= 0; --l) {               // up: prolongation with correction, post-smoothing
+        AmgLevel &L = S.lv[l];
+        const double *B = l == 0 ? r : L.b;
+        double *xc = x[l], *xo = alt[l];
+        launch_row<OP_ACC>(L.P, L.tpr_p, nullptr, 0.0, nullptr, xc, nullptr, xcoarse, xo, nullptr, nullptr, nullptr, s, done);
+        std::swap(xc, xo);
+        for (int k = 0; k < nu; ++k) {
+            const bool last = k == nu - 1;
+            double *out = (l == 0 && last) ? z : xo;
+            double *part = (l == 0 && last) ? part_rz : nullptr;
+            int grid = 0;
+            launch_row<OP_POST>(L.A, L.tpr_a, L.dinv, L.omega, B, xc, nullptr, nullptr, out, nullptr, part, &grid, s, done);
+            if (part && n_part_rz) *n_part_rz = grid;
+            if (!(l == 0 && last)) std::swap(xc, xo);
+        }
+        xcoarse = xc;
+    }
+    return DPCG_OK;
+}
+
+extern "C" int dpcg_set_precond_amg(dpcg_handle_t h, double theta, int max_levels, int max_coarse, int sweeps, uint64_t seed,
+                                    dpcg_stream_t stream) {
+    if (!h) return invalid("NULL handle");
+    if (!(theta >= 0.0 && theta <= 1.0)) return invalid("dpcg_set_precond_amg: theta must lie in [0, 1]");
+    if (max_levels < 1 || max_levels > 64) return invalid("dpcg_set_precond_amg: max_levels must lie in 1 .. 64");
+    if (max_coarse < 1) return invalid("dpcg_set_precond_amg: max_coarse must be >= 1");
+    if (sweeps < 1 || sweeps > 8) return invalid("dpcg_set_precond_amg: sweeps must lie in 1 .. 8");
+    hipStream_t s = (hipStream_t)stream;
+    SetupScope scope(s, true);
+    AmgState *old = h->amg_parked;
+    h->amg_parked = nullptr;
+    free_precond(h);
+    const bool reusable = old && old->theta == theta && old->max_levels == max_levels &&
+                          old->max_coarse == max_coarse && old->seed == seed && !old->lv.empty() && old->lv[0].A.n == h->A.n;
+    AmgState *S = new AmgState();
+    S->theta = theta;
+    S->max_levels = max_levels;
+    S->max_coarse = max_coarse;
+    S->sweeps = sweeps;
+    S->seed = seed;
+    int st = build(h, *S, reusable ? old : nullptr, s);
+    free_amg(old);
+    if (st >= 0) st = ensure_work(h, 0, false, false);
+    if (st < 0) {
+        (void)hipStreamSynchronize(s);
+        free_amg(S);
+        return st;
+    }
+    h->amg = S;
+    h->precond = DPCG_PRECOND_AMG;
+    DPCG_CHECK_LAUNCH();
+    return DPCG_OK;
+}
+
+extern "C" int dpcg_get_amg_info(dpcg_handle_t h, int capacity, int *n_levels, int64_t *rows, int64_t *nnz, int64_t *p_nnz,
+                                 double *rho, double *omega, double *operator_complexity, double *grid_complexity,
+                                 int *reused_levels) {
+    if (!h) return invalid("NULL handle");
+    if (h->precond != DPCG_PRECOND_AMG || !h->amg) {
+        set_error("dpcg_get_amg_info: no smoothed-aggregation preconditioner is attached");
+        return DPCG_ERR_STATE;
+    }
+    const AmgState &S = *h->amg;
+    const int nl = (int)S.lv.size();
+    if (n_levels) *n_levels = nl;
+    if (reused_levels) *reused_levels = S.reused_levels;
+    double sn = 0, sz = 0;
+    for (int l = 0; l < nl; ++l) {
+        const AmgLevel &L = S.lv[l];
+        sn += (double)L.A.n;
+        sz += (double)L.A.nnz;
+        if (l < capacity) {
+            if (rows) rows[l] = L.A.n;
+            if (nnz) nnz[l] = L.A.nnz;
+            if (p_nnz) p_nnz[l] = L.P.nnz;
+            if (rho) rho[l] = L.rho;
+            if (omega) omega[l] = L.omega;
+        }
+    }
+    if (operator_complexity) *operator_complexity = sz / (double)S.lv[0].A.nnz;
+    if (grid_complexity) *grid_complexity = sn / (double)S.lv[0].A.n;
+    return DPCG_OK;
+}
+
+extern "C" int dpcg_get_amg_level(dpcg_handle_t h, int level, const int64_t sizes[4], int32_t *agg, int32_t *p_rowptr, int32_t *p_col,
+                                  double *p_val, int32_t *a_rowptr, int32_t *a_col, double *a_val, dpcg_stream_t stream) {
+    if (!h || !sizes) return invalid("dpcg_get_amg_level: NULL handle or sizes");
+    if (h->precond != DPCG_PRECOND_AMG || !h->amg) {
+        set_error("dpcg_get_amg_level: no smoothed-aggregation preconditioner is attached");
+        return DPCG_ERR_STATE;
+    }
+    const AmgState &S = *h->amg;
+    if (level < 0 || level >= (int)S.lv.size() - 1) return invalid("dpcg_get_amg_level: level must lie in 0 .. levels - 2");
+    const AmgLevel &L = S.lv[level];
+    const AmgLevel &N = S.lv[level + 1];
+    const int64_t n = L.A.n;
+    if (sizes[0] != n || sizes[1] != L.P.nnz || sizes[2] != N.A.n || sizes[3] != N.A.nnz)
+        return invalid("dpcg_get_amg_level: the buffers were sized for another hierarchy (ask dpcg_get_amg_info again)");
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<int32_t> perm, a, rp, ci;
+    std::vector<double> v;
+    if (level == 0 && h->perm) {
+        perm.resize(n);
+        DPCG_HIP(hipMemcpyAsync(perm.data(), h->perm, n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    }
+    if (agg) {
+        a.resize(n);
+        DPCG_HIP(hipMemcpyAsync(a.data(), L.agg, n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    }
+    const bool want_p = p_rowptr || p_col || p_val;
+    if (want_p) {
+        rp.resize(n + 1);
+        ci.resize(L.P.nnz);
+        v.resize(L.P.nnz);
+        DPCG_HIP(hipMemcpyAsync(rp.data(), L.P.rowptr, (n + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        DPCG_HIP(hipMemcpyAsync(ci.data(), L.P.col, L.P.nnz * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        DPCG_HIP(hipMemcpyAsync(v.data(), L.P.val, L.P.nnz * sizeof(double), hipMemcpyDeviceToHost, s));
+    }
+    if (a_rowptr) DPCG_HIP(hipMemcpyAsync(a_rowptr, N.A.rowptr, (N.A.n + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (a_col) DPCG_HIP(hipMemcpyAsync(a_col, N.A.col, N.A.nnz * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (a_val) DPCG_HIP(hipMemcpyAsync(a_val, N.A.val, N.A.nnz * sizeof(double), hipMemcpyDeviceToHost, s));
+    DPCG_HIP(hipStreamSynchronize(s));
+    if (agg)
+        for (int64_t i = 0; i < n; ++i) agg[perm.empty() ? i : perm[i]] = a[i];     // caller numbering at level 0
+    if (want_p) {                                     // rows of P_0 in the caller's numbering
+        std::vector<int32_t> orp(n + 1, 0);
+        std::vector<int64_t> src(n);                  // caller row -> handle row
+        for (int64_t i = 0; i < n; ++i) src[perm.empty() ? i : perm[i]] = i;
+        for (int64_t c = 0; c < n; ++c) orp[c + 1] = orp[c] + (rp[src[c] + 1] - rp[src[c]]);
+        if (p_rowptr) std::copy(orp.begin(), orp.end(), p_rowptr);
+        for (int64_t c = 0; c < n; ++c) {
+            const int64_t i = src[c];
+            for (int k = rp[i], o = orp[c]; k < rp[i + 1]; ++k, ++o) {
+                if (p_col) p_col[o] = ci[k];
+                if (p_val) p_val[o] = v[k];
+            }
+        }
+    }
+    return DPCG_OK;
+}

@@ -349,6 +349,8 @@ void free_precond(dpcg_system *h, bool keep_parked) {
     h->precond_colors = 0;
     h->precond_fn = nullptr;
     h->precond_user = nullptr;
+    free_amg(h->amg);
+    if (!keep_parked) free_amg(h->amg_parked);
     h->precond = DPCG_PRECOND_NONE;
 }
 
@@ -558,6 +560,11 @@ extern "C" int dpcg_update_values(dpcg_handle_t h, const void *val, int val_dtyp
     }
     h->A.val32_lossless = 0;                     // decided again on demand
     if (!h->parked.valid) park_precond(h);
+    if (h->precond == DPCG_PRECOND_AMG && h->amg) {      // a smoothed-aggregation hierarchy keeps what its pattern determined
+        free_amg(h->amg_parked);
+        h->amg_parked = h->amg;
+        h->amg = nullptr;
+    }
     free_precond(h, true);
     free_ell(h->ell_a);
     drop_graph(h);
@@ -615,7 +622,7 @@ extern "C" int dpcg_get_info(dpcg_handle_t h, int64_t *n, int64_t *nnz, int *spm
                        (h->planA.kernel == SPMV_TILE && h->planA.tile_mixed ? 64 : 0) +
                        (h->planA.kernel == SPMV_TILE && h->planA.cyclic ? 128 : 0);
     if (precond_kind) *precond_kind = h->precond;
-    if (precond_nnz) *precond_nnz = h->precond == DPCG_PRECOND_CSR ? h->M.nnz : h->L.nnz;
+    if (precond_nnz) *precond_nnz = h->precond == DPCG_PRECOND_CSR ? h->M.nnz : (h->precond == DPCG_PRECOND_AMG ? amg_nnz(h->amg) : h->L.nnz);
     if ((n_levels_lower || n_levels_upper) && h->lvlL.n_levels < 0) DPCG_TRY(count_levels_on_demand(h));
     if (n_levels_lower) *n_levels_lower = h->lvlL.n_levels;
     if (n_levels_upper) *n_levels_upper = h->lvlU.n_levels;
@@ -711,6 +718,7 @@ int rz_partial_count(const dpcg_system *h) {
     if (h->precond == DPCG_PRECOND_CSR) return h->planM.grid;
     if (h->precond == DPCG_PRECOND_LLT_MULTIPLY) return h->planL.grid;
     if (h->precond == DPCG_PRECOND_LLT_SOLVE && h->lvlU.sweep) return h->lvlU.sweep_grid;   // colour sweeps
+    if (h->precond == DPCG_PRECOND_AMG && amg_rz_partials(h->amg) > 0) return amg_rz_partials(h->amg);   // level 0's last smoothing pass
     return h->vec_grid;
 }
 
@@ -740,6 +748,9 @@ int apply_precond(dpcg_system *h, const double *r, double *z, hipStream_t s, boo
             } else {
                 launch_spmv(h->perm ? h->Lp : h->L, h->planL, h->t, z, nullptr, nullptr, s);
             }
+            break;
+        case DPCG_PRECOND_AMG:                // one V-cycle; its last kernel sums <r, z> on the way when asked to
+            DPCG_TRY(amg_apply(h, r, z, s, part_rz, n_part_rz, in_loop ? &h->scal->done : nullptr));
             break;
         case DPCG_PRECOND_CALLBACK:
             if (h->perm) {                        // the caller's function sees the caller's numbering; t and q (dead

@@ -120,3 +120,10 @@ int apply_precond(dpcg_system *h, const double *r, double *z, hipStream_t s, boo
 // number of <r,z> partials an in-loop apply of the handle's preconditioner leaves (vec_grid when it leaves none)
 int rz_partial_count(const dpcg_system *h);
 int check_spin_errors(dpcg_system *h, hipStream_t s);
+// dpcg_amg.hip: the smoothed-aggregation hierarchy -- free, launches of one V-cycle, sum over levels of nnz(A_l) + 2 nnz(P_l), the apply
+// (part_rz: the last kernel leaves the partials of <r, z>), and how many partials an in-loop apply leaves (0: none)
+void free_amg(AmgState *&S);
+int amg_launches(const AmgState *S);
+int64_t amg_nnz(const AmgState *S);
+int amg_apply(dpcg_system *h, const double *r, double *z, hipStream_t s, double *part_rz, int *n_part_rz, const int *done = nullptr);
+int amg_rz_partials(const AmgState *S);

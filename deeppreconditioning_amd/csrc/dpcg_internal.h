@@ -212,6 +212,8 @@ void launch_fill_pending(double *v, int64_t n, hipStream_t s);
 // largest entry count of the blocks {blk[2b], blk[2b+1]} of a level-ordered copy -> *out_dev (atomicMax)
 void launch_sfs_block_max(const int32_t *blk, int nblk, const int32_t *lo_rowptr, int *out_dev, hipStream_t s);
 
+struct AmgState;   // dpcg_amg.hip: a smoothed-aggregation hierarchy
+
 // (dpcg_chip_trsv.hip; the comment is with ChipTrsvDesc below)
 struct ChipTrsvLists {
     int32_t *first_blk = nullptr, *first_ent = nullptr;     // 2049 each
@@ -260,6 +262,9 @@ struct dpcg_system {
         int32_t *rows_l = nullptr, *rows_u = nullptr;   // level-order position -> factor row, for L and for L^T
     } parked;
     dpcg::SpmvPlan planL, planLt;
+    // DPCG_PRECOND_AMG (dpcg_amg.hip): the hierarchy; amg_parked: the one dpcg_update_values set aside, whose pattern-only parts the
+    // next dpcg_set_precond_amg takes over (any other preconditioner call frees it)
+    dpcg::AmgState *amg = nullptr, *amg_parked = nullptr;
     // dpcg_reorder: the handle iterates on A = P A_user P^T; perm[new] = old, iperm[old] = new (device)
     int32_t *perm = nullptr, *iperm = nullptr;
     dpcg::CsrDev A_user;                  // the caller's matrix once A has been replaced by the reordered one

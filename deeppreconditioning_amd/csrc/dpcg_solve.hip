@@ -155,6 +155,7 @@ static int precond_launches(const dpcg_system *h) {
         case DPCG_PRECOND_CALLBACK: return 1;
         case DPCG_PRECOND_LLT_MULTIPLY: return 2;
         case DPCG_PRECOND_LLT_SOLVE: return trsv(h->lvlL) + trsv(h->lvlU);
+        case DPCG_PRECOND_AMG: return amg_launches(h->amg);
         default: return 0;
     }
 }
@@ -269,6 +270,9 @@ struct Solve {
         const int per_update = 3 + precond_launches(h);
         many_launches = per_update >= 16;
         if (many_launches) chunk = std::max(1, std::min(chunk, 1024 / per_update));   // keep the graph at ~1K nodes
+        // a V-cycle update takes 0.1-0.3 ms at 1M rows and a multigrid solve converges in tens of updates: replayed chunks of two keep
+        // the run-ahead beyond convergence short (its kernels skip once `done` is set, their launches still cost)
+        if (h->precond == DPCG_PRECOND_AMG) chunk = 2;
         if (defer_x && (chunk & 1)) chunk += 1;   // a replayed chunk must start at an even update (p buffer parity)
         use_graph = !(flags & DPCG_NO_GRAPH) && !x_true && max_iter >= chunk && h->precond != DPCG_PRECOND_CALLBACK;
         if (use_graph) {
@@ -547,6 +551,7 @@ extern "C" int dpcg_get_reduction_geometry(dpcg_handle_t h, int32_t out[16]) {
         case DPCG_PRECOND_LLT_SOLVE:
             rzk = h->lvlU.sweep ? 9 : ((h->lvlU.level_major && h->lvlU.strips.n_strips == 0) ? 2 : 1);
             break;
+        case DPCG_PRECOND_AMG: rzk = amg_rz_partials(h->amg) > 0 ? 9 : 1; break;   // (the V-cycle's last smoothing pass)
         default: rzk = 1; break;
     }
     out[9] = out[10] = out[11] = 0;

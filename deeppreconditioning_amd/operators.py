@@ -291,6 +291,80 @@ class ICT(Preconditioner):
         raise TypeError("ICT needs the system matrix: attach it with CsrSystem.set_preconditioner")
 
 
+class SmoothedAggregation(Preconditioner):
+    """Smoothed-aggregation algebraic multigrid applied as one V(sweeps, sweeps) cycle per update -- the reference harness's
+    `algebraic_multigrid` technique (test.py:95-98: pyamg's `smoothed_aggregation_solver(A).aspreconditioner(cycle="V")`), set up
+    and applied on the device (dpcg_set_precond_amg in include/dpcg.h).  The same family as pyamg's default -- symmetric strength
+    with `theta`, MIS(2) aggregation, the Jacobi-smoothed prolongator with omega = (4/3) / rho(D^-1 A), Galerkin coarse operators,
+    an exact solve on the coarsest level -- smoothed by damped Jacobi instead of pyamg's sequential Gauss-Seidel.  Parity with
+    pyamg's own output is not pinned (pyamg is not a dependency); `CsrSystem.amg_hierarchy()` shows what was built."""
+
+    def __init__(self, theta: float = 0.0, max_levels: int = 10, max_coarse: int = 500, sweeps: int = 1, seed: int = 0):
+        if not 0.0 <= float(theta) <= 1.0:
+            raise ValueError("theta must lie in [0, 1]")
+        if not 1 <= int(max_levels) <= 64:
+            raise ValueError("max_levels must lie in 1 .. 64")
+        if int(max_coarse) < 1:
+            raise ValueError("max_coarse must be >= 1")
+        if not 1 <= int(sweeps) <= 8:
+            raise ValueError("sweeps must lie in 1 .. 8")
+        if int(seed) < 0:
+            raise ValueError("seed must be >= 0")
+        self.theta, self.max_levels, self.max_coarse = float(theta), int(max_levels), int(max_coarse)
+        self.sweeps, self.seed = int(sweeps), int(seed)
+
+    def _attach(self, system):
+        L.check(L.lib().dpcg_set_precond_amg(system._h, self.theta, self.max_levels, self.max_coarse, self.sweeps,
+                                             self.seed & (2**64 - 1), _stream()))
+
+    def __matmul__(self, r):
+        raise TypeError("SmoothedAggregation needs the system matrix: attach it with CsrSystem.set_preconditioner")
+
+
+@dataclass
+class AmgLevel:
+    """Level l of a hierarchy: the aggregate of each row (level 0: the caller's numbering), P_l and A_{l+1} as scipy CSR."""
+    aggregates: np.ndarray
+    P: "object"
+    A_next: "object"
+
+
+@dataclass
+class AmgHierarchy:
+    """What `SmoothedAggregation` built (CsrSystem.amg_hierarchy): per level the rows, nnz(A_l), nnz(P_l), rho (the Lanczos estimate
+    of lambda_max(D^-1 A_l)) and omega = (4/3) / rho (0 on the coarsest level, which is solved exactly); the operator and grid
+    complexities; how many levels a re-attach after `update_values` took over from the previous hierarchy (0: built afresh).
+    `level(l)` copies level l out (0 <= l < levels - 1) of the hierarchy attached NOW; it raises when that is no longer the one
+    this snapshot describes (the system was re-attached meanwhile with other sizes)."""
+    levels: int
+    rows: list
+    nnz: list
+    p_nnz: list
+    rho: list
+    omega: list
+    operator_complexity: float
+    grid_complexity: float
+    reused_levels: int = 0
+    _system: "object" = None
+
+    def level(self, l: int) -> AmgLevel:
+        import scipy.sparse as sp
+        if not 0 <= l < self.levels - 1:
+            raise IndexError("level must lie in 0 .. levels - 2")
+        now = self._system.amg_hierarchy()            # the buffers are sized from the hierarchy attached now, never from a stale snapshot
+        n, nc, pn, an = now.rows[l], now.rows[l + 1], now.p_nnz[l], now.nnz[l + 1]
+        if (now.levels, now.rows, now.nnz, now.p_nnz) != (self.levels, self.rows, self.nnz, self.p_nnz):
+            raise RuntimeError("the system's hierarchy was rebuilt since this snapshot: call amg_hierarchy() again")
+        agg = np.empty(n, dtype=np.int32)
+        prp, pci, pv = np.empty(n + 1, dtype=np.int32), np.empty(pn, dtype=np.int32), np.empty(pn)
+        arp, aci, av = np.empty(nc + 1, dtype=np.int32), np.empty(an, dtype=np.int32), np.empty(an)
+        sizes = np.array([n, pn, nc, an], dtype=np.int64)
+        with torch.cuda.device(self._system.device):
+            L.check(L.lib().dpcg_get_amg_level(self._system._h, int(l), _np_ptr(sizes), _np_ptr(agg), _np_ptr(prp), _np_ptr(pci),
+                                               _np_ptr(pv), _np_ptr(arp), _np_ptr(aci), _np_ptr(av), _stream()))
+        return AmgLevel(agg, sp.csr_matrix((pv, pci, prp), shape=(n, nc)), sp.csr_matrix((av, aci, arp), shape=(nc, nc)))
+
+
 class _DevArray:
     """Zero-copy view of a device buffer the library hands to a callback (CUDA array interface, fp64 vector)."""
 
@@ -655,6 +729,20 @@ class CsrSystem:
         k = iters.value
         return SolveResult(x, k, status, res.value, sec.value, hist[: k + 1] if hist is not None else np.empty(0),
                            err[: k + 1] if err is not None else None)
+
+    def amg_hierarchy(self) -> AmgHierarchy:
+        """The smoothed-aggregation hierarchy of the attached `SmoothedAggregation` preconditioner (DpcgError otherwise)."""
+        cap = 64
+        nl = C.c_int(0)
+        rows, nnz, pnnz = np.zeros(cap, dtype=np.int64), np.zeros(cap, dtype=np.int64), np.zeros(cap, dtype=np.int64)
+        rho, omega = np.zeros(cap), np.zeros(cap)
+        oc, gc, reused = C.c_double(), C.c_double(), C.c_int(0)
+        with torch.cuda.device(self.device):
+            L.check(L.lib().dpcg_get_amg_info(self._h, cap, C.byref(nl), _np_ptr(rows), _np_ptr(nnz), _np_ptr(pnnz), _np_ptr(rho),
+                                              _np_ptr(omega), C.byref(oc), C.byref(gc), C.byref(reused)))
+        k = nl.value
+        return AmgHierarchy(k, [int(v) for v in rows[:k]], [int(v) for v in nnz[:k]], [int(v) for v in pnnz[:k]],
+                            [float(v) for v in rho[:k]], [float(v) for v in omega[:k]], oc.value, gc.value, reused.value, self)
 
     def spectrum_bounds(self, *, max_steps: int = 1000, rtol: float = 1e-6, seed: int = 0) -> SpectrumBounds:
         """Extreme eigenvalues of M A for the attached preconditioner M (M = I without one) and kappa = lambda_max / lambda_min,

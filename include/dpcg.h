@@ -52,7 +52,8 @@ enum dpcg_precond {
     DPCG_PRECOND_CSR = 2,          /* z = M r, M an explicit CSR    test.py:88,105 (M = L L^T)      */
     DPCG_PRECOND_LLT_MULTIPLY = 3, /* z = L (L^T r), same operator as test.py:102-105, never formed */
     DPCG_PRECOND_LLT_SOLVE = 4,    /* z = L^-T (L^-1 r), level-scheduled SpTRSV (north_star)        */
-    DPCG_PRECOND_CALLBACK = 5      /* z = M r by a caller-supplied function (the duck-typed `M @ rk`) */
+    DPCG_PRECOND_CALLBACK = 5,     /* z = M r by a caller-supplied function (the duck-typed `M @ rk`) */
+    DPCG_PRECOND_AMG = 6           /* z = M r by one smoothed-aggregation V-cycle  test.py:95-98 (algebraic_multigrid) */
 };
 
 /* dpcg_solve flags */
@@ -185,6 +186,39 @@ int dpcg_set_precond_icholt(dpcg_handle_t h, int mode, int add_fill_in, double t
  * around the call on a reordered handle -- while SpMV, dots and vector updates stay the HIP kernels. */
 typedef void (*dpcg_precond_fn)(void *user, const double *r, double *z, int64_t n, dpcg_stream_t stream);
 int dpcg_set_precond_callback(dpcg_handle_t h, dpcg_precond_fn fn, void *user);
+/* Smoothed-aggregation algebraic multigrid -- the reference harness's `algebraic_multigrid` (test.py:95-98: pyamg's
+ * smoothed_aggregation_solver(A).aspreconditioner(cycle="V")) -- set up on the device and applied as ONE V(sweeps, sweeps) cycle
+ * per update inside the multi-launch PCG loop (graph replay included).  The hierarchy, level by level (rules that look at a row
+ * index use the caller's index, so a reordered handle gets the same aggregates):
+ *   strength: j is a strong neighbour of i when j != i, a_ij != 0 and |a_ij| >= theta sqrt(|a_ii a_jj|) (theta = 0: every non-zero);
+ *   roots: a deterministic parallel MIS(2) on tuples (state, splitmix64(seed, index), index), OUT < UNDECIDED < IN (Bell, Dalton,
+ *   Olson 2012); aggregates: a root's neighbours join it, the others the step-1-assigned neighbour of largest |a_ij| (ties: smaller
+ *   index); aggregates are numbered by ascending index of their root;
+ *   T = 1/sqrt(|aggregate|) per row; P = (I - omega D^-1 A) T, omega = (4/3) / rho, rho = theta_max + err_max of a 30-step Lanczos
+ *   estimate of the spectrum of D^-1 A (see dpcg_spectrum; start vector from `seed`); A_c = P^T (A P) by a row-wise device SpGEMM
+ *   that sums every entry in one fixed order (two setups give the same bits).
+ * Coarsening stops at max_coarse rows, at max_levels or when it stalls (n_c > 0.9 n); the coarsest level is solved exactly (dense
+ * inverse by Cholesky on the host, a GEMV on the device): more than 4096 rows there is DPCG_ERR_INVALID, not positive definite
+ * DPCG_ERR_PIVOT; a missing, zero or negative diagonal on any level is DPCG_ERR_PIVOT.  The cycle smooths with damped Jacobi (weight
+ * omega, `sweeps` sweeps before and after; pyamg's default is Gauss-Seidel, which is sequential): M is symmetric positive definite.
+ * Same-pattern reuse: after dpcg_update_values, attaching again with the same parameters keeps, level by level while the aggregates
+ * come out unchanged, the structures of the SpGEMMs and of P^T; only values are computed again (the result equals a fresh setup bit
+ * for bit; dpcg_get_amg_info's reused_levels says how many levels were taken over).  Any other preconditioner call frees what was kept.  The one-launch forms do not take this kind. */
+int dpcg_set_precond_amg(dpcg_handle_t h, double theta, int max_levels, int max_coarse, int sweeps, uint64_t seed,
+                         dpcg_stream_t stream);
+/* *n_levels; per level l < capacity (host arrays, any may be NULL): rows, nnz of A_l, nnz of P_l (0 on the coarsest), rho and
+ * omega (0 on the coarsest); operator complexity sum nnz(A_l) / nnz(A_0), grid complexity sum n_l / n_0; *reused_levels: how many
+ * levels the setup that built this hierarchy took over from a parked one (same-pattern reuse; 0 for a fresh build).  Any out
+ * pointer may be NULL.  DPCG_ERR_STATE when the handle's preconditioner is not this kind. */
+int dpcg_get_amg_info(dpcg_handle_t h, int capacity, int *n_levels, int64_t *rows, int64_t *nnz, int64_t *p_nnz, double *rho,
+                      double *omega, double *operator_complexity, double *grid_complexity, int *reused_levels);
+/* Host copies of level l (0 <= l < n_levels - 1), any pointer may be NULL: agg[n_l] (the aggregate of each row; level 0 in the
+ * caller's numbering), P_l (n_l x n_{l+1} CSR; level 0's rows in the caller's numbering) and A_{l+1}.  sizes = {n_l, nnz(P_l),
+ * n_{l+1}, nnz(A_{l+1})}, the sizes the caller's buffers were made for (from dpcg_get_amg_info): when they are not the attached
+ * hierarchy's -- it was rebuilt meanwhile -- nothing is written and the call returns DPCG_ERR_INVALID.  Copies on `stream`, which
+ * is synchronised. */
+int dpcg_get_amg_level(dpcg_handle_t h, int level, const int64_t sizes[4], int32_t *agg, int32_t *p_rowptr, int32_t *p_col,
+                       double *p_val, int32_t *a_rowptr, int32_t *a_col, double *a_val, dpcg_stream_t stream);
 /* The geometry of the handle's reductions, for a checker that wants to sum in the same order (oracle/pcg_oracle.c,
  * orc_set_dot_tree: with it the CPU restatement reproduces the multi-launch solve's residual history BIT FOR BIT for M = I /
  * Jacobi): out[0] = workgroups of the SpMV kernel of the PCG loop, out[1] = its 256-row blocks, out[2] = 1 when the blocks are
