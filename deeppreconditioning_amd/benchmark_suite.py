@@ -19,7 +19,7 @@ from ._lib import BREAKDOWN, DpcgError
 from .cg import preconditioned_conjugate_gradient
 from .io import coo_to_csr_device
 from .model import lower_factor_csr, tril_batch_from_csr
-from .operators import IC0, ICT, ICholT, CsrSystem, Identity, Jacobi, LLtMultiply, SmoothedAggregation
+from .operators import IC0, ICT, ILUT, ICholT, CsrSystem, Identity, Jacobi, LLtMultiply, SmoothedAggregation
 
 PARAMETERS = ["kappas", "densities", "iterations", "setups", "durations", "totals", "successes"]  # test.py:180
 
@@ -42,6 +42,9 @@ COMPARABILITY = {
     "algebraic_multigrid": "same family as pyamg's smoothed_aggregation_solver(A).aspreconditioner(cycle='V') (test.py:95-98): "
                            "symmetric strength, MIS(2) aggregation, Jacobi-smoothed prolongator, Galerkin levels, exact coarse solve; "
                            "smoothed by damped Jacobi instead of Gauss-Seidel; pyamg absent: unpinned; applied, not materialised",
+    "incomplete_lu": "algorithm per Saad's dual-threshold ILUT(p, tau) as restated in tests/ilut_restatement.py (M = L U multiplied, "
+                     "test.py:90-93); ilupp binary absent: values unpinned; ilupp.ilut's own default arguments cannot be read here, "
+                     "icholt's (add_fill_in=1, threshold=0.1) are assumed",
 }
 
 
@@ -110,6 +113,8 @@ class BenchmarkSuite:
             return IC0("solve")
         if name == "incomplete_cholesky_multicolor":    # ... in multicolour order (opt-in: not among the default techniques)
             return IC0("solve", ordering="multicolor")
+        if name == "incomplete_lu":                 # test.py:90-93 (opt-in): ilupp.ilut, the factors MULTIPLIED (M = L U)
+            return ILUT("multiply", add_fill_in=1, threshold=0.1)
         if name == "algebraic_multigrid":           # test.py:95-98 (opt-in): smoothed aggregation, one V-cycle per update
             return SmoothedAggregation()
         if name == "learned":                       # test.py:100-105
@@ -126,7 +131,9 @@ class BenchmarkSuite:
         if n > self.kappa_max_n:
             try:
                 sb = system.spectrum_bounds(rtol=1e-4, max_steps=min(n, 2000))
-            except DpcgError as exc:     # M found not positive definite: no number (as the dense path would give an indefinite M A)
+            # M found not positive definite -- or, for incomplete_lu, M = L U not symmetric (dpcg_spectrum refuses it up front): no
+            # number (as the dense path would give for an indefinite M A)
+            except DpcgError as exc:
                 if exc.status != BREAKDOWN:
                     raise
                 return float("nan"), float("nan"), None, "unconverged"

@@ -622,7 +622,11 @@ extern "C" int dpcg_get_info(dpcg_handle_t h, int64_t *n, int64_t *nnz, int *spm
                        (h->planA.kernel == SPMV_TILE && h->planA.tile_mixed ? 64 : 0) +
                        (h->planA.kernel == SPMV_TILE && h->planA.cyclic ? 128 : 0);
     if (precond_kind) *precond_kind = h->precond;
-    if (precond_nnz) *precond_nnz = h->precond == DPCG_PRECOND_CSR ? h->M.nnz : (h->precond == DPCG_PRECOND_AMG ? amg_nnz(h->amg) : h->L.nnz);
+    if (precond_nnz) {
+        const bool lu = h->precond == DPCG_PRECOND_LU_MULTIPLY || h->precond == DPCG_PRECOND_LU_SOLVE;
+        *precond_nnz = h->precond == DPCG_PRECOND_CSR ? h->M.nnz
+                     : (h->precond == DPCG_PRECOND_AMG ? amg_nnz(h->amg) : (lu ? h->L.nnz + h->Lt.nnz : h->L.nnz));
+    }
     if ((n_levels_lower || n_levels_upper) && h->lvlL.n_levels < 0) DPCG_TRY(count_levels_on_demand(h));
     if (n_levels_lower) *n_levels_lower = h->lvlL.n_levels;
     if (n_levels_upper) *n_levels_upper = h->lvlU.n_levels;
@@ -716,8 +720,8 @@ extern "C" int dpcg_spmv_f32(dpcg_handle_t h, const float *x, float *y, dpcg_str
 // z = M r for the handle's preconditioner (cg.py:61,81).  `t` is the handle's scratch vector.
 int rz_partial_count(const dpcg_system *h) {
     if (h->precond == DPCG_PRECOND_CSR) return h->planM.grid;
-    if (h->precond == DPCG_PRECOND_LLT_MULTIPLY) return h->planL.grid;
-    if (h->precond == DPCG_PRECOND_LLT_SOLVE && h->lvlU.sweep) return h->lvlU.sweep_grid;   // colour sweeps
+    if (h->precond == DPCG_PRECOND_LLT_MULTIPLY || h->precond == DPCG_PRECOND_LU_MULTIPLY) return h->planL.grid;
+    if ((h->precond == DPCG_PRECOND_LLT_SOLVE || h->precond == DPCG_PRECOND_LU_SOLVE) && h->lvlU.sweep) return h->lvlU.sweep_grid;   // colour sweeps
     if (h->precond == DPCG_PRECOND_AMG && amg_rz_partials(h->amg) > 0) return amg_rz_partials(h->amg);   // level 0's last smoothing pass
     return h->vec_grid;
 }
@@ -741,6 +745,7 @@ int apply_precond(dpcg_system *h, const double *r, double *z, hipStream_t s, boo
             }
             break;
         case DPCG_PRECOND_LLT_MULTIPLY:       // on a reordered handle the SpMVs read P L^T P^T and P L P^T
+        case DPCG_PRECOND_LU_MULTIPLY:        // (L U: the L^T slot holds U)
             launch_spmv(h->perm ? h->Ltp : h->Lt, h->planLt, r, h->t, nullptr, nullptr, s);
             if (part_rz && n_part_rz) {
                 launch_spmv_xdot(h->perm ? h->Lp : h->L, h->planL, h->t, r, z, part_rz, s);
@@ -761,7 +766,8 @@ int apply_precond(dpcg_system *h, const double *r, double *z, hipStream_t s, boo
                 h->precond_fn(h->precond_user, r, z, h->A.n, (dpcg_stream_t)s);
             }
             break;
-        case DPCG_PRECOND_LLT_SOLVE: {
+        case DPCG_PRECOND_LLT_SOLVE:
+        case DPCG_PRECOND_LU_SOLVE: {          // (L U: no level-major hand-over, pairing or riding diagonal is built -- finish_lu)
             SptrsvIo lower_io, upper_io;
             if (h->lvlL.level_major && h->lvlU.level_major && h->lvlU.lm_from_lower) {
                 lower_io.keep_lm = true;                   // y stays in L's level-major numbering, L^T gathers it from there
@@ -818,8 +824,8 @@ extern "C" int dpcg_precond_apply(dpcg_handle_t h, const double *r, double *z, d
 
 extern "C" int dpcg_sptrsv(dpcg_handle_t h, int upper, const double *rhs, double *out, dpcg_stream_t stream) {
     if (!h || !rhs || !out) return invalid("dpcg_sptrsv: NULL argument");
-    if (h->precond != DPCG_PRECOND_LLT_SOLVE) {
-        set_error("dpcg_sptrsv: needs dpcg_set_precond_llt/ic0 in LLT_SOLVE mode");
+    if (h->precond != DPCG_PRECOND_LLT_SOLVE && h->precond != DPCG_PRECOND_LU_SOLVE) {    // (L U: upper = 1 solves with U)
+        set_error("dpcg_sptrsv: needs dpcg_set_precond_llt/ic0 in LLT_SOLVE mode (or an L U factor in LU_SOLVE mode)");
         return DPCG_ERR_STATE;
     }
     hipStream_t s = (hipStream_t)stream;

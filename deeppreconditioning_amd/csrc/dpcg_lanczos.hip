@@ -318,6 +318,12 @@ extern "C" int dpcg_spectrum(dpcg_handle_t h, int max_steps, double rtol, uint64
                              double *theta_min, double *theta_max, double *err_min, double *err_max, double *alpha,
                              double *beta) {
     if (!h || max_steps < 1 || !(rtol >= 0.0)) return invalid("dpcg_spectrum: bad argument (max_steps >= 1, rtol >= 0)");
+    if (h->precond == DPCG_PRECOND_LU_MULTIPLY || h->precond == DPCG_PRECOND_LU_SOLVE) {
+        // the process runs in the M inner product, which a non-symmetric M does not define: no step is taken
+        if (steps) *steps = 0;
+        set_error("dpcg_spectrum: M = L U is not symmetric");
+        return DPCG_BREAKDOWN;
+    }
     hipStream_t s = (hipStream_t)stream;
     const int64_t n = h->A.n;
     const int m = (int)std::min<int64_t>(max_steps, n);  // the Krylov space has at most n dimensions

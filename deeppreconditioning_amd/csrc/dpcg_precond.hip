@@ -757,6 +757,43 @@ int transpose_lower(const CsrDev &L, CsrDev &Lt, hipStream_t s) {
     return DPCG_OK;
 }
 
+// The triangular-solve schedule of factor F (lower, or upper with `upper`) from its level sets `ls`; fm: factor index -> handle index.
+// Large factors try the strip plan FIRST and build the level schedule (level-ordered copy, ring / sync-free records) only when it
+// is not kept; small ones build the schedule first because the choice depends on it.
+int schedule_factor(int64_t n, Levels &lv, LevelSort &ls, const CsrDev &F, bool upper, const int32_t *fm, hipStream_t s) {
+    // more than 2 % of the rows longer than a ring / strip record: no ring walk, no strips (see build_levels; measured on
+    // a 48^3 grid with one extra lower neighbour on a share of the rows: 5 % such rows turn the strip plan's 263 us per
+    // update into 772, the sync-free kernels take 458 whatever the share -- tools/longrow_share_probe.py)
+    DevBuf<int32_t> n_long;
+    DPCG_TRY(n_long.alloc(1));
+    DPCG_HIP(hipMemsetAsync(n_long.p, 0, sizeof(int32_t), s));
+    launch_count_long_rows(n, F.rowptr, 3, n_long.p, s);
+    int32_t h_long = 0;
+    DPCG_HIP(hipMemcpyAsync(&h_long, n_long.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    DPCG_HIP(hipStreamSynchronize(s));
+    // (DPCG_LONG_ROW_PCT: development knob for that share, in per cent)
+    static const int64_t pct = [] { const char *e = getenv("DPCG_LONG_ROW_PCT"); return e ? (int64_t)atoll(e) : (int64_t)2; }();
+    const bool long_rows = (int64_t)h_long * 100 > n * pct;
+    if (long_rows) {
+        DPCG_TRY(build_levels(lv, ls, n, F.nnz, F.rowptr, F.col, F.val, s, fm, upper, true));
+        return DPCG_OK;
+    }
+    const bool strips_first = n > 131072;
+    if (strips_first) {
+        lv.level_ptr = ls.level_ptr;
+        lv.n_levels = (int)ls.level_ptr.size() - 1;
+        DPCG_TRY(dev_alloc(&lv.spin_err, 1));
+        DPCG_HIP(hipMemsetAsync(lv.spin_err, 0, sizeof(int), s));
+        DPCG_TRY(build_strips(lv, n, F.nnz, F.rowptr, F.col, F.val, upper, fm, s));
+        if (lv.strips.n_strips > 0) return DPCG_OK;
+        dev_free(lv.spin_err);
+    }
+    DPCG_TRY(build_levels(lv, ls, n, F.nnz, F.rowptr, F.col, F.val, s, fm, upper));
+    if (!strips_first) DPCG_TRY(build_strips(lv, n, F.nnz, F.rowptr, F.col, F.val, upper, fm, s));
+    if (lv.strips.n_strips > 0) lv.level_major = false;
+    return DPCG_OK;
+}
+
 // h->L holds a lower-triangular factor on the device (owned by the handle): validate it, build L^T, the SpMV plans and,
 // in solve mode, the level schedules.  `lower_levels`: level analysis of L when the caller already has it (IC(0)).
 // `lower_prebuilt`: the schedule of L when IC(0) was factored THROUGH it (a strip plan -- its global level sets were never
@@ -799,40 +836,8 @@ int finish_llt(dpcg_system *h, int mode, hipStream_t s, LevelSort *lower_levels 
         LevelSort own, up_own;
         LevelSort &up = upper_levels ? *upper_levels : up_own;
         bool have_up = upper_levels != nullptr;
-        // Large factors try the strip plan FIRST and build the level schedule (level-ordered copy, ring / sync-free records)
-        // only when it is not kept; small ones build the schedule first because the choice depends on it.
         auto schedule = [&](Levels &lv, LevelSort &ls, const CsrDev &F, bool upper) -> int {
-            // more than 2 % of the rows longer than a ring / strip record: no ring walk, no strips (see build_levels; measured on
-            // a 48^3 grid with one extra lower neighbour on a share of the rows: 5 % such rows turn the strip plan's 263 us per
-            // update into 772, the sync-free kernels take 458 whatever the share -- tools/longrow_share_probe.py)
-            DevBuf<int32_t> n_long;
-            DPCG_TRY(n_long.alloc(1));
-            DPCG_HIP(hipMemsetAsync(n_long.p, 0, sizeof(int32_t), s));
-            launch_count_long_rows(n, F.rowptr, 3, n_long.p, s);
-            int32_t h_long = 0;
-            DPCG_HIP(hipMemcpyAsync(&h_long, n_long.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-            DPCG_HIP(hipStreamSynchronize(s));
-            // (DPCG_LONG_ROW_PCT: development knob for that share, in per cent)
-            static const int64_t pct = [] { const char *e = getenv("DPCG_LONG_ROW_PCT"); return e ? (int64_t)atoll(e) : (int64_t)2; }();
-            const bool long_rows = (int64_t)h_long * 100 > n * pct;
-            if (long_rows) {
-                DPCG_TRY(build_levels(lv, ls, n, F.nnz, F.rowptr, F.col, F.val, s, fm, upper, true));
-                return DPCG_OK;
-            }
-            const bool strips_first = n > 131072;
-            if (strips_first) {
-                lv.level_ptr = ls.level_ptr;
-                lv.n_levels = (int)ls.level_ptr.size() - 1;
-                DPCG_TRY(dev_alloc(&lv.spin_err, 1));
-                DPCG_HIP(hipMemsetAsync(lv.spin_err, 0, sizeof(int), s));
-                DPCG_TRY(build_strips(lv, n, F.nnz, F.rowptr, F.col, F.val, upper, fm, s));
-                if (lv.strips.n_strips > 0) return DPCG_OK;
-                dev_free(lv.spin_err);
-            }
-            DPCG_TRY(build_levels(lv, ls, n, F.nnz, F.rowptr, F.col, F.val, s, fm, upper));
-            if (!strips_first) DPCG_TRY(build_strips(lv, n, F.nnz, F.rowptr, F.col, F.val, upper, fm, s));
-            if (lv.strips.n_strips > 0) lv.level_major = false;
-            return DPCG_OK;
+            return schedule_factor(n, lv, ls, F, upper, fm, s);
         };
         if (lower_prebuilt) {                                 // (the handle owns the schedule from here on)
             h->lvlL = *lower_prebuilt;
@@ -893,6 +898,38 @@ int finish_llt(dpcg_system *h, int mode, hipStream_t s, LevelSort *lower_levels 
             }
             DPCG_CHECK_LAUNCH();
         }
+    }
+    h->precond = mode;
+    return DPCG_OK;
+}
+
+// h->L (unit lower, diagonal last) and h->Lt (an upper factor U of its own, diagonal first) hold an L U factor in the caller's
+// numbering: the SpMV plans of both (multiply mode; P L P^T and P U P^T on a reordered handle) or the level schedules of both,
+// each from its OWN pattern (solve mode).  Nothing of finish_llt's U = L^T shortcuts -- the transpose, L's level sets read
+// backwards, the strip plan taking L's level count, the paired colour sweeps, the diagonal riding on K2 -- holds here.
+int finish_lu(dpcg_system *h, int mode, hipStream_t s) {
+    const int64_t n = h->A.n;
+    PhaseTimer pt(s);
+    if (mode == DPCG_PRECOND_LU_MULTIPLY) {
+        if (h->perm) {
+            DPCG_TRY(permute_csr(h->L, h->perm, h->iperm, h->Lp, s));
+            DPCG_TRY(permute_csr(h->Lt, h->perm, h->iperm, h->Ltp, s));
+            DPCG_TRY(make_plan(h->Lp, h->planL, s));
+            DPCG_TRY(make_plan(h->Ltp, h->planLt, s));
+        } else {
+            DPCG_TRY(make_plan(h->L, h->planL, s));
+            DPCG_TRY(make_plan(h->Lt, h->planLt, s));
+        }
+        pt.mark("plans (L, U)");
+    } else {
+        const int32_t *fm = h->iperm;                 // factor index -> handle index (null: the handle is not reordered)
+        LevelSort lo, up;
+        DPCG_TRY(compute_levels(n, h->L.rowptr, h->L.col, false, lo, s, fm));
+        DPCG_TRY(schedule_factor(n, h->lvlL, lo, h->L, false, fm, s));
+        pt.mark("schedule(L)");
+        DPCG_TRY(compute_levels(n, h->Lt.rowptr, h->Lt.col, true, up, s, fm));
+        DPCG_TRY(schedule_factor(n, h->lvlU, up, h->Lt, true, fm, s));
+        pt.mark("schedule(U)");
     }
     h->precond = mode;
     return DPCG_OK;
@@ -1444,5 +1481,46 @@ extern "C" int dpcg_get_factor(dpcg_handle_t h, int32_t *rowptr, int32_t *col, d
     DPCG_HIP(hipMemcpy(rowptr, h->L.rowptr, (size_t)(h->L.n + 1) * sizeof(int32_t), hipMemcpyDeviceToHost));
     DPCG_HIP(hipMemcpy(col, h->L.col, (size_t)h->L.nnz * sizeof(int32_t), hipMemcpyDeviceToHost));
     DPCG_HIP(hipMemcpy(val, h->L.val, (size_t)h->L.nnz * sizeof(double), hipMemcpyDeviceToHost));
+    return DPCG_OK;
+}
+
+// ilupp.ilut as Saad's dual-threshold ILUT (contract: tests/ilut_restatement.py; device routine: dpcg_ilut.hip).  Like icholt it
+// factors the CALLER's matrix and leaves the previous preconditioner in place when it fails.
+extern "C" int dpcg_set_precond_ilut(dpcg_handle_t h, int mode, int add_fill_in, double threshold, dpcg_stream_t stream) {
+    if (!h) return invalid("NULL handle");
+    if (mode != DPCG_PRECOND_LU_MULTIPLY && mode != DPCG_PRECOND_LU_SOLVE) return invalid("bad LU mode");
+    if (add_fill_in < 0 || !(threshold >= 0.0)) return invalid("dpcg_set_precond_ilut: add_fill_in >= 0 and threshold >= 0");
+    hipStream_t s = (hipStream_t)stream;
+    SetupScope scope(s, true);          // (the preconditioner being replaced may be in use on another stream)
+    const CsrDev &Asrc = h->perm ? h->A_user : h->A;
+    PhaseTimer pt(s);
+    CsrDev Lf, Uf;
+    int st = ilut_factor(Asrc, add_fill_in, threshold, Lf, Uf, s);
+    if (st < 0) return st;
+    pt.mark("ilut: rows");
+    free_precond(h);
+    h->L = Lf;
+    h->Lt = Uf;                         // (the slot of L^T: U is a factor of its own here)
+    st = finish_lu(h, mode, s);
+    if (st < 0) free_precond(h);
+    return st;
+}
+
+extern "C" int dpcg_get_lu_factors(dpcg_handle_t h, int64_t *l_nnz, int64_t *u_nnz, int32_t *l_rowptr, int32_t *l_col,
+                                   double *l_val, int32_t *u_rowptr, int32_t *u_col, double *u_val) {
+    if (!h) return invalid("NULL handle");
+    if (h->precond != DPCG_PRECOND_LU_MULTIPLY && h->precond != DPCG_PRECOND_LU_SOLVE) {
+        set_error("dpcg_get_lu_factors: no L U factor set");
+        return DPCG_ERR_STATE;
+    }
+    if (l_nnz) *l_nnz = h->L.nnz;
+    if (u_nnz) *u_nnz = h->Lt.nnz;
+    const size_t rp = (size_t)(h->A.n + 1) * sizeof(int32_t);
+    if (l_rowptr) DPCG_HIP(hipMemcpy(l_rowptr, h->L.rowptr, rp, hipMemcpyDeviceToHost));
+    if (l_col) DPCG_HIP(hipMemcpy(l_col, h->L.col, (size_t)h->L.nnz * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (l_val) DPCG_HIP(hipMemcpy(l_val, h->L.val, (size_t)h->L.nnz * sizeof(double), hipMemcpyDeviceToHost));
+    if (u_rowptr) DPCG_HIP(hipMemcpy(u_rowptr, h->Lt.rowptr, rp, hipMemcpyDeviceToHost));
+    if (u_col) DPCG_HIP(hipMemcpy(u_col, h->Lt.col, (size_t)h->Lt.nnz * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (u_val) DPCG_HIP(hipMemcpy(u_val, h->Lt.val, (size_t)h->Lt.nnz * sizeof(double), hipMemcpyDeviceToHost));
     return DPCG_OK;
 }

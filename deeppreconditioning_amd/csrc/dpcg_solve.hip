@@ -153,8 +153,8 @@ static int precond_launches(const dpcg_system *h) {
     switch (h->precond) {
         case DPCG_PRECOND_CSR: return 1;
         case DPCG_PRECOND_CALLBACK: return 1;
-        case DPCG_PRECOND_LLT_MULTIPLY: return 2;
-        case DPCG_PRECOND_LLT_SOLVE: return trsv(h->lvlL) + trsv(h->lvlU);
+        case DPCG_PRECOND_LLT_MULTIPLY: case DPCG_PRECOND_LU_MULTIPLY: return 2;
+        case DPCG_PRECOND_LLT_SOLVE: case DPCG_PRECOND_LU_SOLVE: return trsv(h->lvlL) + trsv(h->lvlU);
         case DPCG_PRECOND_AMG: return amg_launches(h->amg);
         default: return 0;
     }
@@ -163,7 +163,7 @@ static int precond_launches(const dpcg_system *h) {
 // A sync-free triangular solve whose bounded poll ran out (cannot happen with a schedule built by this library) has
 // stored NaNs; report it instead of a silent breakdown.
 int check_spin_errors(dpcg_system *h, hipStream_t s) {
-    if (h->precond != DPCG_PRECOND_LLT_SOLVE) return DPCG_OK;
+    if (h->precond != DPCG_PRECOND_LLT_SOLVE && h->precond != DPCG_PRECOND_LU_SOLVE) return DPCG_OK;
     for (Levels *lv : {&h->lvlL, &h->lvlU}) {
         if (!lv->spin_err) continue;
         int e = 0;
@@ -547,8 +547,8 @@ extern "C" int dpcg_get_reduction_geometry(dpcg_handle_t h, int32_t out[16]) {
     switch (h->precond) {
         case DPCG_PRECOND_NONE: case DPCG_PRECOND_JACOBI: rzk = 0; break;
         case DPCG_PRECOND_CSR: pm = &h->planM; break;
-        case DPCG_PRECOND_LLT_MULTIPLY: pm = &h->planL; break;
-        case DPCG_PRECOND_LLT_SOLVE:
+        case DPCG_PRECOND_LLT_MULTIPLY: case DPCG_PRECOND_LU_MULTIPLY: pm = &h->planL; break;
+        case DPCG_PRECOND_LLT_SOLVE: case DPCG_PRECOND_LU_SOLVE:
             rzk = h->lvlU.sweep ? 9 : ((h->lvlU.level_major && h->lvlU.strips.n_strips == 0) ? 2 : 1);
             break;
         case DPCG_PRECOND_AMG: rzk = amg_rz_partials(h->amg) > 0 ? 9 : 1; break;   // (the V-cycle's last smoothing pass)
@@ -562,7 +562,8 @@ extern "C" int dpcg_get_reduction_geometry(dpcg_handle_t h, int32_t out[16]) {
         out[11] = pm->kernel == SPMV_TILE ? pm->cyclic : 0;
         // lanes per row where a CSR-vector kernel applies M (bits 8-15: M or L; 16-23: L^T of an L L^T product)
         if (pm->kernel == SPMV_VECTOR) out[11] |= pm->tpr << 8;
-        if (h->precond == DPCG_PRECOND_LLT_MULTIPLY && h->planLt.kernel == SPMV_VECTOR) out[11] |= h->planLt.tpr << 16;
+        if ((h->precond == DPCG_PRECOND_LLT_MULTIPLY || h->precond == DPCG_PRECOND_LU_MULTIPLY) && h->planLt.kernel == SPMV_VECTOR)
+            out[11] |= h->planLt.tpr << 16;
     }
     out[12] = out[13] = out[14] = out[15] = 0;
     if (rzk == 9 && h->precond == DPCG_PRECOND_LLT_SOLVE && h->lvlU.sweep && h->lvlU.n_levels <= 16) {

@@ -270,6 +270,30 @@ class ICholT(Preconditioner):
         raise TypeError("ICholT needs the system matrix: attach it with CsrSystem.set_preconditioner")
 
 
+class ILUT(Preconditioner):
+    """`ilupp.ilut(A)` -- the reference harness's `incomplete_lu` technique (test.py:90-93, which multiplies the factors: M = L U)
+    -- factored on the device as Saad's dual-threshold ILUT(p, tau): per row, eliminated entries below threshold * ||A[i, :]||_2
+    are dropped, of the rest of L's part the nnz(A[i, :i]) + add_fill_in largest stay, of U's part those >= the threshold and of
+    them the nnz(A[i, i+1:]) + add_fill_in largest.  The ilupp binary is not available: the factors equal the restatement of the
+    published algorithm (tests/ilut_restatement.py) bit for bit, PARITY UNPINNED against ilupp's own output.
+    mode="multiply" applies z = L (U r), the reference's use; mode="solve" applies z = U^-1 (L^-1 r) by triangular solves.  M is
+    not symmetric: `CsrSystem.spectrum_bounds` raises.  See dpcg_set_precond_ilut in include/dpcg.h for the limits."""
+
+    def __init__(self, mode: str = "multiply", add_fill_in: int = 1, threshold: float = 0.1):
+        if mode not in ("solve", "multiply"):
+            raise ValueError("mode must be 'solve' or 'multiply'")
+        if add_fill_in < 0 or not threshold >= 0:
+            raise ValueError("add_fill_in >= 0 and threshold >= 0")
+        self.mode = L.PRECOND_LU_SOLVE if mode == "solve" else L.PRECOND_LU_MULTIPLY
+        self.add_fill_in, self.threshold = int(add_fill_in), float(threshold)
+
+    def _attach(self, system):
+        L.check(L.lib().dpcg_set_precond_ilut(system._h, self.mode, self.add_fill_in, self.threshold, _stream()))
+
+    def __matmul__(self, r):
+        raise TypeError("ILUT needs the system matrix: attach it with CsrSystem.set_preconditioner")
+
+
 class ICT(Preconditioner):
     """Thresholded incomplete Cholesky on a STATIC pattern -- tril(A) plus level-1 fill -- with MATLAB's 'ict' drop rule
     (contract: oracle/oracle.py::ict).  Not what `ilupp.icholt` computes (that is `ICholT`: a per-column entry count instead
@@ -699,6 +723,20 @@ class CsrSystem:
         v = np.empty(nnz, dtype=np.float64)
         L.check(L.lib().dpcg_get_factor(self._h, _np_ptr(rp), _np_ptr(ci), _np_ptr(v)))
         return rp, ci, v
+
+    def lu_factors(self):
+        """The attached `ILUT` factors (L, U) as scipy CSR in the caller's numbering: L unit lower (diagonal last), U upper
+        (diagonal first).  DpcgError (ERR_STATE) when no L U factor is attached."""
+        import scipy.sparse as sp
+        ln, un = C.c_int64(0), C.c_int64(0)
+        L.check(L.lib().dpcg_get_lu_factors(self._h, C.byref(ln), C.byref(un), None, None, None, None, None, None))
+        out = []
+        for nnz in (ln.value, un.value):
+            out.append((np.empty(self.n + 1, dtype=np.int32), np.empty(nnz, dtype=np.int32), np.empty(nnz, dtype=np.float64)))
+        (lr, lc, lv), (ur, uc, uv) = out
+        L.check(L.lib().dpcg_get_lu_factors(self._h, None, None, _np_ptr(lr), _np_ptr(lc), _np_ptr(lv), _np_ptr(ur), _np_ptr(uc),
+                                            _np_ptr(uv)))
+        return (sp.csr_matrix((lv, lc, lr), shape=(self.n, self.n)), sp.csr_matrix((uv, uc, ur), shape=(self.n, self.n)))
 
     def spmv_dot_bench(self, repeats: int = 100) -> float:
         """Average milliseconds of the in-PCG SpMV+<p,Ap> kernel over `repeats` launches (HIP events)."""

@@ -53,7 +53,9 @@ enum dpcg_precond {
     DPCG_PRECOND_LLT_MULTIPLY = 3, /* z = L (L^T r), same operator as test.py:102-105, never formed */
     DPCG_PRECOND_LLT_SOLVE = 4,    /* z = L^-T (L^-1 r), level-scheduled SpTRSV (north_star)        */
     DPCG_PRECOND_CALLBACK = 5,     /* z = M r by a caller-supplied function (the duck-typed `M @ rk`) */
-    DPCG_PRECOND_AMG = 6           /* z = M r by one smoothed-aggregation V-cycle  test.py:95-98 (algebraic_multigrid) */
+    DPCG_PRECOND_AMG = 6,          /* z = M r by one smoothed-aggregation V-cycle  test.py:95-98 (algebraic_multigrid) */
+    DPCG_PRECOND_LU_MULTIPLY = 7,  /* z = L (U r), the reference's M = L U          test.py:90-93 (incomplete_lu)       */
+    DPCG_PRECOND_LU_SOLVE = 8      /* z = U^-1 (L^-1 r), level-scheduled SpTRSVs of an L U factor                      */
 };
 
 /* dpcg_solve flags */
@@ -97,7 +99,7 @@ int dpcg_destroy(dpcg_handle_t h);
  * a default solve runs two-kernel updates (see DPCG_NO_FUSE), +32 when the x-tile kernel reads its once-read streams and
  * writes y non-temporally (streams beyond the Infinity Cache), +64 when some 256-row blocks of the x-tile plan touch too many
  * places of x for an LDS tile and gather instead, +128 when the row blocks are dealt out to the workgroups cyclically instead of
- * in slabs.  precond_nnz: nnz of M (CSR) or of L. */
+ * in slabs.  precond_nnz: nnz of M (CSR), of L, or nnz(L) + nnz(U) for an L U factor. */
 int dpcg_get_info(dpcg_handle_t h, int64_t *n, int64_t *nnz, int *spmv_kernel, int *precond_kind,
                   int64_t *precond_nnz, int *n_levels_lower, int *n_levels_upper);
 
@@ -178,6 +180,21 @@ int dpcg_set_precond_ict(dpcg_handle_t h, int mode, int fill_in, double threshol
  * columns are walked in order by one wave (the pattern of a column depends on the values before it): milliseconds at the
  * reference's 2.4K-22K rows, ~3 us per row beyond. */
 int dpcg_set_precond_icholt(dpcg_handle_t h, int mode, int add_fill_in, double threshold, dpcg_stream_t stream);
+/* ilupp.ilut(A) as Saad's dual-threshold ILUT(p, tau) -- the reference harness's `incomplete_lu` technique (test.py:90-93: the
+ * factors are MULTIPLIED, M = L U: mode DPCG_PRECOND_LU_MULTIPLY; DPCG_PRECOND_LU_SOLVE applies them by triangular solves).
+ * Row by row in the caller's numbering (tests/ilut_restatement.py): w = A[i, :]; tau_i = threshold * ||A[i, :]||_2; for the
+ * columns k < i of w in ascending order (fill included) w_k /= U_kk, dropped when |w_k| < tau_i, else w -= w_k U[k, k+1:];
+ * of the L part the nnz(A[i, :i]) + add_fill_in largest stay, of the U part those >= tau_i and of them the
+ * nnz(A[i, i+1:]) + add_fill_in largest (ties: the smaller column); U_ii = w_i, L_ii = 1.  The ilupp binary is absent: the
+ * factor equals the restatement bit for bit, PARITY UNPINNED against ilupp itself.  Limits: 256 positions per working row and
+ * 64 kept entries per row of L and of U (DPCG_ERR_INVALID beyond); a zero or non-finite pivot is DPCG_ERR_PIVOT (the error
+ * text names the row).  On failure the previous preconditioner stays.  M = L U is not symmetric: dpcg_spectrum returns
+ * DPCG_BREAKDOWN for these kinds, and no one-launch form takes them.  add_fill_in >= 0, threshold >= 0. */
+int dpcg_set_precond_ilut(dpcg_handle_t h, int mode, int add_fill_in, double threshold, dpcg_stream_t stream);
+/* The attached L U factor in the caller's numbering (host arrays; any may be NULL: with all NULL only the sizes are reported):
+ * L unit lower (diagonal last), U upper (diagonal first), columns ascending.  DPCG_ERR_STATE when no L U factor is set. */
+int dpcg_get_lu_factors(dpcg_handle_t h, int64_t *l_nnz, int64_t *u_nnz, int32_t *l_rowptr, int32_t *l_col, double *l_val,
+                        int32_t *u_rowptr, int32_t *u_col, double *u_val);
 /* The reference's operator protocol asks of M nothing but `M @ rk` (cg.py:61,81).  An M that is not a matrix this library
  * can hold (a Python object with __matmul__, a multigrid cycle, ...) is applied through a function the caller supplies:
  * fn(user, r, z, n, stream) must ENQUEUE z = M r on `stream` (device pointers, caller's numbering; it is called from the
