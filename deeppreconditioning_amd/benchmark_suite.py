@@ -42,6 +42,11 @@ COMPARABILITY = {
     "algebraic_multigrid": "same family as pyamg's smoothed_aggregation_solver(A).aspreconditioner(cycle='V') (test.py:95-98): "
                            "symmetric strength, MIS(2) aggregation, Jacobi-smoothed prolongator, Galerkin levels, exact coarse solve; "
                            "smoothed by damped Jacobi instead of Gauss-Seidel; pyamg absent: unpinned; applied, not materialised",
+    "algebraic_multigrid_gauss_seidel": "not in the reference: the algebraic_multigrid hierarchy smoothed by symmetric Gauss-Seidel in "
+                                        "multicolour order (each colour at once; pyamg sweeps row by row: another operator); a level "
+                                        "that needs more than 63 colours keeps damped Jacobi",
+    "algebraic_multigrid_chebyshev": "not in the reference: the algebraic_multigrid hierarchy smoothed by a degree-2 Chebyshev "
+                                     "polynomial in D^-1 A on [rho / 30, rho] (pyamg's default smoother is Gauss-Seidel)",
     "incomplete_lu": "algorithm per Saad's dual-threshold ILUT(p, tau) as restated in tests/ilut_restatement.py (M = L U multiplied, "
                      "test.py:90-93); ilupp binary absent: values unpinned; ilupp.ilut's own default arguments cannot be read here, "
                      "icholt's (add_fill_in=1, threshold=0.1) are assumed",
@@ -117,6 +122,10 @@ class BenchmarkSuite:
             return ILUT("multiply", add_fill_in=1, threshold=0.1)
         if name == "algebraic_multigrid":           # test.py:95-98 (opt-in): smoothed aggregation, one V-cycle per update
             return SmoothedAggregation()
+        if name == "algebraic_multigrid_gauss_seidel":     # the same hierarchy, multicolour Gauss-Seidel smoothing (opt-in)
+            return SmoothedAggregation(smoother="gauss_seidel")
+        if name == "algebraic_multigrid_chebyshev":        # the same hierarchy, Chebyshev smoothing (opt-in)
+            return SmoothedAggregation(smoother="chebyshev")
         if name == "learned":                       # test.py:100-105
             with torch.no_grad():
                 out = self.model(system_tril)

@@ -27,6 +27,17 @@
 // Apply (launch_amg_apply), per level: k_amg_row<PRE> (x = omega D^-1 b and r = b - A x in one pass), nu - 1 k_amg_row<SWEEP>,
 // k_amg_row<PLAIN> (b_{l+1} = P^T r); k_amg_gemv on the coarsest level; then k_amg_row<ACC> (x += P x_{l+1}) and nu
 // k_amg_row<POST> (x += omega D^-1 (b - A x)) -- on level 0 the last one writes z and the partials of <r, z> for PCG.
+//
+// Other smoothers (dpcg_set_precond_amg_smoothed); the hierarchy is the same, only the smoothing steps of a level change:
+//   Gauss-Seidel  rows colour by colour (multicolor_order's perm) and the colour offsets.  A pass (k_amg_gs) updates one colour in
+//                 place, x_i += dinv_i (b_i - sum a_ij x_j); a symmetric sweep is the passes 0 .. m-1, m-2 .. 0.  Pre-smoothing's first
+//                 pass starts from x = 0 (it writes every row).  Levels of at most gs_block_rows() rows run all their sweeps in one
+//                 workgroup (k_amg_gs_block: a block barrier between colours).  k_amg_row<RES> forms b - A x before the restriction.
+//                 The last pass covers one colour, so level 0 emits no <r, z> partials and PCG sums <r, z> itself.
+//   Chebyshev     (x, r = b - A x) is carried from step to step: k_amg_cheb<STEP> gathers the new x_j = x_j + d'_j,
+//                 d'_j = c1 d_j + c2 (dinv_j r_j), on the fly and writes x', d' and r' = b - A x' (first step of an application:
+//                 d'_j = c2 (dinv_j r_j)); pre-smoothing starts from x = 0, r = b; post-smoothing forms r with k_amg_row<RES> after the
+//                 correction; the last step of a level needs no r' (k_amg_cheb<LAST>, on level 0 with the <r, z> partials).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -50,12 +61,22 @@ struct AmgLevel {
     double rho = 0.0, omega = 0.0;
     int tpr_a = 2, tpr_p = 2, tpr_pt = 2;
     double *b = nullptr, *xa = nullptr, *xb = nullptr, *ra = nullptr, *rb = nullptr;   // work vectors (b: levels >= 1)
+    int smoother = DPCG_AMG_JACOBI;   // what this level smooths with (a Gauss-Seidel level that could not be coloured: Jacobi)
+    int32_t *gs_rows = nullptr;       // Gauss-Seidel: the rows colour by colour (n)
+    int32_t *gs_off_dev = nullptr;    // ... where each colour begins in gs_rows (m + 1), for the one-workgroup sweep
+    std::vector<int32_t> gs_off;      // ... the same on the host
+    bool gs_block = false;            // ... the whole sweep in one workgroup
+    double cheb_lo = 0.0, cheb_hi = 0.0;
+    std::vector<double> cheb_c1, cheb_c2;   // Chebyshev: the coefficients of each step (c1[0] unused)
+    double *da = nullptr, *db = nullptr;    // Chebyshev: the direction d, double-buffered
 };
 
 struct AmgState {
     double theta = 0.0;
     int max_levels = 10, max_coarse = 500, sweeps = 1;
     uint64_t seed = 0;
+    int smoother = DPCG_AMG_JACOBI, degree = 2;
+    double eig_ratio = 30.0;
     std::vector<AmgLevel> lv;         // lv.back(): the coarsest level (dense solve)
     double *cinv = nullptr;           // dense inverse of the coarsest matrix, row-major
     int64_t nco = 0;
@@ -67,6 +88,13 @@ namespace {
 constexpr int kSgCap = 1024;          // products of a row sorted in LDS (16 KiB per one-wave workgroup)
 constexpr int kApplyMaxGrid = kMaxSpmvGrid;
 constexpr int kRhoSteps = 30;         // Lanczos steps of the spectral-radius estimate
+constexpr int kGsBlockThreads = 1024; // the one-workgroup Gauss-Seidel sweep
+
+// Gauss-Seidel levels of at most this many rows sweep in one workgroup (DPCG_AMG_GS_BLOCK_ROWS overrides; DESIGN.md has the measurement)
+int gs_block_rows() {
+    static const int v = [] { const char *e = getenv("DPCG_AMG_GS_BLOCK_ROWS"); return e ? atoi(e) : 4096; }();
+    return v;
+}
 
 enum MisState : int8_t { MIS_OUT = 0, MIS_UND = 1, MIS_IN = 2 };
 
@@ -349,7 +377,7 @@ __global__ __launch_bounds__(64) void k_spgemm(int64_t m, const int32_t *__restr
 __global__ void k_set_last(int32_t *rp, int64_t n) { rp[n] = 0; }
 
 // ---- apply kernels ------------------------------------------------------------------------------------------------------
-enum AmgOp { OP_PRE = 0, OP_SWEEP = 1, OP_POST = 2, OP_ACC = 3, OP_PLAIN = 4 };
+enum AmgOp { OP_PRE = 0, OP_SWEEP = 1, OP_POST = 2, OP_ACC = 3, OP_PLAIN = 4, OP_RES = 5 };
 
 // One row per TPR lanes.  y_j is what the row gathers:
 //   PRE    y_j = omega dinv_j b_j;         x_i = y_i,  r_i = b_i - sum a_ij y_j
@@ -357,6 +385,7 @@ enum AmgOp { OP_PRE = 0, OP_SWEEP = 1, OP_POST = 2, OP_ACC = 3, OP_PLAIN = 4 };
 //   POST   y_j = x_j;                      x'_i = x_i + omega dinv_i (b_i - sum a_ij y_j)   [part: <b, x'> per workgroup]
 //   ACC    y_j = u_j;                      x'_i = x_i + sum a_ij y_j          (a = P)
 //   PLAIN  y_j = u_j;                      x'_i = sum a_ij y_j                (a = P^T)
+//   RES    y_j = x_j;                      r_i = b_i - sum a_ij y_j
 template <int OP, int TPR>
 __global__ __launch_bounds__(kBlock) void k_amg_row(int64_t n, const int32_t *__restrict__ rp, const int32_t *__restrict__ ci,
                                                     const double *__restrict__ av, const double *__restrict__ dinv, double omega,
@@ -377,7 +406,7 @@ __global__ __launch_bounds__(kBlock) void k_amg_row(int64_t n, const int32_t *__
                 double y;
                 if (OP == OP_PRE) y = omega * dinv[j] * b[j];
                 else if (OP == OP_SWEEP) y = xin[j] + omega * dinv[j] * rin[j];
-                else if (OP == OP_POST) y = xin[j];
+                else if (OP == OP_POST || OP == OP_RES) y = xin[j];
                 else y = u[j];
                 s += av[k] * y;
             }
@@ -397,12 +426,131 @@ __global__ __launch_bounds__(kBlock) void k_amg_row(int64_t n, const int32_t *__
                 if (part) acc += b[i] * x;
             } else if (OP == OP_ACC) {
                 xout[i] = xin[i] + s;
+            } else if (OP == OP_RES) {
+                rout[i] = b[i] - s;
             } else {
                 xout[i] = s;
             }
         }
     }
     if (OP == OP_POST && part) {   // fixed-order workgroup sum (rows are owned by lanes sub == 0; the others hold 0)
+        __shared__ double red[kBlock / 64];
+        const double w = wave_sum(acc);
+        if ((threadIdx.x & 63) == 63) red[threadIdx.x >> 6] = w;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            double t = 0.0;
+            for (int q = 0; q < kBlock / 64; ++q) t += red[q];
+            part[blockIdx.x] = t;
+        }
+    }
+}
+
+// One Gauss-Seidel colour pass: the rows rows[0 .. cnt) (one colour: no two share an edge) updated in place,
+// x_i += dinv_i (b_i - sum_j a_ij x_j).  INIT (the first pass from x = 0): rows[0 .. n_all) are walked, the colour's own rows get
+// dinv_i b_i and every other row 0.
+template <int TPR, bool INIT>
+__global__ __launch_bounds__(kBlock) void k_amg_gs(int64_t cnt, int64_t n_all, const int32_t *__restrict__ rows,
+                                                   const int32_t *__restrict__ rp, const int32_t *__restrict__ ci,
+                                                   const double *__restrict__ av, const double *__restrict__ dinv,
+                                                   const double *__restrict__ b, double *x, const int *__restrict__ done) {
+    if (done && *done) return;
+    constexpr int RPB = kBlock / TPR;
+    const int sub = threadIdx.x % TPR;
+    const int64_t total = INIT ? n_all : cnt;
+    for (int64_t p0 = (int64_t)blockIdx.x * RPB; p0 < total; p0 += (int64_t)gridDim.x * RPB) {
+        const int64_t p = p0 + threadIdx.x / TPR;
+        if (INIT) {
+            if (p < total && sub == 0) {
+                const int i = rows[p];
+                x[i] = p < cnt ? dinv[i] * b[i] : 0.0;
+            }
+            continue;
+        }
+        const int i = p < total ? rows[p] : 0;
+        double s = 0.0;
+        if (p < total)
+            for (int k = rp[i] + sub; k < rp[i + 1]; k += TPR) s += av[k] * x[ci[k]];
+#pragma unroll
+        for (int w = 1; w < TPR; w <<= 1) s += __shfl_xor(s, w, TPR);
+        if (p < total && sub == 0) x[i] = x[i] + dinv[i] * (b[i] - s);
+    }
+}
+
+// `sweeps` symmetric sweeps of one level in ONE workgroup (a block barrier between colours, no grid-wide wait); init: from x = 0
+template <int TPR>
+__global__ __launch_bounds__(kGsBlockThreads) void k_amg_gs_block(int64_t n, int m, const int32_t *__restrict__ off,
+                                                                  const int32_t *__restrict__ rows, const int32_t *__restrict__ rp,
+                                                                  const int32_t *__restrict__ ci, const double *__restrict__ av,
+                                                                  const double *__restrict__ dinv, const double *__restrict__ b,
+                                                                  double *x, int sweeps, int init, const int *__restrict__ done) {
+    if (done && *done) return;
+    constexpr int RPB = kGsBlockThreads / TPR;
+    const int sub = threadIdx.x % TPR;
+    if (init) {
+        for (int64_t i = threadIdx.x; i < n; i += kGsBlockThreads) x[i] = 0.0;
+        __syncthreads();
+    }
+    for (int sw = 0; sw < sweeps; ++sw)
+        for (int q = 0; q < 2 * m - 1; ++q) {
+            const int c = q < m ? q : 2 * m - 2 - q;
+            const int lo = off[c], hi = off[c + 1];
+            for (int p0 = lo; p0 < hi; p0 += RPB) {
+                const int p = p0 + (int)threadIdx.x / TPR;
+                const int i = p < hi ? rows[p] : 0;
+                double s = 0.0;
+                if (p < hi)
+                    for (int k = rp[i] + sub; k < rp[i + 1]; k += TPR) s += av[k] * x[ci[k]];
+#pragma unroll
+                for (int w = 1; w < TPR; w <<= 1) s += __shfl_xor(s, w, TPR);
+                if (p < hi && sub == 0) x[i] = x[i] + dinv[i] * (b[i] - s);
+            }
+            __syncthreads();
+        }
+}
+
+// One Chebyshev step on (x, r = b - A x): d' = c1 d + c2 (dinv r) (din null: the first step, d' = c2 (dinv r)), x' = x + d'
+// (xin null: x = 0).  STEP gathers the new x_j on the fly and writes x', d' and r' = b - A x'; LAST writes x' only (part: <b, x'>
+// per workgroup, rows owned as in k_amg_row so the partials line up with amg_rz_partials).
+enum ChebMode { CHEB_STEP = 0, CHEB_LAST = 1 };
+template <int TPR, int MODE>
+__global__ __launch_bounds__(kBlock) void k_amg_cheb(int64_t n, const int32_t *__restrict__ rp, const int32_t *__restrict__ ci,
+                                                     const double *__restrict__ av, const double *__restrict__ dinv,
+                                                     const double *__restrict__ b, const double *__restrict__ xin,
+                                                     const double *__restrict__ din, const double *__restrict__ rin, double c1, double c2,
+                                                     double *__restrict__ xout, double *__restrict__ dout, double *__restrict__ rout,
+                                                     double *__restrict__ part, const int *__restrict__ done) {
+    if (done && *done) return;
+    constexpr int RPB = kBlock / TPR;
+    const int sub = threadIdx.x % TPR;
+    auto dnew = [&](int64_t j) { return din ? c1 * din[j] + c2 * (dinv[j] * rin[j]) : c2 * (dinv[j] * rin[j]); };
+    auto xnew = [&](int64_t j, double d) { return (xin ? xin[j] : 0.0) + d; };
+    double acc = 0.0;
+    for (int64_t row0 = (int64_t)blockIdx.x * RPB; row0 < n; row0 += (int64_t)gridDim.x * RPB) {
+        const int64_t i = row0 + threadIdx.x / TPR;
+        double s = 0.0;
+        if (MODE == CHEB_STEP) {
+            if (i < n)
+                for (int k = rp[i] + sub; k < rp[i + 1]; k += TPR) {
+                    const int j = ci[k];
+                    s += av[k] * xnew(j, dnew(j));
+                }
+#pragma unroll
+            for (int w = 1; w < TPR; w <<= 1) s += __shfl_xor(s, w, TPR);
+        }
+        if (i < n && sub == 0) {
+            const double d = dnew(i);
+            const double x = xnew(i, d);
+            xout[i] = x;
+            if (MODE == CHEB_STEP) {
+                dout[i] = d;
+                rout[i] = b[i] - s;
+            } else if (part) {
+                acc += b[i] * x;
+            }
+        }
+    }
+    if (MODE == CHEB_LAST && part) {
         __shared__ double red[kBlock / 64];
         const double w = wave_sum(acc);
         if ((threadIdx.x & 63) == 63) red[threadIdx.x >> 6] = w;
@@ -450,6 +598,66 @@ void launch_row(const CsrDev &A, int tpr, const double *dinv, double omega, cons
 #undef AMG_ROW
 }
 
+void launch_gs(const AmgLevel &L, int64_t lo, int64_t cnt, bool init, const double *b, double *x, hipStream_t s, const int *done) {
+    const int rpb = kBlock / L.tpr_a;
+    const int64_t total = init ? L.A.n : cnt;
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((total + rpb - 1) / rpb, kApplyMaxGrid));
+    const int32_t *rows = L.gs_rows + lo;
+#define AMG_GS(T)                                                                                                              \
+    case T:                                                                                                                    \
+        if (init)                                                                                                              \
+            hipLaunchKernelGGL((k_amg_gs<T, true>), dim3(grid), dim3(kBlock), 0, s, cnt, L.A.n, rows, L.A.rowptr, L.A.col,       \
+                               L.A.val, L.dinv, b, x, done);                                                                   \
+        else                                                                                                                   \
+            hipLaunchKernelGGL((k_amg_gs<T, false>), dim3(grid), dim3(kBlock), 0, s, cnt, L.A.n, rows, L.A.rowptr, L.A.col,      \
+                               L.A.val, L.dinv, b, x, done);                                                                   \
+        break;
+    switch (L.tpr_a) { AMG_GS(2) AMG_GS(4) AMG_GS(8) AMG_GS(16) AMG_GS(32) default: AMG_GS(64) }
+#undef AMG_GS
+}
+
+void launch_gs_block(const AmgLevel &L, int sweeps, bool init, const double *b, double *x, hipStream_t s, const int *done) {
+    const int m = (int)L.gs_off.size() - 1;
+#define AMG_GSB(T)                                                                                                             \
+    case T:                                                                                                                    \
+        hipLaunchKernelGGL((k_amg_gs_block<T>), dim3(1), dim3(kGsBlockThreads), 0, s, L.A.n, m, L.gs_off_dev, L.gs_rows,       \
+                           L.A.rowptr, L.A.col, L.A.val, L.dinv, b, x, sweeps, init ? 1 : 0, done);                            \
+        break;
+    switch (L.tpr_a) { AMG_GSB(2) AMG_GSB(4) AMG_GSB(8) AMG_GSB(16) AMG_GSB(32) default: AMG_GSB(64) }
+#undef AMG_GSB
+}
+
+// `sweeps` symmetric Gauss-Seidel sweeps of level L on x (init: from x = 0); returns the launches
+int gs_sweeps(const AmgLevel &L, int sweeps, bool init, const double *b, double *x, hipStream_t s, const int *done) {
+    if (L.gs_block) {
+        launch_gs_block(L, sweeps, init, b, x, s, done);
+        return 1;
+    }
+    const int m = (int)L.gs_off.size() - 1;
+    int k = 0;
+    for (int sw = 0; sw < sweeps; ++sw)
+        for (int q = 0; q < 2 * m - 1; ++q, ++k) {
+            const int c = q < m ? q : 2 * m - 2 - q;
+            launch_gs(L, L.gs_off[c], L.gs_off[c + 1] - L.gs_off[c], init && k == 0, b, x, s, done);
+        }
+    return k;
+}
+
+template <int MODE>
+void launch_cheb(const AmgLevel &L, double c1, double c2, const double *b, const double *xin, const double *din, const double *rin,
+                 double *xout, double *dout, double *rout, double *part, int *grid_out, hipStream_t s, const int *done) {
+    const int rpb = kBlock / L.tpr_a;
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((L.A.n + rpb - 1) / rpb, kApplyMaxGrid));
+    if (grid_out) *grid_out = grid;
+#define AMG_CHEB(T)                                                                                                            \
+    case T:                                                                                                                    \
+        hipLaunchKernelGGL((k_amg_cheb<T, MODE>), dim3(grid), dim3(kBlock), 0, s, L.A.n, L.A.rowptr, L.A.col, L.A.val, L.dinv, \
+                           b, xin, din, rin, c1, c2, xout, dout, rout, part, done);                                            \
+        break;
+    switch (L.tpr_a) { AMG_CHEB(2) AMG_CHEB(4) AMG_CHEB(8) AMG_CHEB(16) AMG_CHEB(32) default: AMG_CHEB(64) }
+#undef AMG_CHEB
+}
+
 // ---- host helpers ---------------------------------------------------------------------------------------------------
 template <typename T>
 int read1(const T *dev, T *host, hipStream_t s) {
@@ -469,6 +677,8 @@ void free_level(AmgLevel &L, bool keep_a) {
     free_csr(L.AP);
     dev_free(L.pt_order);
     dev_free(L.b); dev_free(L.xa); dev_free(L.xb); dev_free(L.ra); dev_free(L.rb);
+    dev_free(L.gs_rows); dev_free(L.gs_off_dev);
+    dev_free(L.da); dev_free(L.db);
     L = AmgLevel();
 }
 
@@ -671,8 +881,79 @@ int alloc_work(AmgLevel &L, bool coarse, int sweeps) {
     if (coarse) return DPCG_OK;
     DPCG_TRY(dev_alloc(&L.xb, n));
     DPCG_TRY(dev_alloc(&L.ra, n));
-    if (sweeps > 1) DPCG_TRY(dev_alloc(&L.rb, n));
+    if (sweeps > 1 || L.smoother == DPCG_AMG_CHEBYSHEV) DPCG_TRY(dev_alloc(&L.rb, n));
+    if (L.smoother == DPCG_AMG_CHEBYSHEV) {
+        DPCG_TRY(dev_alloc(&L.da, n));
+        DPCG_TRY(dev_alloc(&L.db, n));
+    }
     return DPCG_OK;
+}
+
+// Gauss-Seidel: colour level l (taken over from the parked level O when its pattern was kept; level 0: the handle's cached colouring,
+// computed and cached here when there is none).  A graph the greedy colouring cannot colour with 63 colours keeps damped Jacobi.
+int color_level(dpcg_system *h, AmgLevel &L, AmgLevel *O, int l, hipStream_t s) {
+    const int64_t n = L.A.n;
+    if (O && O->gs_rows && !O->gs_off.empty() && O->gs_off.back() == n) {
+        L.gs_rows = O->gs_rows; O->gs_rows = nullptr;
+        L.gs_off_dev = O->gs_off_dev; O->gs_off_dev = nullptr;
+        L.gs_off.swap(O->gs_off);
+    } else {
+        const bool cached = l == 0 && h->mc_perm && (int)h->mc_offsets.size() == h->mc_colors + 1 && h->mc_offsets.back() == n;
+        if (cached) {
+            L.gs_off = h->mc_offsets;
+            DPCG_TRY(dev_alloc(&L.gs_rows, n));
+            DPCG_HIP(hipMemcpyAsync(L.gs_rows, h->mc_perm, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+        } else {
+            int32_t *p = nullptr, *ip = nullptr;
+            int nc = 0;
+            std::vector<int32_t> off;
+            const int st = multicolor_order(L.A, &p, &ip, &nc, s, &off);
+            if (st == DPCG_ERR_INVALID) {             // more than 63 colours (or a pattern it cannot colour): damped Jacobi here
+                dev_free(p);
+                dev_free(ip);
+                L.smoother = DPCG_AMG_JACOBI;
+                return DPCG_OK;
+            }
+            DPCG_TRY(st);
+            if (l == 0 && !h->mc_perm) {              // the handle keeps the colouring of its pattern (it survives update_values)
+                DPCG_TRY(dev_alloc(&L.gs_rows, n));
+                DPCG_HIP(hipMemcpyAsync(L.gs_rows, p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+                h->mc_perm = p;
+                h->mc_iperm = ip;
+                h->mc_colors = nc;
+                h->mc_offsets = off;
+            } else {
+                L.gs_rows = p;
+                dev_free(ip);
+            }
+            L.gs_off.swap(off);
+        }
+        DPCG_TRY(dev_alloc(&L.gs_off_dev, (int64_t)L.gs_off.size()));
+        DPCG_HIP(hipMemcpyAsync(L.gs_off_dev, L.gs_off.data(), L.gs_off.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        DPCG_HIP(hipStreamSynchronize(s));
+    }
+    L.smoother = DPCG_AMG_GAUSS_SEIDEL;
+    L.gs_block = n <= gs_block_rows();
+    return DPCG_OK;
+}
+
+// Chebyshev on [rho / eig_ratio, rho]: theta, delta, sigma and the coefficients of every step, in double on the host in this order
+void chebyshev_coefficients(AmgLevel &L, int degree, double eig_ratio) {
+    const double u = L.rho, lo = u / eig_ratio;
+    const double theta = (u + lo) / 2.0, delta = (u - lo) / 2.0, sigma = theta / delta;
+    L.cheb_lo = lo;
+    L.cheb_hi = u;
+    L.cheb_c1.assign(degree, 0.0);
+    L.cheb_c2.assign(degree, 0.0);
+    L.cheb_c2[0] = 1.0 / theta;
+    double rho0 = 1.0 / sigma;
+    for (int k = 1; k < degree; ++k) {
+        const double rho1 = 1.0 / (2.0 * sigma - rho0);
+        L.cheb_c1[k] = rho1 * rho0;
+        L.cheb_c2[k] = 2.0 * rho1 / delta;
+        rho0 = rho1;
+    }
+    L.smoother = DPCG_AMG_CHEBYSHEV;
 }
 
 void free_state(AmgState *S) {
@@ -845,6 +1126,12 @@ int build(dpcg_system *h, AmgState &S, AmgState *old, hipStream_t s) {
         L.tpr_a = tpr_for(L.A);
         L.tpr_p = tpr_for(L.P);
         L.tpr_pt = tpr_for(L.Pt);
+        if (S.smoother == DPCG_AMG_GAUSS_SEIDEL) {
+            DPCG_TRY(color_level(h, L, O, l, s));
+            pt.mark("amg: colouring");
+        } else if (S.smoother == DPCG_AMG_CHEBYSHEV) {
+            chebyshev_coefficients(L, S.degree, S.eig_ratio);
+        }
         DPCG_TRY(alloc_work(L, false, S.sweeps));
         if (l == 0) dev_free(L.b);                  // (level 0's right-hand side is the caller's r)
     }
@@ -863,12 +1150,24 @@ void free_amg(AmgState *&S) {
 
 int amg_launches(const AmgState *S) {
     if (!S) return 0;
-    return (int)(S->lv.size() - 1) * (2 + 2 * S->sweeps) + 1;
+    const int nu = S->sweeps;
+    int t = 1;                                        // the coarse GEMV
+    for (size_t l = 0; l + 1 < S->lv.size(); ++l) {
+        const AmgLevel &L = S->lv[l];
+        if (L.smoother == DPCG_AMG_GAUSS_SEIDEL)      // sweeps, residual, restriction, correction, sweeps
+            t += L.gs_block ? 5 : 2 * nu * (2 * ((int)L.gs_off.size() - 1) - 1) + 3;
+        else if (L.smoother == DPCG_AMG_CHEBYSHEV)    // steps, restriction, correction, residual, steps
+            t += 2 * nu * (int)L.cheb_c1.size() + 3;
+        else
+            t += 2 + 2 * nu;
+    }
+    return t;
 }
 
 int amg_rz_partials(const AmgState *S) {
     if (!S || S->lv.size() < 2) return 0;
     const AmgLevel &L = S->lv[0];
+    if (L.smoother == DPCG_AMG_GAUSS_SEIDEL) return 0;     // (its last pass covers one colour: PCG sums <r, z> itself)
     const int rpb = kBlock / L.tpr_a;
     return (int)std::max<int64_t>(1, std::min<int64_t>((L.A.n + rpb - 1) / rpb, kApplyMaxGrid));
 }
@@ -896,6 +1195,29 @@ int amg_apply(dpcg_system *h, const double *r, double *z, hipStream_t s, double 
     for (int l = 0; l < Lc; ++l) {                    // down: pre-smoothing, residual, restriction
         AmgLevel &L = S.lv[l];
         const double *B = l == 0 ? r : L.b;
+        if (L.smoother == DPCG_AMG_GAUSS_SEIDEL) {
+            gs_sweeps(L, nu, true, B, L.xa, s, done);
+            launch_row<OP_RES>(L.A, L.tpr_a, nullptr, 0.0, B, L.xa, nullptr, nullptr, nullptr, L.ra, nullptr, nullptr, s, done);
+            launch_row<OP_PLAIN>(L.Pt, L.tpr_pt, nullptr, 0.0, nullptr, nullptr, nullptr, L.ra, S.lv[l + 1].b, nullptr, nullptr, nullptr, s, done);
+            x[l] = L.xa;
+            alt[l] = L.xb;
+            continue;
+        }
+        if (L.smoother == DPCG_AMG_CHEBYSHEV) {       // from x = 0, r = b
+            const double *xin = nullptr, *din = nullptr, *rin = B;
+            double *xo = L.xa, *xo2 = L.xb, *dn = L.da, *dn2 = L.db, *rn = L.ra, *rn2 = L.rb;
+            const int deg = (int)L.cheb_c1.size();
+            for (int t = 0; t < nu * deg; ++t) {
+                const int k = t % deg;
+                launch_cheb<CHEB_STEP>(L, L.cheb_c1[k], L.cheb_c2[k], B, xin, k == 0 ? nullptr : din, rin, xo, dn, rn, nullptr, nullptr, s, done);
+                xin = xo; din = dn; rin = rn;
+                std::swap(xo, xo2); std::swap(dn, dn2); std::swap(rn, rn2);
+            }
+            launch_row<OP_PLAIN>(L.Pt, L.tpr_pt, nullptr, 0.0, nullptr, nullptr, nullptr, rin, S.lv[l + 1].b, nullptr, nullptr, nullptr, s, done);
+            x[l] = const_cast<double *>(xin);
+            alt[l] = xo;
+            continue;
+        }
         double *xc = L.xa, *xo = L.xb, *rc = L.ra, *ro = L.rb;
         launch_row<OP_PRE>(L.A, L.tpr_a, L.dinv, L.omega, B, nullptr, nullptr, nullptr, xc, rc, nullptr, nullptr, s, done);
         for (int k = 1; k < nu; ++k) {
@@ -912,6 +1234,38 @@ int amg_apply(dpcg_system *h, const double *r, double *z, hipStream_t s, double 
     for (int l = Lc - 1; l >= 0; --l) {               // up: prolongation with correction, post-smoothing
         AmgLevel &L = S.lv[l];
         const double *B = l == 0 ? r : L.b;
+        if (L.smoother == DPCG_AMG_GAUSS_SEIDEL) {    // (level 0 sweeps in z itself)
+            double *out = l == 0 ? z : alt[l];
+            launch_row<OP_ACC>(L.P, L.tpr_p, nullptr, 0.0, nullptr, x[l], nullptr, xcoarse, out, nullptr, nullptr, nullptr, s, done);
+            gs_sweeps(L, nu, false, B, out, s, done);
+            xcoarse = out;
+            continue;
+        }
+        if (L.smoother == DPCG_AMG_CHEBYSHEV) {
+            double *xc = alt[l], *xo = x[l], *dn = L.da, *dn2 = L.db, *rn = L.rb, *rn2 = L.ra;
+            launch_row<OP_ACC>(L.P, L.tpr_p, nullptr, 0.0, nullptr, x[l], nullptr, xcoarse, xc, nullptr, nullptr, nullptr, s, done);
+            launch_row<OP_RES>(L.A, L.tpr_a, nullptr, 0.0, B, xc, nullptr, nullptr, nullptr, L.ra, nullptr, nullptr, s, done);
+            const double *din = nullptr, *rin = L.ra;
+            const int deg = (int)L.cheb_c1.size();
+            for (int t = 0; t < nu * deg; ++t) {
+                const int k = t % deg;
+                const double *dk = k == 0 ? nullptr : din;
+                if (t == nu * deg - 1) {
+                    double *out = l == 0 ? z : xo;
+                    double *part = l == 0 ? part_rz : nullptr;
+                    int grid = 0;
+                    launch_cheb<CHEB_LAST>(L, L.cheb_c1[k], L.cheb_c2[k], B, xc, dk, rin, out, nullptr, nullptr, part, &grid, s, done);
+                    if (part && n_part_rz) *n_part_rz = grid;
+                    xc = out;
+                    break;
+                }
+                launch_cheb<CHEB_STEP>(L, L.cheb_c1[k], L.cheb_c2[k], B, xc, dk, rin, xo, dn, rn, nullptr, nullptr, s, done);
+                din = dn; rin = rn;
+                std::swap(xc, xo); std::swap(dn, dn2); std::swap(rn, rn2);
+            }
+            xcoarse = xc;
+            continue;
+        }
         double *xc = x[l], *xo = alt[l];
         launch_row<OP_ACC>(L.P, L.tpr_p, nullptr, 0.0, nullptr, xc, nullptr, xcoarse, xo, nullptr, nullptr, nullptr, s, done);
         std::swap(xc, xo);
@@ -931,24 +1285,37 @@ int amg_apply(dpcg_system *h, const double *r, double *z, hipStream_t s, double 
 
 extern "C" int dpcg_set_precond_amg(dpcg_handle_t h, double theta, int max_levels, int max_coarse, int sweeps, uint64_t seed,
                                     dpcg_stream_t stream) {
+    return dpcg_set_precond_amg_smoothed(h, theta, max_levels, max_coarse, sweeps, seed, DPCG_AMG_JACOBI, 2, 30.0, stream);
+}
+
+extern "C" int dpcg_set_precond_amg_smoothed(dpcg_handle_t h, double theta, int max_levels, int max_coarse, int sweeps, uint64_t seed,
+                                             int smoother, int degree, double eig_ratio, dpcg_stream_t stream) {
     if (!h) return invalid("NULL handle");
     if (!(theta >= 0.0 && theta <= 1.0)) return invalid("dpcg_set_precond_amg: theta must lie in [0, 1]");
     if (max_levels < 1 || max_levels > 64) return invalid("dpcg_set_precond_amg: max_levels must lie in 1 .. 64");
     if (max_coarse < 1) return invalid("dpcg_set_precond_amg: max_coarse must be >= 1");
     if (sweeps < 1 || sweeps > 8) return invalid("dpcg_set_precond_amg: sweeps must lie in 1 .. 8");
+    if (smoother != DPCG_AMG_JACOBI && smoother != DPCG_AMG_GAUSS_SEIDEL && smoother != DPCG_AMG_CHEBYSHEV)
+        return invalid("dpcg_set_precond_amg_smoothed: unknown smoother (DPCG_AMG_JACOBI, _GAUSS_SEIDEL or _CHEBYSHEV)");
+    if (degree < 1 || degree > 8) return invalid("dpcg_set_precond_amg_smoothed: degree must lie in 1 .. 8");
+    if (!(eig_ratio > 1.0) || !std::isfinite(eig_ratio)) return invalid("dpcg_set_precond_amg_smoothed: eig_ratio must be finite and > 1");
     hipStream_t s = (hipStream_t)stream;
     SetupScope scope(s, true);
     AmgState *old = h->amg_parked;
     h->amg_parked = nullptr;
     free_precond(h);
     const bool reusable = old && old->theta == theta && old->max_levels == max_levels &&
-                          old->max_coarse == max_coarse && old->seed == seed && !old->lv.empty() && old->lv[0].A.n == h->A.n;
+                          old->max_coarse == max_coarse && old->seed == seed && old->smoother == smoother && old->degree == degree &&
+                          old->eig_ratio == eig_ratio && !old->lv.empty() && old->lv[0].A.n == h->A.n;
     AmgState *S = new AmgState();
     S->theta = theta;
     S->max_levels = max_levels;
     S->max_coarse = max_coarse;
     S->sweeps = sweeps;
     S->seed = seed;
+    S->smoother = smoother;
+    S->degree = degree;
+    S->eig_ratio = eig_ratio;
     int st = build(h, *S, reusable ? old : nullptr, s);
     free_amg(old);
     if (st >= 0) st = ensure_work(h, 0, false, false);
@@ -1047,5 +1414,50 @@ extern "C" int dpcg_get_amg_level(dpcg_handle_t h, int level, const int64_t size
             }
         }
     }
+    return DPCG_OK;
+}
+
+extern "C" int dpcg_get_amg_smoothers(dpcg_handle_t h, int capacity, int *smoother, int *n_colors, double *cheb_lower, double *cheb_upper) {
+    if (!h) return invalid("NULL handle");
+    if (h->precond != DPCG_PRECOND_AMG || !h->amg) {
+        set_error("dpcg_get_amg_smoothers: no smoothed-aggregation preconditioner is attached");
+        return DPCG_ERR_STATE;
+    }
+    const AmgState &S = *h->amg;
+    for (int l = 0; l + 1 < (int)S.lv.size() && l < capacity; ++l) {
+        const AmgLevel &L = S.lv[l];
+        const bool gs = L.smoother == DPCG_AMG_GAUSS_SEIDEL, ch = L.smoother == DPCG_AMG_CHEBYSHEV;
+        if (smoother) smoother[l] = L.smoother;
+        if (n_colors) n_colors[l] = gs ? (int)L.gs_off.size() - 1 : 0;
+        if (cheb_lower) cheb_lower[l] = ch ? L.cheb_lo : 0.0;
+        if (cheb_upper) cheb_upper[l] = ch ? L.cheb_hi : 0.0;
+    }
+    return DPCG_OK;
+}
+
+extern "C" int dpcg_get_amg_colors(dpcg_handle_t h, int level, int64_t n, int32_t *color, dpcg_stream_t stream) {
+    if (!h) return invalid("NULL handle");
+    if (h->precond != DPCG_PRECOND_AMG || !h->amg) {
+        set_error("dpcg_get_amg_colors: no smoothed-aggregation preconditioner is attached");
+        return DPCG_ERR_STATE;
+    }
+    const AmgState &S = *h->amg;
+    if (level < 0 || level >= (int)S.lv.size() - 1) return invalid("dpcg_get_amg_colors: level must lie in 0 .. levels - 2");
+    const AmgLevel &L = S.lv[level];
+    if (L.smoother != DPCG_AMG_GAUSS_SEIDEL) {
+        set_error("dpcg_get_amg_colors: the level is not smoothed by Gauss-Seidel");
+        return DPCG_ERR_STATE;
+    }
+    if (n != L.A.n || !color) return invalid("dpcg_get_amg_colors: n is not the level's number of rows (or color is NULL)");
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<int32_t> rows(n), perm;
+    DPCG_HIP(hipMemcpyAsync(rows.data(), L.gs_rows, n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (level == 0 && h->perm) {
+        perm.resize(n);
+        DPCG_HIP(hipMemcpyAsync(perm.data(), h->perm, n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    }
+    DPCG_HIP(hipStreamSynchronize(s));
+    for (int c = 0; c + 1 < (int)L.gs_off.size(); ++c)
+        for (int32_t p = L.gs_off[c]; p < L.gs_off[c + 1]; ++p) color[perm.empty() ? rows[p] : perm[rows[p]]] = c;
     return DPCG_OK;
 }

@@ -437,6 +437,7 @@ extern "C" int dpcg_reorder(dpcg_handle_t h, int mode, dpcg_stream_t stream, int
         dev_free(h->mc_perm);            // ... and so did a cached colouring
         dev_free(h->mc_iperm);
         h->mc_colors = 0;
+        h->mc_offsets.clear();
         free_ell(h->ell_a);
         drop_graph(h);
         dev_free(h->A.val32);            // recreated on demand from the reordered values

@@ -247,6 +247,7 @@ struct dpcg_system {
     // ordering is attached.  Dropped when the handle is renumbered or destroyed.
     int32_t *mc_perm = nullptr, *mc_iperm = nullptr;
     int mc_colors = 0;
+    std::vector<int32_t> mc_offsets;      // host: where each colour's rows begin in mc_perm (mc_colors + 1 entries)
     // An IC(0) in multicolour order, applied by colour sweeps, that dpcg_update_values PARKED instead of freeing (the handle has
     // no preconditioner meanwhile): everything that depends on the pattern only -- the factor's pattern, both schedules with their
     // tile plans and maps -- is kept, and the next dpcg_set_precond_ic0_ordered(multicolour, solve) only computes the values
@@ -599,7 +600,9 @@ void launch_relabel(int64_t count, const int32_t *map, int32_t *idx, hipStream_t
 int gather_line_ratio(const CsrDev &A, double *ratio, hipStream_t s);
 int permute_csr(const CsrDev &A, const int32_t *perm, const int32_t *iperm, CsrDev &B, hipStream_t s);
 int rcm_order(const CsrDev &A, int32_t **perm_out, int32_t **iperm_out, int *n_components, hipStream_t s);
-int multicolor_order(const CsrDev &A, int32_t **perm_out, int32_t **iperm_out, int *n_colors, hipStream_t s);
+// offsets (optional): where each colour's rows begin in perm (n_colors + 1 entries)
+int multicolor_order(const CsrDev &A, int32_t **perm_out, int32_t **iperm_out, int *n_colors, hipStream_t s,
+                     std::vector<int32_t> *offsets = nullptr);
 // region-by-region numbering (dpcg_reorder.hip): `regions` searches grown at once, numbered region by region, ring by ring
 int region_order(const CsrDev &A, int regions, int32_t **perm_out, int32_t **iperm_out, hipStream_t s);
 int region_order_default_regions(int64_t n);

@@ -1070,7 +1070,8 @@ extern "C" int dpcg_set_precond_ic0_ordered(dpcg_handle_t h, int mode, int order
         if (!h->mc_perm || !keep_coloring) {
             int32_t *p = nullptr, *ip = nullptr;
             int nc = 0;
-            DPCG_TRY(multicolor_order(h->A, &p, &ip, &nc, s));
+            std::vector<int32_t> off;
+            DPCG_TRY(multicolor_order(h->A, &p, &ip, &nc, s, &off));
             if (h->fmap == h->mc_perm) {       // the attached factor keeps the arrays it was built with until it is replaced
                 h->mc_perm = h->mc_iperm = nullptr;
             } else {
@@ -1080,6 +1081,7 @@ extern "C" int dpcg_set_precond_ic0_ordered(dpcg_handle_t h, int mode, int order
             h->mc_perm = p;
             h->mc_iperm = ip;
             h->mc_colors = nc;
+            h->mc_offsets.swap(off);
         }
         cperm = h->mc_perm;
         ciperm = h->mc_iperm;

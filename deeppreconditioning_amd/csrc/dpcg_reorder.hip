@@ -1517,7 +1517,8 @@ int region_order(const CsrDev &A, int regions, int32_t **perm_out, int32_t **ipe
     return DPCG_OK;
 }
 
-int multicolor_order(const CsrDev &A, int32_t **perm_out, int32_t **iperm_out, int *n_colors, hipStream_t s) {
+int multicolor_order(const CsrDev &A, int32_t **perm_out, int32_t **iperm_out, int *n_colors, hipStream_t s,
+                     std::vector<int32_t> *offsets) {
     const int64_t n = A.n;
     if (n + 2 + kBfsBatch > 2147483000LL) return invalid("multicolour ordering: system too large");
     Buf<int32_t> color, perm, iperm, iota;
@@ -1719,6 +1720,17 @@ int multicolor_order(const CsrDev &A, int32_t **perm_out, int32_t **iperm_out, i
     DPCG_CHECK_LAUNCH();
     pt.mark("  sort by colour");
     if (n_colors) *n_colors = cmax + 1;
+    if (offsets) {                          // class sizes -> where each class begins in perm
+        Buf<int> hist;
+        DPCG_TRY(hist.alloc(64));
+        DPCG_HIP(hipMemsetAsync(hist.p, 0, 64 * sizeof(int), s));
+        hipLaunchKernelGGL(k_color_histogram, dim3(rows_grid(n, 1024)), dim3(kBlock), 0, s, n, color.p, hist.p);
+        int h_hist[64];
+        DPCG_HIP(hipMemcpyAsync(h_hist, hist.p, sizeof(h_hist), hipMemcpyDeviceToHost, s));
+        DPCG_HIP(hipStreamSynchronize(s));
+        offsets->assign((size_t)cmax + 2, 0);
+        for (int c = 0; c <= cmax; ++c) (*offsets)[c + 1] = (*offsets)[c] + h_hist[c];
+    }
     *perm_out = perm.release();
     *iperm_out = iperm.release();
     return DPCG_OK;

@@ -8,7 +8,8 @@ libdpcg.so; torch is used for device memory and streams only.
 from __future__ import annotations
 
 import ctypes as C
-from dataclasses import dataclass
+import math
+from dataclasses import dataclass, field
 
 import numpy as np
 import torch
@@ -320,10 +321,18 @@ class SmoothedAggregation(Preconditioner):
     `algebraic_multigrid` technique (test.py:95-98: pyamg's `smoothed_aggregation_solver(A).aspreconditioner(cycle="V")`), set up
     and applied on the device (dpcg_set_precond_amg in include/dpcg.h).  The same family as pyamg's default -- symmetric strength
     with `theta`, MIS(2) aggregation, the Jacobi-smoothed prolongator with omega = (4/3) / rho(D^-1 A), Galerkin coarse operators,
-    an exact solve on the coarsest level -- smoothed by damped Jacobi instead of pyamg's sequential Gauss-Seidel.  Parity with
-    pyamg's own output is not pinned (pyamg is not a dependency); `CsrSystem.amg_hierarchy()` shows what was built."""
+    an exact solve on the coarsest level -- smoothed by damped Jacobi by default instead of pyamg's sequential Gauss-Seidel.  Parity
+    with pyamg's own output is not pinned (pyamg is not a dependency); `CsrSystem.amg_hierarchy()` shows what was built.
 
-    def __init__(self, theta: float = 0.0, max_levels: int = 10, max_coarse: int = 500, sweeps: int = 1, seed: int = 0):
+    `smoother` picks the cycle's smoother; the hierarchy does not depend on it.  "jacobi" (the default) is damped Jacobi with
+    omega = (4/3) / rho.  "gauss_seidel" is symmetric Gauss-Seidel in multicolour order: every level is coloured and one sweep
+    updates colour 0, 1, .., m-1, m-2, .., 0, each colour at once.  That is the parallel counterpart of pyamg's row-by-row sweep,
+    not the same operator.  A level that needs more than 63 colours keeps Jacobi, and `amg_hierarchy().smoother` says so.
+    "chebyshev" is a Chebyshev polynomial of `degree` steps in D^-1 A on [rho / eig_ratio, rho].  `sweeps` counts smoother
+    applications for all three; `degree` and `eig_ratio` matter for "chebyshev" only."""
+
+    def __init__(self, theta: float = 0.0, max_levels: int = 10, max_coarse: int = 500, sweeps: int = 1, seed: int = 0,
+                 smoother: str = "jacobi", degree: int = 2, eig_ratio: float = 30.0):
         if not 0.0 <= float(theta) <= 1.0:
             raise ValueError("theta must lie in [0, 1]")
         if not 1 <= int(max_levels) <= 64:
@@ -334,23 +343,36 @@ class SmoothedAggregation(Preconditioner):
             raise ValueError("sweeps must lie in 1 .. 8")
         if int(seed) < 0:
             raise ValueError("seed must be >= 0")
+        if smoother not in AMG_SMOOTHERS:
+            raise ValueError(f"smoother must be one of {', '.join(AMG_SMOOTHERS)}")
+        if isinstance(degree, bool) or int(degree) != degree or not 1 <= int(degree) <= 8:
+            raise ValueError("degree must be an integer in 1 .. 8")
+        if not (math.isfinite(float(eig_ratio)) and float(eig_ratio) > 1.0):
+            raise ValueError("eig_ratio must be finite and > 1")
         self.theta, self.max_levels, self.max_coarse = float(theta), int(max_levels), int(max_coarse)
         self.sweeps, self.seed = int(sweeps), int(seed)
+        self.smoother, self.degree, self.eig_ratio = smoother, int(degree), float(eig_ratio)
 
     def _attach(self, system):
-        L.check(L.lib().dpcg_set_precond_amg(system._h, self.theta, self.max_levels, self.max_coarse, self.sweeps,
-                                             self.seed & (2**64 - 1), _stream()))
+        L.check(L.lib().dpcg_set_precond_amg_smoothed(system._h, self.theta, self.max_levels, self.max_coarse, self.sweeps,
+                                                      self.seed & (2**64 - 1), AMG_SMOOTHERS.index(self.smoother), self.degree,
+                                                      self.eig_ratio, _stream()))
 
     def __matmul__(self, r):
         raise TypeError("SmoothedAggregation needs the system matrix: attach it with CsrSystem.set_preconditioner")
 
 
+AMG_SMOOTHERS = ("jacobi", "gauss_seidel", "chebyshev")      # in the order of dpcg_amg_smoother (include/dpcg.h)
+
+
 @dataclass
 class AmgLevel:
-    """Level l of a hierarchy: the aggregate of each row (level 0: the caller's numbering), P_l and A_{l+1} as scipy CSR."""
+    """Level l of a hierarchy: the aggregate of each row (level 0: the caller's numbering), P_l and A_{l+1} as scipy CSR, and the
+    colour of each row (int32, level 0 in the caller's numbering) when the level is smoothed by Gauss-Seidel (None otherwise)."""
     aggregates: np.ndarray
     P: "object"
     A_next: "object"
+    colors: np.ndarray | None = None
 
 
 @dataclass
@@ -358,6 +380,8 @@ class AmgHierarchy:
     """What `SmoothedAggregation` built (CsrSystem.amg_hierarchy): per level the rows, nnz(A_l), nnz(P_l), rho (the Lanczos estimate
     of lambda_max(D^-1 A_l)) and omega = (4/3) / rho (0 on the coarsest level, which is solved exactly); the operator and grid
     complexities; how many levels a re-attach after `update_values` took over from the previous hierarchy (0: built afresh).
+    Per smoothed level (all but the coarsest): the smoother it uses ("jacobi" also where Gauss-Seidel was asked for and the level
+    could not be coloured), its number of colours (0 unless Gauss-Seidel) and the Chebyshev interval (lower, upper) or None.
     `level(l)` copies level l out (0 <= l < levels - 1) of the hierarchy attached NOW; it raises when that is no longer the one
     this snapshot describes (the system was re-attached meanwhile with other sizes)."""
     levels: int
@@ -369,6 +393,9 @@ class AmgHierarchy:
     operator_complexity: float
     grid_complexity: float
     reused_levels: int = 0
+    smoother: list = field(default_factory=list)
+    colors: list = field(default_factory=list)
+    chebyshev: list = field(default_factory=list)
     _system: "object" = None
 
     def level(self, l: int) -> AmgLevel:
@@ -386,7 +413,12 @@ class AmgHierarchy:
         with torch.cuda.device(self._system.device):
             L.check(L.lib().dpcg_get_amg_level(self._system._h, int(l), _np_ptr(sizes), _np_ptr(agg), _np_ptr(prp), _np_ptr(pci),
                                                _np_ptr(pv), _np_ptr(arp), _np_ptr(aci), _np_ptr(av), _stream()))
-        return AmgLevel(agg, sp.csr_matrix((pv, pci, prp), shape=(n, nc)), sp.csr_matrix((av, aci, arp), shape=(nc, nc)))
+        colors = None
+        if now.smoother[l] == "gauss_seidel":
+            colors = np.empty(n, dtype=np.int32)
+            with torch.cuda.device(self._system.device):
+                L.check(L.lib().dpcg_get_amg_colors(self._system._h, int(l), int(n), _np_ptr(colors), _stream()))
+        return AmgLevel(agg, sp.csr_matrix((pv, pci, prp), shape=(n, nc)), sp.csr_matrix((av, aci, arp), shape=(nc, nc)), colors)
 
 
 class _DevArray:
@@ -779,8 +811,15 @@ class CsrSystem:
             L.check(L.lib().dpcg_get_amg_info(self._h, cap, C.byref(nl), _np_ptr(rows), _np_ptr(nnz), _np_ptr(pnnz), _np_ptr(rho),
                                               _np_ptr(omega), C.byref(oc), C.byref(gc), C.byref(reused)))
         k = nl.value
+        sm, ncol, lo, hi = np.zeros(cap, dtype=np.int32), np.zeros(cap, dtype=np.int32), np.zeros(cap), np.zeros(cap)
+        with torch.cuda.device(self.device):
+            L.check(L.lib().dpcg_get_amg_smoothers(self._h, cap, _np_ptr(sm), _np_ptr(ncol), _np_ptr(lo), _np_ptr(hi)))
+        m = max(k - 1, 0)
+        cheb = [(float(a), float(b)) if int(t) == L.AMG_CHEBYSHEV else None for t, a, b in zip(sm[:m], lo[:m], hi[:m])]
         return AmgHierarchy(k, [int(v) for v in rows[:k]], [int(v) for v in nnz[:k]], [int(v) for v in pnnz[:k]],
-                            [float(v) for v in rho[:k]], [float(v) for v in omega[:k]], oc.value, gc.value, reused.value, self)
+                            [float(v) for v in rho[:k]], [float(v) for v in omega[:k]], oc.value, gc.value, reused.value,
+                            smoother=[AMG_SMOOTHERS[int(v)] for v in sm[:m]], colors=[int(v) for v in ncol[:m]], chebyshev=cheb,
+                            _system=self)
 
     def spectrum_bounds(self, *, max_steps: int = 1000, rtol: float = 1e-6, seed: int = 0) -> SpectrumBounds:
         """Extreme eigenvalues of M A for the attached preconditioner M (M = I without one) and kappa = lambda_max / lambda_min,

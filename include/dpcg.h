@@ -217,12 +217,36 @@ int dpcg_set_precond_callback(dpcg_handle_t h, dpcg_precond_fn fn, void *user);
  * Coarsening stops at max_coarse rows, at max_levels or when it stalls (n_c > 0.9 n); the coarsest level is solved exactly (dense
  * inverse by Cholesky on the host, a GEMV on the device): more than 4096 rows there is DPCG_ERR_INVALID, not positive definite
  * DPCG_ERR_PIVOT; a missing, zero or negative diagonal on any level is DPCG_ERR_PIVOT.  The cycle smooths with damped Jacobi (weight
- * omega, `sweeps` sweeps before and after; pyamg's default is Gauss-Seidel, which is sequential): M is symmetric positive definite.
+ * omega, `sweeps` sweeps before and after; pyamg's default is Gauss-Seidel, which is sequential -- dpcg_set_precond_amg_smoothed
+ * offers multicolour Gauss-Seidel and Chebyshev): M is symmetric positive definite.
  * Same-pattern reuse: after dpcg_update_values, attaching again with the same parameters keeps, level by level while the aggregates
  * come out unchanged, the structures of the SpGEMMs and of P^T; only values are computed again (the result equals a fresh setup bit
  * for bit; dpcg_get_amg_info's reused_levels says how many levels were taken over).  Any other preconditioner call frees what was kept.  The one-launch forms do not take this kind. */
 int dpcg_set_precond_amg(dpcg_handle_t h, double theta, int max_levels, int max_coarse, int sweeps, uint64_t seed,
                          dpcg_stream_t stream);
+/* The same hierarchy with another smoother in the cycle (dpcg_set_precond_amg = DPCG_AMG_JACOBI).  Strength, aggregates, P (still
+ * the Jacobi-smoothed prolongator), the Galerkin levels and the coarse inverse do not depend on the choice; the V(sweeps, sweeps)
+ * cycle keeps its shape and only the smoother differs.  Each is self-adjoint in the A inner product, so M stays SPD.
+ *   DPCG_AMG_GAUSS_SEIDEL: symmetric Gauss-Seidel in multicolour order.  Level l is coloured (multicolour ordering of dpcg_reorder;
+ *     level 0 reuses the handle's cached colouring); a colour pass updates every row of one colour at once,
+ *     x_i += (b_i - sum_j a_ij x_j) / a_ii; a sweep is the passes 0, 1, .., m-1, m-2, .., 0 (the repeated pass m-1 is skipped: it
+ *     is a no-op).  A level whose graph needs more than 63 colours keeps damped Jacobi (dpcg_get_amg_smoothers reports it).  pyamg
+ *     sweeps in row order instead (sequential); this is its parallel counterpart, not the same operator.
+ *   DPCG_AMG_CHEBYSHEV: Saad's Chebyshev iteration of `degree` (1 .. 8) steps with a Jacobi preconditioner on [rho_l / eig_ratio,
+ *     rho_l] (rho_l: the level's Lanczos estimate of lambda_max(D^-1 A_l), eig_ratio > 1).
+ * `sweeps` counts smoother applications for every kind; degree and eig_ratio are read for DPCG_AMG_CHEBYSHEV only (but still
+ * checked).  Argument errors are DPCG_ERR_INVALID and leave the handle as it was.  A re-attach after dpcg_update_values reuses
+ * structures (colourings included) when every parameter, smoother, degree and eig_ratio included, is the same. */
+enum dpcg_amg_smoother { DPCG_AMG_JACOBI = 0, DPCG_AMG_GAUSS_SEIDEL = 1, DPCG_AMG_CHEBYSHEV = 2 };
+int dpcg_set_precond_amg_smoothed(dpcg_handle_t h, double theta, int max_levels, int max_coarse, int sweeps, uint64_t seed,
+                                  int smoother, int degree, double eig_ratio, dpcg_stream_t stream);
+/* Per smoothed level l < min(capacity, n_levels - 1) (host arrays, any may be NULL): the smoother the level USES (a Gauss-Seidel
+ * level that could not be coloured reports DPCG_AMG_JACOBI), its number of colours (0 unless Gauss-Seidel) and the Chebyshev
+ * interval [lower, upper] (0 unless Chebyshev).  DPCG_ERR_STATE when the handle's preconditioner is not AMG. */
+int dpcg_get_amg_smoothers(dpcg_handle_t h, int capacity, int *smoother, int *n_colors, double *cheb_lower, double *cheb_upper);
+/* color[n] (host): the colour of each row of smoothed level `level` (level 0 in the caller's numbering).  DPCG_ERR_INVALID when
+ * level or n is not the attached hierarchy's (nothing written), DPCG_ERR_STATE when the level is not Gauss-Seidel-smoothed. */
+int dpcg_get_amg_colors(dpcg_handle_t h, int level, int64_t n, int32_t *color, dpcg_stream_t stream);
 /* *n_levels; per level l < capacity (host arrays, any may be NULL): rows, nnz of A_l, nnz of P_l (0 on the coarsest), rho and
  * omega (0 on the coarsest); operator complexity sum nnz(A_l) / nnz(A_0), grid complexity sum n_l / n_0; *reused_levels: how many
  * levels the setup that built this hierarchy took over from a parked one (same-pattern reuse; 0 for a fresh build).  Any out
