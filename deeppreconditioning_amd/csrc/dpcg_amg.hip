@@ -285,7 +285,7 @@ __global__ __launch_bounds__(kBlock) void k_sg_products(int64_t m, const int32_t
         cnt[i] = (int32_t)std::min<int64_t>(c, 0x7fffffff);
         int64_t p = 1;
         while (p < c) p <<= 1;
-        long_pad[i] = c > kSgCap ? (int32_t)std::min<int64_t>(p, 0x40000000) : 0;
+        long_pad[i] = c <= kSgCap ? 0 : p > 0x40000000 ? 0x7fffffff : (int32_t)p;   // (0x7fffffff: no scratch can hold it)
     }
 }
 
@@ -375,6 +375,14 @@ __global__ __launch_bounds__(64) void k_spgemm(int64_t m, const int32_t *__restr
 }
 
 __global__ void k_set_last(int32_t *rp, int64_t n) { rp[n] = 0; }
+
+// *total += sum of v[0 .. n) in 64 bits (integers: the order does not matter): what an int32 scan of v would wrap on
+__global__ __launch_bounds__(kBlock) void k_sum_i64(int64_t n, const int32_t *__restrict__ v, unsigned long long *total) {
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    unsigned long long t = 0;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) t += (unsigned long long)(uint32_t)v[i];
+    if (t) atomicAdd(total, t);
+}
 
 // ---- apply kernels ------------------------------------------------------------------------------------------------------
 enum AmgOp { OP_PRE = 0, OP_SWEEP = 1, OP_POST = 2, OP_ACC = 3, OP_PLAIN = 4, OP_RES = 5 };
@@ -711,15 +719,22 @@ int spgemm(const CsrDev &X, const CsrDev &Y, int64_t ncols, CsrDev &C, int epi, 
     DPCG_TRY(t.alloc(&cnt, m));
     DPCG_TRY(t.alloc(&lpad, m + 1));
     DPCG_TRY(t.alloc(&loff, m + 1));
+    unsigned long long *total = nullptr;
+    DPCG_TRY(t.alloc(&total, 1));
     hipLaunchKernelGGL(k_sg_products, dim3(grid_of(m)), dim3(kBlock), 0, s, m, X.rowptr, X.col, Y.rowptr, cnt, lpad);
     hipLaunchKernelGGL(k_set_last, dim3(1), dim3(1), 0, s, lpad, m);
-    DPCG_TRY(exclusive_scan_i32(lpad, loff, m + 1, s));
-    int32_t scratch = 0;
-    DPCG_TRY(read1(loff + m, &scratch, s));
-    if (scratch < 0) {
+    // the scratch offsets are an int32 scan: its total is checked in 64 bits first (a sum past 2^32 would wrap back to a small
+    // positive number, and the long rows would be sorted outside the scratch)
+    DPCG_HIP(hipMemsetAsync(total, 0, sizeof(unsigned long long), s));
+    hipLaunchKernelGGL(k_sum_i64, dim3(grid_of(m)), dim3(kBlock), 0, s, m, lpad, total);
+    unsigned long long scratch64 = 0;
+    DPCG_TRY(read1(total, &scratch64, s));
+    if (scratch64 >= 0x7fffffffull) {
         set_error("dpcg_set_precond_amg: the long rows of a Galerkin product need more than 2^31 scratch entries");
         return DPCG_ERR_INVALID;
     }
+    DPCG_TRY(exclusive_scan_i32(lpad, loff, m + 1, s));
+    const int32_t scratch = (int32_t)scratch64;
     uint64_t *gkey = nullptr;
     double *gval = nullptr;
     DPCG_TRY(t.alloc(&gkey, std::max<int64_t>(1, scratch)));
@@ -736,13 +751,16 @@ int spgemm(const CsrDev &X, const CsrDev &Y, int64_t ncols, CsrDev &C, int epi, 
         hipLaunchKernelGGL((k_spgemm<SG_COUNT, SG_PLAIN>), dim3(grid), dim3(64), 0, s, m, X.rowptr, X.col, X.val, Y.rowptr, Y.col,
                            Y.val, cnt, loff, gkey, gval, nullptr, nullptr, nullptr, len, nullptr, nullptr, nullptr, 0.0);
         hipLaunchKernelGGL(k_set_last, dim3(1), dim3(1), 0, s, len, m);
-        DPCG_TRY(exclusive_scan_i32(len, C.rowptr, m + 1, s));
-        int32_t nnz = 0;
-        DPCG_TRY(read1(C.rowptr + m, &nnz, s));
-        if (nnz < 0) {
+        DPCG_HIP(hipMemsetAsync(total, 0, sizeof(unsigned long long), s));
+        hipLaunchKernelGGL(k_sum_i64, dim3(grid_of(m)), dim3(kBlock), 0, s, m, len, total);
+        unsigned long long nnz64 = 0;
+        DPCG_TRY(read1(total, &nnz64, s));
+        if (nnz64 > 0x7fffffffull) {
             set_error("dpcg_set_precond_amg: a Galerkin product has more than 2^31 entries");
             return DPCG_ERR_INVALID;
         }
+        DPCG_TRY(exclusive_scan_i32(len, C.rowptr, m + 1, s));
+        const int32_t nnz = (int32_t)nnz64;
         C.nnz = nnz;
         DPCG_TRY(dev_alloc(&C.col, std::max<int64_t>(1, nnz)));
         DPCG_TRY(dev_alloc(&C.val, std::max<int64_t>(1, nnz)));
@@ -1303,7 +1321,6 @@ extern "C" int dpcg_set_precond_amg_smoothed(dpcg_handle_t h, double theta, int 
     SetupScope scope(s, true);
     AmgState *old = h->amg_parked;
     h->amg_parked = nullptr;
-    free_precond(h);
     const bool reusable = old && old->theta == theta && old->max_levels == max_levels &&
                           old->max_coarse == max_coarse && old->seed == seed && old->smoother == smoother && old->degree == degree &&
                           old->eig_ratio == eig_ratio && !old->lv.empty() && old->lv[0].A.n == h->A.n;
@@ -1316,6 +1333,8 @@ extern "C" int dpcg_set_precond_amg_smoothed(dpcg_handle_t h, double theta, int 
     S->smoother = smoother;
     S->degree = degree;
     S->eig_ratio = eig_ratio;
+    // built before the attached preconditioner is freed: on failure that one stays (the build reads only the handle's matrix,
+    // permutation and cached colouring, none of which belongs to the preconditioner)
     int st = build(h, *S, reusable ? old : nullptr, s);
     free_amg(old);
     if (st >= 0) st = ensure_work(h, 0, false, false);
@@ -1324,6 +1343,7 @@ extern "C" int dpcg_set_precond_amg_smoothed(dpcg_handle_t h, double theta, int 
         free_amg(S);
         return st;
     }
+    free_precond(h);
     h->amg = S;
     h->precond = DPCG_PRECOND_AMG;
     DPCG_CHECK_LAUNCH();

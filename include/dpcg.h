@@ -216,9 +216,10 @@ int dpcg_set_precond_callback(dpcg_handle_t h, dpcg_precond_fn fn, void *user);
  *   that sums every entry in one fixed order (two setups give the same bits).
  * Coarsening stops at max_coarse rows, at max_levels or when it stalls (n_c > 0.9 n); the coarsest level is solved exactly (dense
  * inverse by Cholesky on the host, a GEMV on the device): more than 4096 rows there is DPCG_ERR_INVALID, not positive definite
- * DPCG_ERR_PIVOT; a missing, zero or negative diagonal on any level is DPCG_ERR_PIVOT.  The cycle smooths with damped Jacobi (weight
- * omega, `sweeps` sweeps before and after; pyamg's default is Gauss-Seidel, which is sequential -- dpcg_set_precond_amg_smoothed
- * offers multicolour Gauss-Seidel and Chebyshev): M is symmetric positive definite.
+ * DPCG_ERR_PIVOT; a missing, zero or negative diagonal on any level is DPCG_ERR_PIVOT.  On any failure the previous preconditioner
+ * stays.  The cycle smooths with damped Jacobi (weight omega, `sweeps` sweeps before and after; pyamg's default is Gauss-Seidel,
+ * which is sequential -- dpcg_set_precond_amg_smoothed offers multicolour Gauss-Seidel and Chebyshev): M is symmetric positive
+ * definite.
  * Same-pattern reuse: after dpcg_update_values, attaching again with the same parameters keeps, level by level while the aggregates
  * come out unchanged, the structures of the SpGEMMs and of P^T; only values are computed again (the result equals a fresh setup bit
  * for bit; dpcg_get_amg_info's reused_levels says how many levels were taken over).  Any other preconditioner call frees what was kept.  The one-launch forms do not take this kind. */
