@@ -96,6 +96,13 @@ SIGNATURES = {
     "dpcg_convnet_plan_info": (_int, [_p, _int, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
     "dpcg_convnet_plan_output": (_int, [_p, _p, _p, _p, _p]),
     "dpcg_convnet_forward": (_int, [_p, _p, _p, _p, _p, _p, _p, _p, _int, _p]),
+    "dpcg_unet_plan_create": (_int, [C.POINTER(_p), _int, _i64, _i64, _i64, _p, _p]),
+    "dpcg_unet_plan_rebuild": (_int, [_p, _int, _i64, _i64, _i64, _p, _p]),
+    "dpcg_unet_plan_destroy": (_int, [_p]),
+    "dpcg_unet_plan_info": (_int, [_p, _int, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
+    "dpcg_unet_plan_level_indices": (_int, [_p, _int, _p, _p]),
+    "dpcg_unet_plan_output": (_int, [_p, _p, _p, _p, _p]),
+    "dpcg_unet_forward": (_int, [_p, _p, _p, _p, _p, _p, _p, _int, _p, _p, _p]),
 }
 
 

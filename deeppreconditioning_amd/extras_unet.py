@@ -1,15 +1,17 @@
-"""OUT OF SCOPE -- fenced off.  `PreconditionerSparseUNet` with its sub-manifold, strided and inverse sparse convolutions
+"""`PreconditionerSparseUNet` with its sub-manifold, strided and inverse sparse convolutions
 (`uibk/deep_preconditioning/model.py:62-179`), restated on plain torch ops.
 
-SURVEY.md section 8-f1 names `model.py:13-59` (`PreconditionerNet`) only, and section 2 marks the U-Net variant out of scope; this
-file exists because `params.yaml` of the reference can select `model: PreconditionerSparseUNet` and the compat shim resolves the
-reference's import lines.  Nothing here is on the hot path, nothing here is hand-written HIP, and no parity claim is made
-beyond tests/test_unet_extras.py (dense `conv2d` restatements on CPU).  `deeppreconditioning_amd.model` resolves these names
-lazily (module `__getattr__`).
+`params.yaml` of the reference selects the network that emits L: `model: PreconditionerNet` or `model:
+PreconditionerSparseUNet` (test.py:215, train.py:154).  The modules here are the U-Net's torch restatement, pinned to dense
+`conv2d` restatements on CPU (tests/test_unet_extras.py).  Inference on the GPU -- no autograd, CUDA fp32 features, int32
+indices, the reference's structure, `DPCG_CNN_TORCH` not 1 -- runs the hand-written HIP forward instead (unet_hip.py,
+csrc/dpcg_unet.hip: device rulebooks once per pattern, gathered GEMMs on the fp32 matrix cores, L written into
+`output.lower_csr`).  Training and everything else run the torch ops below.  `deeppreconditioning_amd.model` resolves these
+names lazily (module `__getattr__`).
 
-Also here, for the same reason (the reference's scripts/compare_meshes.py:65 calls `metrics.condition_loss`): the two dense
-diagnostics of metrics.py:58-100, `hutchinson_trace` and `condition_loss`, as plain torch restatements;
-`deeppreconditioning_amd.metrics` resolves them lazily too."""
+Also here (the reference's scripts/compare_meshes.py:65 calls `metrics.condition_loss`): the two dense diagnostics of
+metrics.py:58-100, `hutchinson_trace` and `condition_loss`, as plain torch restatements; `deeppreconditioning_amd.metrics`
+resolves them lazily too."""
 
 from __future__ import annotations
 
@@ -153,6 +155,14 @@ class PreconditionerSparseUNet(nn.Module):
         self.out_conv = seq(SubMConv2d(c[1], c[5], 1, padding=0))                     # model.py:137-139
 
     def forward(self, input_: SparseBatch) -> SparseBatch:
+        """The `L` part of the `L @ L.T` preconditioner (model.py:141-179), on every output channel.
+
+        Inference on the GPU takes the HIP path (`unet_hip.hip_unet_forward`; the output carries `lower_csr`, channel 0 as a
+        lower-triangular CSR).  Training (autograd), CPU tensors and modules of another structure take the torch ops below;
+        `DPCG_CNN_TORCH=1` forces them."""
+        from . import unet_hip
+        if unet_hip.hip_unet_applies(self, input_):
+            return unet_hip.hip_unet_forward(self, input_)
         input_ = SparseBatch(input_.features, input_.indices, input_.spatial_shape, input_.batch_size, {})
         enc1 = self.enc1(input_)                                                      # model.py:143-147
         enc2 = self.enc2(self.down1(enc1))

@@ -1,5 +1,5 @@
 """spconv-free forward pass of `PreconditionerNet` (drop-in for `uibk/deep_preconditioning/model.py:13-59`; the U-Net
-variant of model.py:62-179 is out of scope and fenced off in extras_unet.py, resolved lazily).
+variant of model.py:62-179 lives in extras_unet.py with its HIP forward in unet_hip.py, both resolved lazily).
 
 `spconv` ships CUDA-only wheels (`pyproject.toml:20`), so on ROCm the reference model cannot even be imported.
 This module re-states the pieces the network needs on plain PyTorch-ROCm ops -- the host code the north star
@@ -309,9 +309,9 @@ def forward_cost(net, t: SparseBatch) -> dict:
     return {"layers": out, "flops": total_f, "min_hbm_bytes": total_b}
 
 
-# `PreconditionerSparseUNet` and its sub-manifold / inverse convolutions (model.py:62-179 of the reference) are OUTSIDE the
-# hot-path scope (SURVEY.md 8-f1 names model.py:13-59 only): they live, fenced off, in extras_unet.py and resolve lazily so
-# that `params.yaml: model: PreconditionerSparseUNet` (test.py:215, train.py:154) and the reference's import lines keep working.
+# `PreconditionerSparseUNet` and its sub-manifold / inverse convolutions (model.py:62-179 of the reference) live in
+# extras_unet.py (torch restatement) and unet_hip.py (HIP inference path, `unet_forward_cost`); they resolve lazily so that
+# `params.yaml: model: PreconditionerSparseUNet` (test.py:215, train.py:154) and the reference's import lines keep working.
 _UNET_NAMES = ("SubMConv2d", "SparseInverseConv2d", "sparse_add", "PreconditionerSparseUNet")
 
 
@@ -319,6 +319,9 @@ def __getattr__(name):
     if name in _UNET_NAMES:
         from . import extras_unet
         return getattr(extras_unet, name)
+    if name == "unet_forward_cost":
+        from . import unet_hip
+        return unet_hip.unet_forward_cost
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

@@ -447,6 +447,38 @@ int dpcg_convnet_forward(dpcg_convnet_plan_t plan, const int32_t *channels, cons
                          const float *const *biases, const float *const *prelu, const float *features_in,
                          float *features_out, double *lower_val, int lower_softplus, dpcg_stream_t stream);
 
+/* ---- the U-Net variant: PreconditionerSparseUNet (model.py:62-179) ----------------------------------------------------
+ * Fixed structure (extras_unet.py states it on torch ops): levels S0 (the input sites) .. S4, each made by a stride-2,
+ * padding-1, 3 x 3 convolution of the previous one; 3 x 3 submanifold convolutions on S0 .. S3 (one rulebook per level,
+ * shared by the encoder and the decoder layer); inverse convolutions back up through the stride-2 rulebooks read backwards,
+ * each followed by LeakyReLU and the skip add of the encoder output on the same level; a pointwise out_conv on S0 with
+ * model.py:169-173 applied to every channel.  A PLAN per sparsity pattern holds the levels and rulebooks (built on the device,
+ * no sort, no atomics); the FORWARD runs the 17 layers as gathered GEMMs and writes channel 0 of the output into the
+ * lower-triangular CSR of S0 (fp64 values).  Invalid sites (outside the image, duplicates) give DPCG_ERR_INVALID; unsorted
+ * ones too, with "sorted" in the message.  indices: as for dpcg_convnet_plan_create. */
+typedef struct dpcg_unet_plan *dpcg_unet_plan_t;
+int dpcg_unet_plan_create(dpcg_unet_plan_t *out, int batch, int64_t height, int64_t width, int64_t nnz,
+                          const int32_t *indices, dpcg_stream_t stream);
+/* the same for ANOTHER pattern in an existing plan, reusing its device memory; on failure the plan is left empty */
+int dpcg_unet_plan_rebuild(dpcg_unet_plan_t plan, int batch, int64_t height, int64_t width, int64_t nnz,
+                           const int32_t *indices, dpcg_stream_t stream);
+int dpcg_unet_plan_destroy(dpcg_unet_plan_t plan);
+/* sites and image size of level `level` (0 .. 4); nnz_lower: entries with col <= row of S0 */
+int dpcg_unet_plan_info(dpcg_unet_plan_t plan, int level, int64_t *sites, int64_t *height, int64_t *width, int64_t *nnz_lower);
+/* the sites of level `level` as (sites, 3) int32 indices sorted by (batch, row, col), device */
+int dpcg_unet_plan_level_indices(dpcg_unet_plan_t plan, int level, int32_t *indices_out, dpcg_stream_t stream);
+/* the output sites (= S0, sorted) and the pattern of the lower-triangular CSR over batch * height rows; any may be NULL */
+int dpcg_unet_plan_output(dpcg_unet_plan_t plan, int32_t *indices_out, int32_t *lower_rowptr, int32_t *lower_col,
+                          dpcg_stream_t stream);
+/* channels: host, 6 (c[0] .. c[5] of the module).  Layers in the order enc1 down1 enc2 down2 enc3 down3 enc4 bottleneck up3
+ * dec3 up2 dec2 up1 dec1 up0 dec0 out_conv; layer_dims: host, (C_in, C_out) of each layer's weights, checked against
+ * `channels`; weights[l]: device fp32 KRSC (C_out, 3, 3, C_in), out_conv (C_out, 1, 1, C_in); biases[l]: device or NULL;
+ * slopes: host, the LeakyReLU slope after layers 0 .. 15.  features_in: device fp32 (S0, in_channels).  features_out: device
+ * fp32 (S0, c[5]) or NULL; lower_val: device fp64 [nnz_lower] (channel 0) or NULL.  Enqueues on `stream`; no atomics. */
+int dpcg_unet_forward(dpcg_unet_plan_t plan, const int32_t *channels, const int32_t *layer_dims, const float *const *weights,
+                      const float *const *biases, const float *slopes, const float *features_in, int in_channels,
+                      float *features_out, double *lower_val, dpcg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
