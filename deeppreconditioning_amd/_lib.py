@@ -62,6 +62,9 @@ SIGNATURES = {
     "dpcg_set_precond_ict": (_int, [_p, _int, _int, _dbl, _p]),
     "dpcg_set_precond_icholt": (_int, [_p, _int, _int, _dbl, _p]),
     "dpcg_set_precond_ilut": (_int, [_p, _int, _int, _dbl, _p]),
+    "dpcg_set_precond_fsai": (_int, [_p, _int, _p]),
+    "dpcg_set_precond_fsai_pattern": (_int, [_p, _i64, _p, _p, _int, _p]),
+    "dpcg_get_fsai_info": (_int, [_p, _p]),
     "dpcg_get_lu_factors": (_int, [_p, C.POINTER(_i64), C.POINTER(_i64), _p, _p, _p, _p, _p, _p]),
     "dpcg_get_reduction_geometry": (_int, [_p, _p]),
     "dpcg_get_chip_info": (_int, [_p, _p, _p]),

@@ -19,7 +19,7 @@ from ._lib import BREAKDOWN, DpcgError
 from .cg import preconditioned_conjugate_gradient
 from .io import coo_to_csr_device
 from .model import lower_factor_csr, tril_batch_from_csr
-from .operators import IC0, ICT, ILUT, ICholT, CsrSystem, Identity, Jacobi, LLtMultiply, SmoothedAggregation
+from .operators import FSAI, IC0, ICT, ILUT, ICholT, CsrSystem, Identity, Jacobi, LLtMultiply, SmoothedAggregation
 
 PARAMETERS = ["kappas", "densities", "iterations", "setups", "durations", "totals", "successes"]  # test.py:180
 
@@ -50,6 +50,10 @@ COMPARABILITY = {
     "incomplete_lu": "algorithm per Saad's dual-threshold ILUT(p, tau) as restated in tests/ilut_restatement.py (M = L U multiplied, "
                      "test.py:90-93); ilupp binary absent: values unpinned; ilupp.ilut's own default arguments cannot be read here, "
                      "icholt's (add_fill_in=1, threshold=0.1) are assumed",
+    "sparse_approximate_inverse": "not in the reference: the factorised sparse approximate inverse (FSAI, Kolotilina & Yeremin 1993) on "
+                                  "tril(A) -- the closed-form optimum of ||I - L^T U_A||_F on a fixed pattern, the untrained twin of "
+                                  "`learned`; M = L L^T multiplied",
+    "sparse_approximate_inverse_level2": "not in the reference: FSAI on the lower triangle of the pattern of A^2",
 }
 
 
@@ -120,6 +124,10 @@ class BenchmarkSuite:
             return IC0("solve", ordering="multicolor")
         if name == "incomplete_lu":                 # test.py:90-93 (opt-in): ilupp.ilut, the factors MULTIPLIED (M = L U)
             return ILUT("multiply", add_fill_in=1, threshold=0.1)
+        if name == "sparse_approximate_inverse":    # FSAI on tril(A) (opt-in; not in the reference)
+            return FSAI(level=1)
+        if name == "sparse_approximate_inverse_level2":    # ... on the lower triangle of the pattern of A^2 (opt-in)
+            return FSAI(level=2)
         if name == "algebraic_multigrid":           # test.py:95-98 (opt-in): smoothed aggregation, one V-cycle per update
             return SmoothedAggregation()
         if name == "algebraic_multigrid_gauss_seidel":     # the same hierarchy, multicolour Gauss-Seidel smoothing (opt-in)

@@ -351,6 +351,7 @@ void free_precond(dpcg_system *h, bool keep_parked) {
     h->precond_user = nullptr;
     free_amg(h->amg);
     if (!keep_parked) free_amg(h->amg_parked);
+    if (keep_parked) fsai_detach(h->fsai); else free_fsai(h->fsai);
     h->precond = DPCG_PRECOND_NONE;
 }
 

@@ -70,6 +70,14 @@ void free_csr(CsrDev &c);
 int icholt_factor(const CsrDev &A, int add_fill_in, double threshold, CsrDev &Lf, hipStream_t s);
 // dpcg_ilut.hip: Saad's dual-threshold ILUT of a CSR matrix into owned L (unit lower, diagonal last) and U (upper, diagonal first)
 int ilut_factor(const CsrDev &A, int add_fill_in, double threshold, CsrDev &Lf, CsrDev &Uf, hipStream_t s);
+// dpcg_fsai.hip: the factorised sparse approximate inverse of the handle's matrix (caller's numbering) into an owned lower-triangular
+// CSR; level 1 .. 3, or 0 with an explicit lower pattern on the device (taken over).  The handle's FsaiCache serves and is refreshed.
+int fsai_factor(dpcg_system *h, int level, int64_t pat_nnz, int32_t *pat_rp, int32_t *pat_ci, CsrDev &Lf, hipStream_t s);
+int fsai_upload_pattern(int64_t n, int64_t nnz, const int32_t *rowptr, const int32_t *col, int memspace, int32_t **rp_out, int32_t **ci_out,
+                        hipStream_t s);
+void free_fsai(FsaiCache *&c);
+void fsai_detach(FsaiCache *c);                         // the handle's preconditioner is no longer this factor
+void fsai_mark_attached(FsaiCache *c);
 void free_parked(dpcg_system *h);                       // dpcg_api.hip: the multicolour IC(0) parked by dpcg_update_values
 void free_levels(Levels &l);
 int count_levels_on_demand(dpcg_system *h);   // dpcg_precond.hip

@@ -213,6 +213,7 @@ void launch_fill_pending(double *v, int64_t n, hipStream_t s);
 void launch_sfs_block_max(const int32_t *blk, int nblk, const int32_t *lo_rowptr, int *out_dev, hipStream_t s);
 
 struct AmgState;   // dpcg_amg.hip: a smoothed-aggregation hierarchy
+struct FsaiCache;  // dpcg_fsai.hip: what the symbolic phase of an FSAI factor leaves on the handle
 
 // (dpcg_chip_trsv.hip; the comment is with ChipTrsvDesc below)
 struct ChipTrsvLists {
@@ -266,6 +267,9 @@ struct dpcg_system {
     // DPCG_PRECOND_AMG (dpcg_amg.hip): the hierarchy; amg_parked: the one dpcg_update_values set aside, whose pattern-only parts the
     // next dpcg_set_precond_amg takes over (any other preconditioner call frees it)
     dpcg::AmgState *amg = nullptr, *amg_parked = nullptr;
+    // dpcg_set_precond_fsai (dpcg_fsai.hip): pattern, gather map and binning of the last FSAI factor, keyed on level | explicit pattern and
+    // kept across dpcg_update_values (the next attach computes only values); any other preconditioner call frees it
+    dpcg::FsaiCache *fsai = nullptr;
     // dpcg_reorder: the handle iterates on A = P A_user P^T; perm[new] = old, iperm[old] = new (device)
     int32_t *perm = nullptr, *iperm = nullptr;
     dpcg::CsrDev A_user;                  // the caller's matrix once A has been replaced by the reordered one

@@ -1474,6 +1474,50 @@ extern "C" int dpcg_set_precond_icholt(dpcg_handle_t h, int mode, int add_fill_i
     return st;
 }
 
+// The factorised sparse approximate inverse (contract: tests/fsai_restatement.py; device routine: dpcg_fsai.hip): an LLT_MULTIPLY
+// factor computed from the CALLER's matrix.  The previous preconditioner stays when it fails; the symbolic phase stays on the handle.
+namespace {
+int attach_fsai(dpcg_system *h, int level, int64_t pat_nnz, int32_t *pat_rp, int32_t *pat_ci, hipStream_t s) {
+    CsrDev Lf;
+    int st = fsai_factor(h, level, pat_nnz, pat_rp, pat_ci, Lf, s);
+    if (st < 0) return st;
+    FsaiCache *cache = h->fsai;         // (free_precond frees everything else, a parked factor included)
+    h->fsai = nullptr;
+    free_precond(h);
+    h->fsai = cache;
+    h->L = Lf;
+    st = finish_llt(h, DPCG_PRECOND_LLT_MULTIPLY, s);
+    if (st < 0) {
+        h->fsai = nullptr;
+        free_precond(h);
+        h->fsai = cache;
+        return st;
+    }
+    fsai_mark_attached(h->fsai);
+    return st;
+}
+}  // namespace
+
+extern "C" int dpcg_set_precond_fsai(dpcg_handle_t h, int level, dpcg_stream_t stream) {
+    if (!h) return invalid("NULL handle");
+    if (level < 1 || level > 3) return invalid("dpcg_set_precond_fsai: level must be 1, 2 or 3");
+    hipStream_t s = (hipStream_t)stream;
+    SetupScope scope(s, true);          // (the preconditioner being replaced may be in use on another stream)
+    return attach_fsai(h, level, 0, nullptr, nullptr, s);
+}
+
+extern "C" int dpcg_set_precond_fsai_pattern(dpcg_handle_t h, int64_t nnz, const int32_t *rowptr, const int32_t *col, int memspace,
+                                             dpcg_stream_t stream) {
+    if (!h) return invalid("NULL handle");
+    if (nnz <= 0 || nnz > 2147483647LL || !rowptr || !col) return invalid("dpcg_set_precond_fsai_pattern: bad arguments");
+    if (memspace != DPCG_HOST && memspace != DPCG_DEVICE) return invalid("dpcg_set_precond_fsai_pattern: bad memspace");
+    hipStream_t s = (hipStream_t)stream;
+    SetupScope scope(s, true);
+    int32_t *rp = nullptr, *ci = nullptr;
+    DPCG_TRY(fsai_upload_pattern(h->A.n, nnz, rowptr, col, memspace, &rp, &ci, s));
+    return attach_fsai(h, 0, nnz, rp, ci, s);
+}
+
 extern "C" int dpcg_get_factor(dpcg_handle_t h, int32_t *rowptr, int32_t *col, double *val) {
     if (!h) return invalid("NULL handle");
     if (h->precond != DPCG_PRECOND_LLT_MULTIPLY && h->precond != DPCG_PRECOND_LLT_SOLVE) {

@@ -295,6 +295,58 @@ class ILUT(Preconditioner):
         raise TypeError("ILUT needs the system matrix: attach it with CsrSystem.set_preconditioner")
 
 
+class FSAI(Preconditioner):
+    """The factorised sparse approximate inverse (Kolotilina & Yeremin 1993): for every column i the dense SPD system
+    A[P_i, P_i] y = e_1 on P_i = {j >= i : (j, i) in P} gives L[P_i, i] = y / sqrt(y_1); M = L L^T approximates A^-1 (SPD for every
+    SPD A) and is only ever multiplied: z = L (L^T r), two dependency-free SpMVs.  Not in the reference -- the closed-form
+    counterpart of the factor its network is trained to emit.
+
+    level=k (1, 2 or 3): P = the structural pattern of A^k (level 1: tril(A), as IC(0)).  pattern=: tril(P) by rows as a scipy
+    matrix or (rowptr, col) arrays -- lower triangular, ascending columns, the diagonal in every row; values are ignored.
+    The factor equals tests/fsai_restatement.py bit for bit; `CsrSystem.factor()` returns it, `CsrSystem.fsai_info()` describes
+    it.  See dpcg_set_precond_fsai in include/dpcg.h for the limits (local systems of at most 64 unknowns).
+
+    level and pattern are mutually exclusive: with a pattern, level must be left at its default (1, which then means nothing) or
+    be None; any other level beside a pattern raises."""
+
+    def __init__(self, level=1, pattern=None):
+        if pattern is not None and not (level is None or (level == 1 and not isinstance(level, bool))):
+            raise ValueError("level and pattern are mutually exclusive")
+        if pattern is None:
+            level = 1 if level is None else level
+            if isinstance(level, bool) or not isinstance(level, (int, np.integer)) or not 1 <= int(level) <= 3:
+                raise ValueError("level must be an integer in 1..3")
+            self.level, self.pattern = int(level), None
+        else:
+            if _is_scipy(pattern):
+                P = pattern.tocsr()
+                if not P.has_sorted_indices:
+                    P = P.sorted_indices()
+                rp, ci = P.indptr, P.indices
+            else:
+                try:
+                    rp, ci = pattern
+                except (TypeError, ValueError):
+                    raise ValueError("pattern must be a scipy sparse matrix or a (rowptr, col) pair") from None
+            rp = np.ascontiguousarray(rp, dtype=np.int32)
+            ci = np.ascontiguousarray(ci, dtype=np.int32)
+            if rp.ndim != 1 or ci.ndim != 1 or rp.size < 2 or int(rp[-1]) != ci.size or ci.size == 0:
+                raise ValueError("pattern: rowptr / col do not describe a CSR pattern")
+            self.level, self.pattern = None, (rp, ci)
+
+    def _attach(self, system):
+        if self.pattern is None:
+            L.check(L.lib().dpcg_set_precond_fsai(system._h, self.level, _stream()))
+            return
+        rp, ci = self.pattern
+        if rp.size != system.n + 1:
+            raise ValueError("pattern size mismatch")
+        L.check(L.lib().dpcg_set_precond_fsai_pattern(system._h, ci.size, _np_ptr(rp), _np_ptr(ci), L.HOST, _stream()))
+
+    def __matmul__(self, r):
+        raise TypeError("FSAI needs the system matrix: attach it with CsrSystem.set_preconditioner")
+
+
 class ICT(Preconditioner):
     """Thresholded incomplete Cholesky on a STATIC pattern -- tril(A) plus level-1 fill -- with MATLAB's 'ict' drop rule
     (contract: oracle/oracle.py::ict).  Not what `ilupp.icholt` computes (that is `ICholT`: a per-column entry count instead
@@ -755,6 +807,14 @@ class CsrSystem:
         v = np.empty(nnz, dtype=np.float64)
         L.check(L.lib().dpcg_get_factor(self._h, _np_ptr(rp), _np_ptr(ci), _np_ptr(v)))
         return rp, ci, v
+
+    def fsai_info(self) -> dict:
+        """The attached `FSAI` factor (dpcg_get_fsai_info): level (0: explicit pattern), the largest local system, the columns per
+        width class of the device kernels, whether the last attach reused the symbolic phase.  DpcgError (ERR_STATE) otherwise."""
+        out = (C.c_int32 * 8)()
+        L.check(L.lib().dpcg_get_fsai_info(self._h, out))
+        return {"level": out[0], "max_m": out[1], "columns_by_width": {w: out[2 + k] for k, w in enumerate((4, 8, 16, 32, 64))},
+                "pattern_reused": bool(out[7])}
 
     def lu_factors(self):
         """The attached `ILUT` factors (L, U) as scipy CSR in the caller's numbering: L unit lower (diagonal last), U upper

@@ -195,6 +195,35 @@ int dpcg_set_precond_ilut(dpcg_handle_t h, int mode, int add_fill_in, double thr
  * L unit lower (diagonal last), U upper (diagonal first), columns ascending.  DPCG_ERR_STATE when no L U factor is set. */
 int dpcg_get_lu_factors(dpcg_handle_t h, int64_t *l_nnz, int64_t *u_nnz, int32_t *l_rowptr, int32_t *l_col, double *l_val,
                         int32_t *u_rowptr, int32_t *u_col, double *u_val);
+/* The factorised sparse approximate inverse (FSAI; Kolotilina & Yeremin, SIAM J. Matrix Anal. Appl. 14 (1993)): the factor that
+ * is MADE to be multiplied.  P: a symmetric pattern with the diagonal; for column i, P_i = { j >= i : (j, i) in P } ascending
+ * (first element i), m_i = |P_i|; A[P_i, P_i] y = e_1 (dense SPD), L[P_i, i] = y / sqrt(y_1).  Then (L^T A)[i, j] = 0 for j in
+ * P_i \ {i}, (L^T A L)[i, i] = 1, and M = L L^T ~ A^-1 is SPD for every SPD A.  Not in the reference: it is the closed-form
+ * optimum of || I - L^T U_A ||_F (A = U_A U_A^T) on the kind of pattern the reference's network is trained on.
+ * dpcg_set_precond_fsai: P = the pattern of A^level as a structural power (level 1, 2 or 3; level 1: tril(A), as IC(0)).
+ * dpcg_set_precond_fsai_pattern: tril(P) by rows from the caller (int32 CSR, values none; lower triangular, columns ascending,
+ * the diagonal last in every row; memspace DPCG_HOST or DPCG_DEVICE) -- the optimum on the exact pattern a network emits.
+ * The factor is attached exactly as dpcg_set_precond_llt(DPCG_PRECOND_LLT_MULTIPLY) attaches one (kind 3: dpcg_get_factor,
+ * dpcg_precond_apply, dpcg_spectrum, the one-launch forms and the batch path serve it unchanged); there is no apply mode.
+ * Everything happens in the CALLER's numbering (a reordered handle gives the same bits).  Operation order of a local solve
+ * (tests/fsai_restatement.py; the device equals it bit for bit): only b_pq = A[P_i[p], P_i[q]], q <= p, is read (absent: 0);
+ * Cholesky column by column, s = b_pj - sum_{k<j} c_pk c_jk with k ascending, c_jj = sqrt(s_j), c_pj = s_p / c_jj; C w = e_1
+ * and C^T y = w column-oriented (s_p -= c_pj w_j for j ascending; s_p -= c_jp y_j for j descending; w_j, y_j = s_j / c_jj);
+ * l_p = y_p / sqrt(y_0).  No tree-shaped sums.
+ * Limits and errors: m_i <= 64 (beyond: DPCG_ERR_INVALID, the text names the column and its m_i); a structurally missing
+ * diagonal and a level outside 1 .. 3 are DPCG_ERR_INVALID; a non-positive or non-finite pivot of a local Cholesky is
+ * DPCG_ERR_PIVOT (the text names the column); the gather map holds sum m_i (m_i + 1) / 2 int32 entries, at most 2^31
+ * (DPCG_ERR_INVALID beyond).  On any failure the previous preconditioner stays.
+ * Reuse: the pattern, the gather map and the binning by m_i stay on the handle, keyed on (level | the explicit pattern), across
+ * dpcg_update_values; attaching the same key again computes only values.  They are freed when another kind of preconditioner is
+ * attached (dpcg_set_precond_none / jacobi / csr / llt / ic0 / ict / icholt / ilut / amg / callback), by dpcg_reorder and by
+ * dpcg_destroy; a failed attach of another FSAI key leaves them as they were. */
+int dpcg_set_precond_fsai(dpcg_handle_t h, int level, dpcg_stream_t stream);
+int dpcg_set_precond_fsai_pattern(dpcg_handle_t h, int64_t nnz, const int32_t *rowptr, const int32_t *col, int memspace,
+                                  dpcg_stream_t stream);
+/* out = {level (0: explicit pattern), max m_i, columns with m_i <= 4, 5 .. 8, 9 .. 16, 17 .. 32, 33 .. 64, 1 when the last attach
+ * reused the symbolic phase}; nnz(L) is dpcg_get_info's.  DPCG_ERR_STATE when the attached preconditioner is not an FSAI factor. */
+int dpcg_get_fsai_info(dpcg_handle_t h, int32_t out[8]);
 /* The reference's operator protocol asks of M nothing but `M @ rk` (cg.py:61,81).  An M that is not a matrix this library
  * can hold (a Python object with __matmul__, a multigrid cycle, ...) is applied through a function the caller supplies:
  * fn(user, r, z, n, stream) must ENQUEUE z = M r on `stream` (device pointers, caller's numbering; it is called from the
