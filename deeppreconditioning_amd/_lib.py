@@ -28,6 +28,7 @@ INIT_CHECK_R, SPMV_F32, NO_GRAPH, NO_SMALL, VAL32_IF_LOSSLESS, NO_FUSE, NO_TEAM,
 REORDER_NONE, REORDER_AUTO, REORDER_ALWAYS, REORDER_REGIONS = 0, 1, 2, 3
 ORDER_CALLER, ORDER_MULTICOLOR = 0, 1
 AMG_JACOBI, AMG_GAUSS_SEIDEL, AMG_CHEBYSHEV = 0, 1, 2
+AMG_FP64, AMG_FP32 = 0, 1
 
 # name -> (restype, argtypes); every symbol include/dpcg.h declares
 _p = C.c_void_p
@@ -52,6 +53,9 @@ SIGNATURES = {
     "dpcg_get_amg_level": (_int, [_p, _int, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "dpcg_set_precond_amg_smoothed": (_int, [_p, _dbl, _int, _int, _int, C.c_uint64, _int, _int, _dbl, _p]),
     "dpcg_get_amg_smoothers": (_int, [_p, _int, _p, _p, _p, _p]),
+    "dpcg_set_precond_amg_precision": (_int, [_p, _dbl, _int, _int, _int, C.c_uint64, _int, _int, _dbl, _int, _p]),
+    "dpcg_get_amg_precision": (_int, [_p, C.POINTER(_int)]),
+    "dpcg_get_amg_launches": (_int, [_p, C.POINTER(_int), C.POINTER(_int)]),
     "dpcg_get_amg_colors": (_int, [_p, _int, _i64, _p, _p]),
     "dpcg_set_precond_jacobi": (_int, [_p, _p, _int, _p]),
     "dpcg_set_precond_csr": (_int, [_p, _i64, _p, _p, _p, _int, _p]),

@@ -47,6 +47,8 @@ COMPARABILITY = {
                                         "that needs more than 63 colours keeps damped Jacobi",
     "algebraic_multigrid_chebyshev": "not in the reference: the algebraic_multigrid hierarchy smoothed by a degree-2 Chebyshev "
                                      "polynomial in D^-1 A on [rho / 30, rho] (pyamg's default smoother is Gauss-Seidel)",
+    "algebraic_multigrid_fp32": "not in the reference: the algebraic_multigrid hierarchy (built in fp64, the same bits) with the cycle's "
+                                "operands and work vectors stored in fp32 and all arithmetic in fp64; PCG itself stays fp64",
     "incomplete_lu": "algorithm per Saad's dual-threshold ILUT(p, tau) as restated in tests/ilut_restatement.py (M = L U multiplied, "
                      "test.py:90-93); ilupp binary absent: values unpinned; ilupp.ilut's own default arguments cannot be read here, "
                      "icholt's (add_fill_in=1, threshold=0.1) are assumed",
@@ -134,6 +136,8 @@ class BenchmarkSuite:
             return SmoothedAggregation(smoother="gauss_seidel")
         if name == "algebraic_multigrid_chebyshev":        # the same hierarchy, Chebyshev smoothing (opt-in)
             return SmoothedAggregation(smoother="chebyshev")
+        if name == "algebraic_multigrid_fp32":             # the same hierarchy, the cycle stored in fp32 (opt-in)
+            return SmoothedAggregation(precision="fp32")
         if name == "learned":                       # test.py:100-105
             with torch.no_grad():
                 out = self.model(system_tril)

@@ -38,9 +38,17 @@
 //                 d'_j = c1 d_j + c2 (dinv_j r_j), on the fly and writes x', d' and r' = b - A x' (first step of an application:
 //                 d'_j = c2 (dinv_j r_j)); pre-smoothing starts from x = 0, r = b; post-smoothing forms r with k_amg_row<RES> after the
 //                 correction; the last step of a level needs no r' (k_amg_cheb<LAST>, on level 0 with the <r, z> partials).
+//
+// fp32 cycle (dpcg_set_precond_amg_precision with DPCG_AMG_FP32; Jacobi and Chebyshev): the hierarchy is the fp64 one; after the setup
+// the values of A_l, P_l, P_l^T and dinv_l of every smoothed level are stored a second time, rounded to fp32 (k_amg_to_f32), and
+// every work vector of the cycle is fp32.  The kernels are the same templates with other storage types: operands are converted
+// on load, every product and sum is fp64, and whatever the fp64 cycle stores to a work vector is rounded to fp32 where it is
+// computed -- also when a row gathers it on the fly (PRE's and SWEEP's y_j, Chebyshev's d'_j and x_j + d'_j).  Level 0 reads
+// PCG's r and writes z in fp64 (not rounded); the dense coarse inverse stays fp64 (fp32 in, fp32 out).  Same launches as fp64.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "dpcg_device.h"
@@ -69,6 +77,9 @@ struct AmgLevel {
     double cheb_lo = 0.0, cheb_hi = 0.0;
     std::vector<double> cheb_c1, cheb_c2;   // Chebyshev: the coefficients of each step (c1[0] unused)
     double *da = nullptr, *db = nullptr;    // Chebyshev: the direction d, double-buffered
+    // fp32 cycle: the values of A, P, P^T and dinv rounded to fp32 (patterns shared with the fp64 arrays) and the work vectors
+    float *a32 = nullptr, *p32 = nullptr, *pt32 = nullptr, *dinv32 = nullptr;
+    float *b32 = nullptr, *xa32 = nullptr, *xb32 = nullptr, *ra32 = nullptr, *rb32 = nullptr, *da32 = nullptr, *db32 = nullptr;
 };
 
 struct AmgState {
@@ -77,6 +88,7 @@ struct AmgState {
     uint64_t seed = 0;
     int smoother = DPCG_AMG_JACOBI, degree = 2;
     double eig_ratio = 30.0;
+    int precision = DPCG_AMG_FP64;    // what the cycle stores (the hierarchy is fp64 either way)
     std::vector<AmgLevel> lv;         // lv.back(): the coarsest level (dense solve)
     double *cinv = nullptr;           // dense inverse of the coarsest matrix, row-major
     int64_t nco = 0;
@@ -394,12 +406,19 @@ enum AmgOp { OP_PRE = 0, OP_SWEEP = 1, OP_POST = 2, OP_ACC = 3, OP_PLAIN = 4, OP
 //   ACC    y_j = u_j;                      x'_i = x_i + sum a_ij y_j          (a = P)
 //   PLAIN  y_j = u_j;                      x'_i = sum a_ij y_j                (a = P^T)
 //   RES    y_j = x_j;                      r_i = b_i - sum a_ij y_j
-template <int OP, int TPR>
+// Storage types (all double: the fp64 cycle): AT the matrix values and dinv, BT b, WT the work vectors gathered (xin, rin, u) and
+// r', OT x' (POST on level 0: z, double; otherwise WT).  Arithmetic is double; rnd<T> rounds what is stored as T where it is computed.
+template <typename T>
+__device__ __forceinline__ double rnd(double v) {
+    return (double)(T)v;
+}
+
+template <int OP, int TPR, typename AT = double, typename BT = double, typename WT = double, typename OT = double>
 __global__ __launch_bounds__(kBlock) void k_amg_row(int64_t n, const int32_t *__restrict__ rp, const int32_t *__restrict__ ci,
-                                                    const double *__restrict__ av, const double *__restrict__ dinv, double omega,
-                                                    const double *__restrict__ b, const double *__restrict__ xin,
-                                                    const double *__restrict__ rin, const double *__restrict__ u,
-                                                    double *__restrict__ xout, double *__restrict__ rout, double *__restrict__ part,
+                                                    const AT *__restrict__ av, const AT *__restrict__ dinv, double omega,
+                                                    const BT *__restrict__ b, const WT *__restrict__ xin,
+                                                    const WT *__restrict__ rin, const WT *__restrict__ u,
+                                                    OT *__restrict__ xout, WT *__restrict__ rout, double *__restrict__ part,
                                                     const int *__restrict__ done) {
     if (done && *done) return;        // (in the PCG loop: the updates enqueued beyond convergence cost a launch each, not a cycle)
     constexpr int RPB = kBlock / TPR;
@@ -412,8 +431,8 @@ __global__ __launch_bounds__(kBlock) void k_amg_row(int64_t n, const int32_t *__
             for (int k = rp[i] + sub; k < rp[i + 1]; k += TPR) {
                 const int j = ci[k];
                 double y;
-                if (OP == OP_PRE) y = omega * dinv[j] * b[j];
-                else if (OP == OP_SWEEP) y = xin[j] + omega * dinv[j] * rin[j];
+                if (OP == OP_PRE) y = rnd<WT>(omega * dinv[j] * b[j]);
+                else if (OP == OP_SWEEP) y = rnd<WT>(xin[j] + omega * dinv[j] * rin[j]);
                 else if (OP == OP_POST || OP == OP_RES) y = xin[j];
                 else y = u[j];
                 s += av[k] * y;
@@ -423,21 +442,21 @@ __global__ __launch_bounds__(kBlock) void k_amg_row(int64_t n, const int32_t *__
         for (int w = 1; w < TPR; w <<= 1) s += __shfl_xor(s, w, TPR);
         if (i < n && sub == 0) {
             if (OP == OP_PRE) {
-                xout[i] = omega * dinv[i] * b[i];
-                rout[i] = b[i] - s;
+                xout[i] = (OT)(omega * dinv[i] * b[i]);
+                rout[i] = (WT)(b[i] - s);
             } else if (OP == OP_SWEEP) {
-                xout[i] = xin[i] + omega * dinv[i] * rin[i];
-                rout[i] = b[i] - s;
+                xout[i] = (OT)(xin[i] + omega * dinv[i] * rin[i]);
+                rout[i] = (WT)(b[i] - s);
             } else if (OP == OP_POST) {
-                const double x = xin[i] + omega * dinv[i] * (b[i] - s);
-                xout[i] = x;
+                const double x = rnd<OT>(xin[i] + omega * dinv[i] * (b[i] - s));
+                xout[i] = (OT)x;
                 if (part) acc += b[i] * x;
             } else if (OP == OP_ACC) {
-                xout[i] = xin[i] + s;
+                xout[i] = (OT)(xin[i] + s);
             } else if (OP == OP_RES) {
-                rout[i] = b[i] - s;
+                rout[i] = (WT)(b[i] - s);
             } else {
-                xout[i] = s;
+                xout[i] = (OT)s;
             }
         }
     }
@@ -520,19 +539,26 @@ __global__ __launch_bounds__(kGsBlockThreads) void k_amg_gs_block(int64_t n, int
 // One Chebyshev step on (x, r = b - A x): d' = c1 d + c2 (dinv r) (din null: the first step, d' = c2 (dinv r)), x' = x + d'
 // (xin null: x = 0).  STEP gathers the new x_j on the fly and writes x', d' and r' = b - A x'; LAST writes x' only (part: <b, x'>
 // per workgroup, rows owned as in k_amg_row so the partials line up with amg_rz_partials).
+// Storage types as k_amg_row's: STEP stores d', x' and r' as WT, so d' is rounded before it enters x' = x + d' and x' before it enters
+// the row sum; LAST stores only x' (as OT), so its d' is not rounded.  RT: the storage of r (pre-smoothing's first step reads r = b).
 enum ChebMode { CHEB_STEP = 0, CHEB_LAST = 1 };
-template <int TPR, int MODE>
+template <int TPR, int MODE, typename AT = double, typename BT = double, typename WT = double, typename OT = double,
+          typename RT = WT>
 __global__ __launch_bounds__(kBlock) void k_amg_cheb(int64_t n, const int32_t *__restrict__ rp, const int32_t *__restrict__ ci,
-                                                     const double *__restrict__ av, const double *__restrict__ dinv,
-                                                     const double *__restrict__ b, const double *__restrict__ xin,
-                                                     const double *__restrict__ din, const double *__restrict__ rin, double c1, double c2,
-                                                     double *__restrict__ xout, double *__restrict__ dout, double *__restrict__ rout,
+                                                     const AT *__restrict__ av, const AT *__restrict__ dinv,
+                                                     const BT *__restrict__ b, const WT *__restrict__ xin,
+                                                     const WT *__restrict__ din, const RT *__restrict__ rin, double c1, double c2,
+                                                     OT *__restrict__ xout, WT *__restrict__ dout, WT *__restrict__ rout,
                                                      double *__restrict__ part, const int *__restrict__ done) {
     if (done && *done) return;
     constexpr int RPB = kBlock / TPR;
     const int sub = threadIdx.x % TPR;
-    auto dnew = [&](int64_t j) { return din ? c1 * din[j] + c2 * (dinv[j] * rin[j]) : c2 * (dinv[j] * rin[j]); };
-    auto xnew = [&](int64_t j, double d) { return (xin ? xin[j] : 0.0) + d; };
+    auto dnew = [&](int64_t j) {
+        // (dinv r in double also when both are stored as float)
+        const double d = din ? c1 * din[j] + c2 * ((double)dinv[j] * (double)rin[j]) : c2 * ((double)dinv[j] * (double)rin[j]);
+        return MODE == CHEB_STEP ? rnd<WT>(d) : d;
+    };
+    auto xnew = [&](int64_t j, double d) { return rnd<OT>((xin ? xin[j] : 0.0) + d); };
     double acc = 0.0;
     for (int64_t row0 = (int64_t)blockIdx.x * RPB; row0 < n; row0 += (int64_t)gridDim.x * RPB) {
         const int64_t i = row0 + threadIdx.x / TPR;
@@ -549,10 +575,10 @@ __global__ __launch_bounds__(kBlock) void k_amg_cheb(int64_t n, const int32_t *_
         if (i < n && sub == 0) {
             const double d = dnew(i);
             const double x = xnew(i, d);
-            xout[i] = x;
+            xout[i] = (OT)x;
             if (MODE == CHEB_STEP) {
-                dout[i] = d;
-                rout[i] = b[i] - s;
+                dout[i] = (WT)d;
+                rout[i] = (WT)(b[i] - s);
             } else if (part) {
                 acc += b[i] * x;
             }
@@ -571,17 +597,25 @@ __global__ __launch_bounds__(kBlock) void k_amg_cheb(int64_t n, const int32_t *_
     }
 }
 
-// x = C b, C dense row-major (nc x nc): one wave per row, fixed-order sums
-__global__ __launch_bounds__(kBlock) void k_amg_gemv(int64_t nc, const double *__restrict__ C, const double *__restrict__ b,
-                                                     double *__restrict__ x, const int *__restrict__ done) {
+// x = C b, C dense row-major (nc x nc): one wave per row, fixed-order sums (VT: the storage of b and x; C and the sums are double)
+template <typename VT = double>
+__global__ __launch_bounds__(kBlock) void k_amg_gemv(int64_t nc, const double *__restrict__ C, const VT *__restrict__ b,
+                                                     VT *__restrict__ x, const int *__restrict__ done) {
     if (done && *done) return;
     const int lane = threadIdx.x & 63;
     for (int64_t i = ((int64_t)blockIdx.x * kBlock + threadIdx.x) >> 6; i < nc; i += ((int64_t)gridDim.x * kBlock) >> 6) {
         double s = 0.0;
         for (int64_t j = lane; j < nc; j += 64) s += C[i * nc + j] * b[j];
         s = wave_sum(s);
-        if (lane == 63) x[i] = s;
+        if (lane == 63) x[i] = (VT)s;
     }
+}
+
+// dst[k] = (float) src[order ? order[k] : k] (round to nearest even): the fp32 copies of the cycle's operands
+__global__ __launch_bounds__(kBlock) void k_amg_to_f32(int64_t n, const double *__restrict__ src, const int32_t *__restrict__ order,
+                                                       float *__restrict__ dst) {
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x; k < n; k += stride) dst[k] = (float)src[order ? order[k] : k];
 }
 
 int tpr_for(const CsrDev &A) {
@@ -591,16 +625,17 @@ int tpr_for(const CsrDev &A) {
     return tpr;
 }
 
-template <int OP>
-void launch_row(const CsrDev &A, int tpr, const double *dinv, double omega, const double *b, const double *xin, const double *rin,
-                const double *u, double *xout, double *rout, double *part, int *grid_out, hipStream_t s, const int *done) {
+// (av: the values the rows multiply -- A.val, or its fp32 copy)
+template <int OP, typename AT, typename BT, typename WT, typename OT>
+void launch_row(const CsrDev &A, const AT *av, int tpr, const AT *dinv, double omega, const BT *b, const WT *xin, const WT *rin,
+                const WT *u, OT *xout, WT *rout, double *part, int *grid_out, hipStream_t s, const int *done) {
     const int rpb = kBlock / tpr;
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((A.n + rpb - 1) / rpb, kApplyMaxGrid));
     if (grid_out) *grid_out = grid;
 #define AMG_ROW(T)                                                                                                           \
     case T:                                                                                                                  \
-        hipLaunchKernelGGL((k_amg_row<OP, T>), dim3(grid), dim3(kBlock), 0, s, A.n, A.rowptr, A.col, A.val, dinv, omega, b, \
-                           xin, rin, u, xout, rout, part, done);                                                             \
+        hipLaunchKernelGGL((k_amg_row<OP, T, AT, BT, WT, OT>), dim3(grid), dim3(kBlock), 0, s, A.n, A.rowptr, A.col, av, dinv, \
+                           omega, b, xin, rin, u, xout, rout, part, done);                                                   \
         break;
     switch (tpr) { AMG_ROW(2) AMG_ROW(4) AMG_ROW(8) AMG_ROW(16) AMG_ROW(32) default: AMG_ROW(64) }
 #undef AMG_ROW
@@ -651,16 +686,16 @@ int gs_sweeps(const AmgLevel &L, int sweeps, bool init, const double *b, double 
     return k;
 }
 
-template <int MODE>
-void launch_cheb(const AmgLevel &L, double c1, double c2, const double *b, const double *xin, const double *din, const double *rin,
-                 double *xout, double *dout, double *rout, double *part, int *grid_out, hipStream_t s, const int *done) {
+template <int MODE, typename AT, typename BT, typename WT, typename OT, typename RT>
+void launch_cheb(const AmgLevel &L, const AT *av, const AT *dinv, double c1, double c2, const BT *b, const WT *xin, const WT *din,
+                 const RT *rin, OT *xout, WT *dout, WT *rout, double *part, int *grid_out, hipStream_t s, const int *done) {
     const int rpb = kBlock / L.tpr_a;
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((L.A.n + rpb - 1) / rpb, kApplyMaxGrid));
     if (grid_out) *grid_out = grid;
 #define AMG_CHEB(T)                                                                                                            \
     case T:                                                                                                                    \
-        hipLaunchKernelGGL((k_amg_cheb<T, MODE>), dim3(grid), dim3(kBlock), 0, s, L.A.n, L.A.rowptr, L.A.col, L.A.val, L.dinv, \
-                           b, xin, din, rin, c1, c2, xout, dout, rout, part, done);                                            \
+        hipLaunchKernelGGL((k_amg_cheb<T, MODE, AT, BT, WT, OT, RT>), dim3(grid), dim3(kBlock), 0, s, L.A.n, L.A.rowptr, L.A.col,  \
+                           av, dinv, b, xin, din, rin, c1, c2, xout, dout, rout, part, done);                                  \
         break;
     switch (L.tpr_a) { AMG_CHEB(2) AMG_CHEB(4) AMG_CHEB(8) AMG_CHEB(16) AMG_CHEB(32) default: AMG_CHEB(64) }
 #undef AMG_CHEB
@@ -687,6 +722,8 @@ void free_level(AmgLevel &L, bool keep_a) {
     dev_free(L.b); dev_free(L.xa); dev_free(L.xb); dev_free(L.ra); dev_free(L.rb);
     dev_free(L.gs_rows); dev_free(L.gs_off_dev);
     dev_free(L.da); dev_free(L.db);
+    dev_free(L.a32); dev_free(L.p32); dev_free(L.pt32); dev_free(L.dinv32);
+    dev_free(L.b32); dev_free(L.xa32); dev_free(L.xb32); dev_free(L.ra32); dev_free(L.rb32); dev_free(L.da32); dev_free(L.db32);
     L = AmgLevel();
 }
 
@@ -892,18 +929,41 @@ int coarse_inverse(const CsrDev &A, int level, double **cinv, hipStream_t s) {
     return DPCG_OK;
 }
 
-int alloc_work(AmgLevel &L, bool coarse, int sweeps) {
+// the work vectors of one level in the cycle's precision (the other set stays null)
+template <typename W>
+int alloc_work_t(AmgLevel &L, bool coarse, int sweeps, W *&b, W *&xa, W *&xb, W *&ra, W *&rb, W *&da, W *&db) {
     const int64_t n = L.A.n;
-    DPCG_TRY(dev_alloc(&L.b, n));
-    DPCG_TRY(dev_alloc(&L.xa, n));
+    DPCG_TRY(dev_alloc(&b, n));
+    DPCG_TRY(dev_alloc(&xa, n));
     if (coarse) return DPCG_OK;
-    DPCG_TRY(dev_alloc(&L.xb, n));
-    DPCG_TRY(dev_alloc(&L.ra, n));
-    if (sweeps > 1 || L.smoother == DPCG_AMG_CHEBYSHEV) DPCG_TRY(dev_alloc(&L.rb, n));
+    DPCG_TRY(dev_alloc(&xb, n));
+    DPCG_TRY(dev_alloc(&ra, n));
+    if (sweeps > 1 || L.smoother == DPCG_AMG_CHEBYSHEV) DPCG_TRY(dev_alloc(&rb, n));
     if (L.smoother == DPCG_AMG_CHEBYSHEV) {
-        DPCG_TRY(dev_alloc(&L.da, n));
-        DPCG_TRY(dev_alloc(&L.db, n));
+        DPCG_TRY(dev_alloc(&da, n));
+        DPCG_TRY(dev_alloc(&db, n));
     }
+    return DPCG_OK;
+}
+
+int alloc_work(AmgLevel &L, bool coarse, int sweeps, int precision) {
+    if (precision == DPCG_AMG_FP32) return alloc_work_t(L, coarse, sweeps, L.b32, L.xa32, L.xb32, L.ra32, L.rb32, L.da32, L.db32);
+    return alloc_work_t(L, coarse, sweeps, L.b, L.xa, L.xb, L.ra, L.rb, L.da, L.db);
+}
+
+// fp32 cycle: the values of A_l, P_l, P_l^T (the rounded numbers of P_l, through pt_order) and dinv_l once more, rounded to fp32
+int make_f32_copies(AmgLevel &L, hipStream_t s) {
+    const int64_t n = L.A.n, an = std::max<int64_t>(1, L.A.nnz), pn = std::max<int64_t>(1, L.P.nnz);
+    DPCG_TRY(dev_alloc(&L.a32, an));
+    DPCG_TRY(dev_alloc(&L.p32, pn));
+    DPCG_TRY(dev_alloc(&L.pt32, pn));
+    DPCG_TRY(dev_alloc(&L.dinv32, n));
+    hipLaunchKernelGGL(k_amg_to_f32, dim3(grid_of(L.A.nnz)), dim3(kBlock), 0, s, L.A.nnz, L.A.val, nullptr, L.a32);
+    hipLaunchKernelGGL(k_amg_to_f32, dim3(grid_of(L.P.nnz)), dim3(kBlock), 0, s, L.P.nnz, L.P.val, nullptr, L.p32);
+    hipLaunchKernelGGL(k_amg_to_f32, dim3(grid_of(L.P.nnz)), dim3(kBlock), 0, s, L.P.nnz, L.P.val, L.pt_order, L.pt32);
+    hipLaunchKernelGGL(k_amg_to_f32, dim3(grid_of(n)), dim3(kBlock), 0, s, n, L.dinv, nullptr, L.dinv32);
+    DPCG_CHECK_LAUNCH();
+    DPCG_HIP(hipStreamSynchronize(s));
     return DPCG_OK;
 }
 
@@ -1087,7 +1147,7 @@ int build(dpcg_system *h, AmgState &S, AmgState *old, hipStream_t s) {
             }
             DPCG_TRY(coarse_inverse(L.A, l, &S.cinv, s));
             S.nco = n;
-            DPCG_TRY(alloc_work(L, true, S.sweeps));
+            DPCG_TRY(alloc_work(L, true, S.sweeps, S.precision));
             pt.mark("amg: coarse inverse");
             break;
         }
@@ -1150,8 +1210,15 @@ int build(dpcg_system *h, AmgState &S, AmgState *old, hipStream_t s) {
         } else if (S.smoother == DPCG_AMG_CHEBYSHEV) {
             chebyshev_coefficients(L, S.degree, S.eig_ratio);
         }
-        DPCG_TRY(alloc_work(L, false, S.sweeps));
-        if (l == 0) dev_free(L.b);                  // (level 0's right-hand side is the caller's r)
+        DPCG_TRY(alloc_work(L, false, S.sweeps, S.precision));
+        if (l == 0) {                               // (level 0's right-hand side is the caller's r)
+            dev_free(L.b);
+            dev_free(L.b32);
+        }
+        if (S.precision == DPCG_AMG_FP32) {
+            DPCG_TRY(make_f32_copies(L, s));
+            pt.mark("amg: fp32 copies");
+        }
     }
     return DPCG_OK;
 }
@@ -1197,108 +1264,177 @@ int64_t amg_nnz(const AmgState *S) {
     return t;
 }
 
+namespace dpcg {
+namespace {
+
+// what the cycle reads and writes on a level in storage type W (double: the hierarchy's own arrays; float: the fp32 copies)
+template <typename W>
+struct LevelView;
+template <>
+struct LevelView<double> {
+    const double *a, *p, *pt, *dinv;
+    double *b, *xa, *xb, *ra, *rb, *da, *db;
+    explicit LevelView(const AmgLevel &L)
+        : a(L.A.val), p(L.P.val), pt(L.Pt.val), dinv(L.dinv), b(L.b), xa(L.xa), xb(L.xb), ra(L.ra), rb(L.rb), da(L.da), db(L.db) {}
+};
+template <>
+struct LevelView<float> {
+    const float *a, *p, *pt, *dinv;
+    float *b, *xa, *xb, *ra, *rb, *da, *db;
+    explicit LevelView(const AmgLevel &L)
+        : a(L.a32), p(L.p32), pt(L.pt32), dinv(L.dinv32), b(L.b32), xa(L.xa32), xb(L.xb32), ra(L.ra32), rb(L.rb32), da(L.da32),
+          db(L.db32) {}
+};
+
+// Down on one level: pre-smoothing, residual, restriction into bnext.  B: the level's right-hand side (level 0: PCG's r, double).
+// x / alt: where the level's iterate is and the spare buffer, for the way up.
+template <typename W, typename BT>
+void level_down(const AmgLevel &L, int nu, const BT *B, W *bnext, W *&x, W *&alt, hipStream_t s, const int *done) {
+    const LevelView<W> V(L);
+    const W *const nw = nullptr;
+    W *const nwo = nullptr;
+    if (L.smoother == DPCG_AMG_GAUSS_SEIDEL) {
+        if constexpr (std::is_same<W, double>::value) {       // (the fp32 cycle is refused for Gauss-Seidel)
+            gs_sweeps(L, nu, true, B, V.xa, s, done);
+            launch_row<OP_RES>(L.A, V.a, L.tpr_a, nw, 0.0, B, (const W *)V.xa, nw, nw, nwo, V.ra, nullptr, nullptr, s, done);
+            launch_row<OP_PLAIN>(L.Pt, V.pt, L.tpr_pt, nw, 0.0, nw, nw, nw, (const W *)V.ra, bnext, nwo, nullptr, nullptr, s, done);
+            x = V.xa;
+            alt = V.xb;
+        }
+        return;
+    }
+    if (L.smoother == DPCG_AMG_CHEBYSHEV) {       // from x = 0, r = b
+        const W *xin = nullptr, *din = nullptr, *rin = nullptr;
+        W *xo = V.xa, *xo2 = V.xb, *dn = V.da, *dn2 = V.db, *rn = V.ra, *rn2 = V.rb;
+        const int deg = (int)L.cheb_c1.size();
+        for (int t = 0; t < nu * deg; ++t) {
+            const int k = t % deg;
+            const W *dk = k == 0 ? nullptr : din;
+            if (t == 0)                           // (r = b, in b's own storage)
+                launch_cheb<CHEB_STEP>(L, V.a, V.dinv, L.cheb_c1[k], L.cheb_c2[k], B, xin, dk, B, xo, dn, rn, nullptr, nullptr, s, done);
+            else
+                launch_cheb<CHEB_STEP>(L, V.a, V.dinv, L.cheb_c1[k], L.cheb_c2[k], B, xin, dk, rin, xo, dn, rn, nullptr, nullptr, s, done);
+            xin = xo; din = dn; rin = rn;
+            std::swap(xo, xo2); std::swap(dn, dn2); std::swap(rn, rn2);
+        }
+        launch_row<OP_PLAIN>(L.Pt, V.pt, L.tpr_pt, nw, 0.0, nw, nw, nw, rin, bnext, nwo, nullptr, nullptr, s, done);
+        x = const_cast<W *>(xin);
+        alt = xo;
+        return;
+    }
+    W *xc = V.xa, *xo = V.xb, *rc = V.ra, *ro = V.rb;
+    launch_row<OP_PRE>(L.A, V.a, L.tpr_a, V.dinv, L.omega, B, nw, nw, nw, xc, rc, nullptr, nullptr, s, done);
+    for (int k = 1; k < nu; ++k) {
+        launch_row<OP_SWEEP>(L.A, V.a, L.tpr_a, V.dinv, L.omega, B, (const W *)xc, (const W *)rc, nw, xo, ro, nullptr, nullptr, s, done);
+        std::swap(xc, xo);
+        std::swap(rc, ro);
+    }
+    launch_row<OP_PLAIN>(L.Pt, V.pt, L.tpr_pt, nw, 0.0, nw, nw, nw, (const W *)rc, bnext, nwo, nullptr, nullptr, s, done);
+    x = xc;
+    alt = xo;
+}
+
+// Up on one level: prolongation with correction, post-smoothing.  TOP (level 0): the right-hand side is PCG's r (double) and the last
+// smoothing pass writes z to zout, in double, with the <r, z> partials; otherwise it writes a work vector.  Returns where the
+// level's result is (null: in zout).
+template <typename W, bool TOP>
+const W *level_up(const AmgLevel &L, int nu, const std::conditional_t<TOP, double, W> *B, const W *xcoarse, W *x, W *alt, double *zout,
+                  double *part_rz, int *n_part_rz, hipStream_t s, const int *done) {
+    const LevelView<W> V(L);
+    const W *const nw = nullptr;
+    W *const nwo = nullptr;
+    if (L.smoother == DPCG_AMG_GAUSS_SEIDEL) {    // (level 0 sweeps in z itself)
+        if constexpr (std::is_same<W, double>::value) {
+            double *out = TOP ? zout : alt;
+            launch_row<OP_ACC>(L.P, V.p, L.tpr_p, nw, 0.0, nw, (const W *)x, nw, xcoarse, out, nwo, nullptr, nullptr, s, done);
+            gs_sweeps(L, nu, false, B, out, s, done);
+            return out;
+        }
+        return nullptr;
+    }
+    if (L.smoother == DPCG_AMG_CHEBYSHEV) {
+        W *xc = alt, *xo = x, *dn = V.da, *dn2 = V.db, *rn = V.rb, *rn2 = V.ra;
+        launch_row<OP_ACC>(L.P, V.p, L.tpr_p, nw, 0.0, nw, (const W *)x, nw, xcoarse, xc, nwo, nullptr, nullptr, s, done);
+        launch_row<OP_RES>(L.A, V.a, L.tpr_a, nw, 0.0, B, (const W *)xc, nw, nw, nwo, V.ra, nullptr, nullptr, s, done);
+        const W *din = nullptr, *rin = V.ra;
+        const int deg = (int)L.cheb_c1.size();
+        for (int t = 0; t < nu * deg; ++t) {
+            const int k = t % deg;
+            const W *dk = k == 0 ? nullptr : din;
+            if (t == nu * deg - 1) {
+                int grid = 0;
+                if constexpr (TOP) {
+                    launch_cheb<CHEB_LAST>(L, V.a, V.dinv, L.cheb_c1[k], L.cheb_c2[k], B, (const W *)xc, dk, rin, zout, nwo, nwo, part_rz,
+                                           &grid, s, done);
+                    if (part_rz && n_part_rz) *n_part_rz = grid;
+                    return nullptr;
+                } else {
+                    launch_cheb<CHEB_LAST>(L, V.a, V.dinv, L.cheb_c1[k], L.cheb_c2[k], B, (const W *)xc, dk, rin, xo, nwo, nwo, nullptr,
+                                           &grid, s, done);
+                    return xo;
+                }
+            }
+            launch_cheb<CHEB_STEP>(L, V.a, V.dinv, L.cheb_c1[k], L.cheb_c2[k], B, (const W *)xc, dk, rin, xo, dn, rn, nullptr, nullptr, s,
+                                   done);
+            din = dn; rin = rn;
+            std::swap(xc, xo); std::swap(dn, dn2); std::swap(rn, rn2);
+        }
+        return xc;
+    }
+    W *xc = x, *xo = alt;
+    launch_row<OP_ACC>(L.P, V.p, L.tpr_p, nw, 0.0, nw, (const W *)xc, nw, xcoarse, xo, nwo, nullptr, nullptr, s, done);
+    std::swap(xc, xo);
+    for (int k = 0; k < nu; ++k) {
+        int grid = 0;
+        if constexpr (TOP) {
+            if (k == nu - 1) {
+                launch_row<OP_POST>(L.A, V.a, L.tpr_a, V.dinv, L.omega, B, (const W *)xc, nw, nw, zout, nwo, part_rz, &grid, s, done);
+                if (part_rz && n_part_rz) *n_part_rz = grid;
+                return nullptr;
+            }
+        }
+        launch_row<OP_POST>(L.A, V.a, L.tpr_a, V.dinv, L.omega, B, (const W *)xc, nw, nw, xo, nwo, nullptr, &grid, s, done);
+        std::swap(xc, xo);
+    }
+    return xc;
+}
+
+// one V(nu, nu) cycle with work vectors and operand copies of storage type W
+template <typename W>
+int apply_cycle(AmgState &S, const double *r, double *z, hipStream_t s, double *part_rz, int *n_part_rz, const int *done) {
+    const int Lc = (int)S.lv.size() - 1;
+    const int nu = S.sweeps;
+    std::vector<W *> x(Lc), alt(Lc);
+    for (int l = 0; l < Lc; ++l) {                    // down: pre-smoothing, residual, restriction
+        W *bnext = LevelView<W>(S.lv[l + 1]).b;
+        if (l == 0) level_down<W, double>(S.lv[l], nu, r, bnext, x[l], alt[l], s, done);
+        else level_down<W, W>(S.lv[l], nu, LevelView<W>(S.lv[l]).b, bnext, x[l], alt[l], s, done);
+    }
+    const LevelView<W> C(S.lv[Lc]);
+    hipLaunchKernelGGL(k_amg_gemv<W>, dim3(grid_of(S.nco * 64)), dim3(kBlock), 0, s, S.nco, S.cinv, (const W *)C.b, C.xa, done);
+    const W *xcoarse = C.xa;
+    for (int l = Lc - 1; l >= 0; --l) {               // up: prolongation with correction, post-smoothing
+        if (l == 0) xcoarse = level_up<W, true>(S.lv[l], nu, r, xcoarse, x[l], alt[l], z, part_rz, n_part_rz, s, done);
+        else xcoarse = level_up<W, false>(S.lv[l], nu, LevelView<W>(S.lv[l]).b, xcoarse, x[l], alt[l], nullptr, nullptr, nullptr, s, done);
+    }
+    return DPCG_OK;
+}
+
+}  // namespace
+}  // namespace dpcg
+
 // z = M r by one V(nu, nu) cycle; r, z in the handle's numbering (distinct buffers).  part_rz: the last post-smoothing pass of
 // level 0 leaves its per-workgroup partials of <r, z> there (*n_part_rz of them).  done (may be null): the solve's `done` word --
 // every kernel returns at once once it is set.
 int amg_apply(dpcg_system *h, const double *r, double *z, hipStream_t s, double *part_rz, int *n_part_rz, const int *done) {
     AmgState &S = *h->amg;
-    const int Lc = (int)S.lv.size() - 1;
-    const int nu = S.sweeps;
     if (n_part_rz) *n_part_rz = 0;
-    if (Lc == 0) {
-        hipLaunchKernelGGL(k_amg_gemv, dim3(grid_of(S.nco * 64)), dim3(kBlock), 0, s, S.nco, S.cinv, r, z, done);
+    if (S.lv.size() == 1) {                           // (one level: the dense inverse alone, fp64 in either precision)
+        hipLaunchKernelGGL(k_amg_gemv<double>, dim3(grid_of(S.nco * 64)), dim3(kBlock), 0, s, S.nco, S.cinv, r, z, done);
         return DPCG_OK;
     }
-    std::vector<double *> x(Lc), alt(Lc);
-    for (int l = 0; l < Lc; ++l) {                    // down: pre-smoothing, residual, restriction
-        AmgLevel &L = S.lv[l];
-        const double *B = l == 0 ? r : L.b;
-        if (L.smoother == DPCG_AMG_GAUSS_SEIDEL) {
-            gs_sweeps(L, nu, true, B, L.xa, s, done);
-            launch_row<OP_RES>(L.A, L.tpr_a, nullptr, 0.0, B, L.xa, nullptr, nullptr, nullptr, L.ra, nullptr, nullptr, s, done);
-            launch_row<OP_PLAIN>(L.Pt, L.tpr_pt, nullptr, 0.0, nullptr, nullptr, nullptr, L.ra, S.lv[l + 1].b, nullptr, nullptr, nullptr, s, done);
-            x[l] = L.xa;
-            alt[l] = L.xb;
-            continue;
-        }
-        if (L.smoother == DPCG_AMG_CHEBYSHEV) {       // from x = 0, r = b
-            const double *xin = nullptr, *din = nullptr, *rin = B;
-            double *xo = L.xa, *xo2 = L.xb, *dn = L.da, *dn2 = L.db, *rn = L.ra, *rn2 = L.rb;
-            const int deg = (int)L.cheb_c1.size();
-            for (int t = 0; t < nu * deg; ++t) {
-                const int k = t % deg;
-                launch_cheb<CHEB_STEP>(L, L.cheb_c1[k], L.cheb_c2[k], B, xin, k == 0 ? nullptr : din, rin, xo, dn, rn, nullptr, nullptr, s, done);
-                xin = xo; din = dn; rin = rn;
-                std::swap(xo, xo2); std::swap(dn, dn2); std::swap(rn, rn2);
-            }
-            launch_row<OP_PLAIN>(L.Pt, L.tpr_pt, nullptr, 0.0, nullptr, nullptr, nullptr, rin, S.lv[l + 1].b, nullptr, nullptr, nullptr, s, done);
-            x[l] = const_cast<double *>(xin);
-            alt[l] = xo;
-            continue;
-        }
-        double *xc = L.xa, *xo = L.xb, *rc = L.ra, *ro = L.rb;
-        launch_row<OP_PRE>(L.A, L.tpr_a, L.dinv, L.omega, B, nullptr, nullptr, nullptr, xc, rc, nullptr, nullptr, s, done);
-        for (int k = 1; k < nu; ++k) {
-            launch_row<OP_SWEEP>(L.A, L.tpr_a, L.dinv, L.omega, B, xc, rc, nullptr, xo, ro, nullptr, nullptr, s, done);
-            std::swap(xc, xo);
-            std::swap(rc, ro);
-        }
-        launch_row<OP_PLAIN>(L.Pt, L.tpr_pt, nullptr, 0.0, nullptr, nullptr, nullptr, rc, S.lv[l + 1].b, nullptr, nullptr, nullptr, s, done);
-        x[l] = xc;
-        alt[l] = xo;
-    }
-    hipLaunchKernelGGL(k_amg_gemv, dim3(grid_of(S.nco * 64)), dim3(kBlock), 0, s, S.nco, S.cinv, S.lv[Lc].b, S.lv[Lc].xa, done);
-    const double *xcoarse = S.lv[Lc].xa;
-    for (int l = Lc - 1; l >= 0; --l) {               // up: prolongation with correction, post-smoothing
-        AmgLevel &L = S.lv[l];
-        const double *B = l == 0 ? r : L.b;
-        if (L.smoother == DPCG_AMG_GAUSS_SEIDEL) {    // (level 0 sweeps in z itself)
-            double *out = l == 0 ? z : alt[l];
-            launch_row<OP_ACC>(L.P, L.tpr_p, nullptr, 0.0, nullptr, x[l], nullptr, xcoarse, out, nullptr, nullptr, nullptr, s, done);
-            gs_sweeps(L, nu, false, B, out, s, done);
-            xcoarse = out;
-            continue;
-        }
-        if (L.smoother == DPCG_AMG_CHEBYSHEV) {
-            double *xc = alt[l], *xo = x[l], *dn = L.da, *dn2 = L.db, *rn = L.rb, *rn2 = L.ra;
-            launch_row<OP_ACC>(L.P, L.tpr_p, nullptr, 0.0, nullptr, x[l], nullptr, xcoarse, xc, nullptr, nullptr, nullptr, s, done);
-            launch_row<OP_RES>(L.A, L.tpr_a, nullptr, 0.0, B, xc, nullptr, nullptr, nullptr, L.ra, nullptr, nullptr, s, done);
-            const double *din = nullptr, *rin = L.ra;
-            const int deg = (int)L.cheb_c1.size();
-            for (int t = 0; t < nu * deg; ++t) {
-                const int k = t % deg;
-                const double *dk = k == 0 ? nullptr : din;
-                if (t == nu * deg - 1) {
-                    double *out = l == 0 ? z : xo;
-                    double *part = l == 0 ? part_rz : nullptr;
-                    int grid = 0;
-                    launch_cheb<CHEB_LAST>(L, L.cheb_c1[k], L.cheb_c2[k], B, xc, dk, rin, out, nullptr, nullptr, part, &grid, s, done);
-                    if (part && n_part_rz) *n_part_rz = grid;
-                    xc = out;
-                    break;
-                }
-                launch_cheb<CHEB_STEP>(L, L.cheb_c1[k], L.cheb_c2[k], B, xc, dk, rin, xo, dn, rn, nullptr, nullptr, s, done);
-                din = dn; rin = rn;
-                std::swap(xc, xo); std::swap(dn, dn2); std::swap(rn, rn2);
-            }
-            xcoarse = xc;
-            continue;
-        }
-        double *xc = x[l], *xo = alt[l];
-        launch_row<OP_ACC>(L.P, L.tpr_p, nullptr, 0.0, nullptr, xc, nullptr, xcoarse, xo, nullptr, nullptr, nullptr, s, done);
-        std::swap(xc, xo);
-        for (int k = 0; k < nu; ++k) {
-            const bool last = k == nu - 1;
-            double *out = (l == 0 && last) ? z : xo;
-            double *part = (l == 0 && last) ? part_rz : nullptr;
-            int grid = 0;
-            launch_row<OP_POST>(L.A, L.tpr_a, L.dinv, L.omega, B, xc, nullptr, nullptr, out, nullptr, part, &grid, s, done);
-            if (part && n_part_rz) *n_part_rz = grid;
-            if (!(l == 0 && last)) std::swap(xc, xo);
-        }
-        xcoarse = xc;
-    }
-    return DPCG_OK;
+    if (S.precision == DPCG_AMG_FP32) return apply_cycle<float>(S, r, z, s, part_rz, n_part_rz, done);
+    return apply_cycle<double>(S, r, z, s, part_rz, n_part_rz, done);
 }
 
 extern "C" int dpcg_set_precond_amg(dpcg_handle_t h, double theta, int max_levels, int max_coarse, int sweeps, uint64_t seed,
@@ -1308,6 +1444,12 @@ extern "C" int dpcg_set_precond_amg(dpcg_handle_t h, double theta, int max_level
 
 extern "C" int dpcg_set_precond_amg_smoothed(dpcg_handle_t h, double theta, int max_levels, int max_coarse, int sweeps, uint64_t seed,
                                              int smoother, int degree, double eig_ratio, dpcg_stream_t stream) {
+    return dpcg_set_precond_amg_precision(h, theta, max_levels, max_coarse, sweeps, seed, smoother, degree, eig_ratio, DPCG_AMG_FP64,
+                                          stream);
+}
+
+extern "C" int dpcg_set_precond_amg_precision(dpcg_handle_t h, double theta, int max_levels, int max_coarse, int sweeps, uint64_t seed,
+                                              int smoother, int degree, double eig_ratio, int precision, dpcg_stream_t stream) {
     if (!h) return invalid("NULL handle");
     if (!(theta >= 0.0 && theta <= 1.0)) return invalid("dpcg_set_precond_amg: theta must lie in [0, 1]");
     if (max_levels < 1 || max_levels > 64) return invalid("dpcg_set_precond_amg: max_levels must lie in 1 .. 64");
@@ -1317,6 +1459,11 @@ extern "C" int dpcg_set_precond_amg_smoothed(dpcg_handle_t h, double theta, int 
         return invalid("dpcg_set_precond_amg_smoothed: unknown smoother (DPCG_AMG_JACOBI, _GAUSS_SEIDEL or _CHEBYSHEV)");
     if (degree < 1 || degree > 8) return invalid("dpcg_set_precond_amg_smoothed: degree must lie in 1 .. 8");
     if (!(eig_ratio > 1.0) || !std::isfinite(eig_ratio)) return invalid("dpcg_set_precond_amg_smoothed: eig_ratio must be finite and > 1");
+    if (precision != DPCG_AMG_FP64 && precision != DPCG_AMG_FP32)
+        return invalid("dpcg_set_precond_amg_precision: unknown precision (DPCG_AMG_FP64 or DPCG_AMG_FP32)");
+    if (precision == DPCG_AMG_FP32 && smoother == DPCG_AMG_GAUSS_SEIDEL)
+        return invalid("dpcg_set_precond_amg_precision: the fp32 cycle takes DPCG_AMG_JACOBI and DPCG_AMG_CHEBYSHEV only (Gauss-Seidel's "
+                       "cost is its colour passes, not its bytes)");
     hipStream_t s = (hipStream_t)stream;
     SetupScope scope(s, true);
     AmgState *old = h->amg_parked;
@@ -1333,6 +1480,7 @@ extern "C" int dpcg_set_precond_amg_smoothed(dpcg_handle_t h, double theta, int 
     S->smoother = smoother;
     S->degree = degree;
     S->eig_ratio = eig_ratio;
+    S->precision = precision;       // (not among the conditions of `reusable`: copies and work vectors are made anew by every build)
     // built before the attached preconditioner is freed: on failure that one stays (the build reads only the handle's matrix,
     // permutation and cached colouring, none of which belongs to the preconditioner)
     int st = build(h, *S, reusable ? old : nullptr, s);
@@ -1434,6 +1582,27 @@ extern "C" int dpcg_get_amg_level(dpcg_handle_t h, int level, const int64_t size
             }
         }
     }
+    return DPCG_OK;
+}
+
+extern "C" int dpcg_get_amg_precision(dpcg_handle_t h, int *precision) {
+    if (!h) return invalid("NULL handle");
+    if (h->precond != DPCG_PRECOND_AMG || !h->amg) {
+        set_error("dpcg_get_amg_precision: no smoothed-aggregation preconditioner is attached");
+        return DPCG_ERR_STATE;
+    }
+    if (precision) *precision = h->amg->precision;
+    return DPCG_OK;
+}
+
+extern "C" int dpcg_get_amg_launches(dpcg_handle_t h, int *launches, int *rz_partials) {
+    if (!h) return invalid("NULL handle");
+    if (h->precond != DPCG_PRECOND_AMG || !h->amg) {
+        set_error("dpcg_get_amg_launches: no smoothed-aggregation preconditioner is attached");
+        return DPCG_ERR_STATE;
+    }
+    if (launches) *launches = amg_launches(h->amg);
+    if (rz_partials) *rz_partials = amg_rz_partials(h->amg);
     return DPCG_OK;
 }
 

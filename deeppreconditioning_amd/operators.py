@@ -381,10 +381,16 @@ class SmoothedAggregation(Preconditioner):
     updates colour 0, 1, .., m-1, m-2, .., 0, each colour at once.  That is the parallel counterpart of pyamg's row-by-row sweep,
     not the same operator.  A level that needs more than 63 colours keeps Jacobi, and `amg_hierarchy().smoother` says so.
     "chebyshev" is a Chebyshev polynomial of `degree` steps in D^-1 A on [rho / eig_ratio, rho].  `sweeps` counts smoother
-    applications for all three; `degree` and `eig_ratio` matter for "chebyshev" only."""
+    applications for all three; `degree` and `eig_ratio` matter for "chebyshev" only.
+
+    `precision` is what the cycle STORES: "fp64" (the default) or "fp32".  With "fp32" the hierarchy is still built in fp64 (the
+    same bits), but the values of A_l, P_l, P_l^T and dinv_l are kept a second time rounded to fp32 and every work vector of the
+    cycle is fp32; all arithmetic stays fp64, PCG's r goes in and z comes out unrounded, and the dense coarse inverse stays fp64
+    (dpcg_set_precond_amg_precision in include/dpcg.h has the contract).  PCG's recurrences are fp64 either way, so the accuracy a
+    solve can reach does not change.  "fp32" takes "jacobi" and "chebyshev"; with "gauss_seidel" it is refused."""
 
     def __init__(self, theta: float = 0.0, max_levels: int = 10, max_coarse: int = 500, sweeps: int = 1, seed: int = 0,
-                 smoother: str = "jacobi", degree: int = 2, eig_ratio: float = 30.0):
+                 smoother: str = "jacobi", degree: int = 2, eig_ratio: float = 30.0, precision: str = "fp64"):
         if not 0.0 <= float(theta) <= 1.0:
             raise ValueError("theta must lie in [0, 1]")
         if not 1 <= int(max_levels) <= 64:
@@ -401,20 +407,27 @@ class SmoothedAggregation(Preconditioner):
             raise ValueError("degree must be an integer in 1 .. 8")
         if not (math.isfinite(float(eig_ratio)) and float(eig_ratio) > 1.0):
             raise ValueError("eig_ratio must be finite and > 1")
+        if precision not in AMG_PRECISIONS:
+            raise ValueError(f"precision must be one of {', '.join(AMG_PRECISIONS)}")
+        if precision == "fp32" and smoother == "gauss_seidel":
+            raise ValueError("precision 'fp32' takes the smoothers 'jacobi' and 'chebyshev' (the cost of Gauss-Seidel is its colour "
+                             "passes, not its bytes)")
         self.theta, self.max_levels, self.max_coarse = float(theta), int(max_levels), int(max_coarse)
         self.sweeps, self.seed = int(sweeps), int(seed)
         self.smoother, self.degree, self.eig_ratio = smoother, int(degree), float(eig_ratio)
+        self.precision = precision
 
     def _attach(self, system):
-        L.check(L.lib().dpcg_set_precond_amg_smoothed(system._h, self.theta, self.max_levels, self.max_coarse, self.sweeps,
-                                                      self.seed & (2**64 - 1), AMG_SMOOTHERS.index(self.smoother), self.degree,
-                                                      self.eig_ratio, _stream()))
+        L.check(L.lib().dpcg_set_precond_amg_precision(system._h, self.theta, self.max_levels, self.max_coarse, self.sweeps,
+                                                       self.seed & (2**64 - 1), AMG_SMOOTHERS.index(self.smoother), self.degree,
+                                                       self.eig_ratio, AMG_PRECISIONS.index(self.precision), _stream()))
 
     def __matmul__(self, r):
         raise TypeError("SmoothedAggregation needs the system matrix: attach it with CsrSystem.set_preconditioner")
 
 
 AMG_SMOOTHERS = ("jacobi", "gauss_seidel", "chebyshev")      # in the order of dpcg_amg_smoother (include/dpcg.h)
+AMG_PRECISIONS = ("fp64", "fp32")                            # in the order of dpcg_amg_precision
 
 
 @dataclass
@@ -434,6 +447,8 @@ class AmgHierarchy:
     complexities; how many levels a re-attach after `update_values` took over from the previous hierarchy (0: built afresh).
     Per smoothed level (all but the coarsest): the smoother it uses ("jacobi" also where Gauss-Seidel was asked for and the level
     could not be coloured), its number of colours (0 unless Gauss-Seidel) and the Chebyshev interval (lower, upper) or None.
+    `precision`: what the cycle stores, "fp64" or "fp32" (the hierarchy reported here is fp64 either way); `launches`: the kernel
+    launches of one cycle.
     `level(l)` copies level l out (0 <= l < levels - 1) of the hierarchy attached NOW; it raises when that is no longer the one
     this snapshot describes (the system was re-attached meanwhile with other sizes)."""
     levels: int
@@ -448,6 +463,8 @@ class AmgHierarchy:
     smoother: list = field(default_factory=list)
     colors: list = field(default_factory=list)
     chebyshev: list = field(default_factory=list)
+    precision: str = "fp64"
+    launches: int = 0
     _system: "object" = None
 
     def level(self, l: int) -> AmgLevel:
@@ -874,12 +891,16 @@ class CsrSystem:
         sm, ncol, lo, hi = np.zeros(cap, dtype=np.int32), np.zeros(cap, dtype=np.int32), np.zeros(cap), np.zeros(cap)
         with torch.cuda.device(self.device):
             L.check(L.lib().dpcg_get_amg_smoothers(self._h, cap, _np_ptr(sm), _np_ptr(ncol), _np_ptr(lo), _np_ptr(hi)))
+            prec = C.c_int(0)
+            L.check(L.lib().dpcg_get_amg_precision(self._h, C.byref(prec)))
+            launches = C.c_int(0)
+            L.check(L.lib().dpcg_get_amg_launches(self._h, C.byref(launches), None))
         m = max(k - 1, 0)
         cheb = [(float(a), float(b)) if int(t) == L.AMG_CHEBYSHEV else None for t, a, b in zip(sm[:m], lo[:m], hi[:m])]
         return AmgHierarchy(k, [int(v) for v in rows[:k]], [int(v) for v in nnz[:k]], [int(v) for v in pnnz[:k]],
                             [float(v) for v in rho[:k]], [float(v) for v in omega[:k]], oc.value, gc.value, reused.value,
                             smoother=[AMG_SMOOTHERS[int(v)] for v in sm[:m]], colors=[int(v) for v in ncol[:m]], chebyshev=cheb,
-                            _system=self)
+                            precision=AMG_PRECISIONS[prec.value], launches=launches.value, _system=self)
 
     def spectrum_bounds(self, *, max_steps: int = 1000, rtol: float = 1e-6, seed: int = 0) -> SpectrumBounds:
         """Extreme eigenvalues of M A for the attached preconditioner M (M = I without one) and kappa = lambda_max / lambda_min,

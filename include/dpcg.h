@@ -270,6 +270,35 @@ int dpcg_set_precond_amg(dpcg_handle_t h, double theta, int max_levels, int max_
 enum dpcg_amg_smoother { DPCG_AMG_JACOBI = 0, DPCG_AMG_GAUSS_SEIDEL = 1, DPCG_AMG_CHEBYSHEV = 2 };
 int dpcg_set_precond_amg_smoothed(dpcg_handle_t h, double theta, int max_levels, int max_coarse, int sweeps, uint64_t seed,
                                   int smoother, int degree, double eig_ratio, dpcg_stream_t stream);
+/* The same hierarchy and cycle with the cycle's operands and work vectors STORED in single precision (DPCG_AMG_FP64: exactly
+ * dpcg_set_precond_amg_smoothed).  The V-cycle is bound by the bytes it moves, not by arithmetic; hypre, AmgX and Ginkgo offer
+ * the same under a double-precision Krylov method.  PCG's own recurrences stay fp64, so the attainable accuracy does not change;
+ * only M is perturbed, at the 6e-8 level.  The contract of DPCG_AMG_FP32:
+ *   setup: the hierarchy is built in fp64 exactly as for DPCG_AMG_FP64 (dpcg_get_amg_info / _level return the same bits);
+ *   copies: after the setup (and after every re-attach) the values of A_l, P_l, P_l^T (the rounded numbers of P_l) and dinv_l of
+ *     every level but the coarsest are stored once more, rounded to fp32 (nearest even); patterns are shared; the fp64 arrays stay;
+ *   coarsest level: the dense inverse stays fp64 (small, and the one operator whose rounding error kappa(A_c) amplifies); it reads
+ *     the fp32 right-hand side and its result is rounded to fp32;
+ *   work vectors: all fp32, except that level 0 reads PCG's r and writes z in fp64 (neither is rounded; the <r, z> partials are
+ *     formed in fp64 from those values);
+ *   arithmetic: fp64 throughout -- operands are converted on load, products and row sums are fp64, omega and the Chebyshev scalars
+ *     are double.  Whatever the fp64 cycle stores to a work vector is rounded to fp32 where it is computed, whether it is then
+ *     stored or consumed in place: the gathered y_j = omega dinv_j b_j and y_j = x_j + omega dinv_j r_j are rounded before they
+ *     enter a row sum (r = b - A x is formed from exactly the x that is stored), and so are Chebyshev's d'_j and x_j + d'_j (the
+ *     last step of a level stores no d', so there d' is not rounded);
+ *   smoothers: DPCG_AMG_JACOBI and DPCG_AMG_CHEBYSHEV; DPCG_AMG_GAUSS_SEIDEL with DPCG_AMG_FP32 is DPCG_ERR_INVALID (its cost is
+ *     its colour passes, not its bytes), as is an unknown precision; the attached preconditioner stays;
+ *   launches: the same as the fp64 cycle's; no float atomics: two applies give the same bits.
+ * A hierarchy parked by dpcg_update_values is taken over whatever its precision was: copies and work vectors are made anew. */
+enum dpcg_amg_precision { DPCG_AMG_FP64 = 0, DPCG_AMG_FP32 = 1 };
+int dpcg_set_precond_amg_precision(dpcg_handle_t h, double theta, int max_levels, int max_coarse, int sweeps, uint64_t seed,
+                                   int smoother, int degree, double eig_ratio, int precision, dpcg_stream_t stream);
+/* *precision: the dpcg_amg_precision of the attached hierarchy's cycle.  DPCG_ERR_STATE when the handle's preconditioner is not AMG. */
+int dpcg_get_amg_precision(dpcg_handle_t h, int *precision);
+/* *launches: the kernel launches of one V-cycle of the attached hierarchy; *rz_partials: the per-workgroup partials of <r, z> its
+ * last smoothing pass leaves for PCG (0: PCG sums <r, z> itself).  Neither depends on the precision.  Either pointer may be NULL.
+ * DPCG_ERR_STATE when the handle's preconditioner is not AMG. */
+int dpcg_get_amg_launches(dpcg_handle_t h, int *launches, int *rz_partials);
 /* Per smoothed level l < min(capacity, n_levels - 1) (host arrays, any may be NULL): the smoother the level USES (a Gauss-Seidel
  * level that could not be coloured reports DPCG_AMG_JACOBI), its number of colours (0 unless Gauss-Seidel) and the Chebyshev
  * interval [lower, upper] (0 unless Chebyshev).  DPCG_ERR_STATE when the handle's preconditioner is not AMG. */
