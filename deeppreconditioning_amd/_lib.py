@@ -87,6 +87,13 @@ SIGNATURES = {
     "dpcg_spectrum": (_int, [_p, _int, _dbl, C.c_uint64, _p, C.POINTER(_int), C.POINTER(_dbl), C.POINTER(_dbl),
                              C.POINTER(_dbl), C.POINTER(_dbl), _p, _p]),
     "dpcg_tridiag_ritz": (_int, [_int, _p, _p, _p, _p]),
+    "dpcg_guess_create": (_int, [_p, _int, _dbl, C.POINTER(_p)]),
+    "dpcg_guess_project": (_int, [_p, _p, _p, _p]),
+    "dpcg_guess_update": (_int, [_p, _p, _p]),
+    "dpcg_guess_reset": (_int, [_p]),
+    "dpcg_guess_info": (_int, [_p, _p]),
+    "dpcg_guess_get_basis": (_int, [_p, _p, _p]),
+    "dpcg_guess_destroy": (_int, [_p]),
     "dpcg_solve": (_int, [_p, _p, _p, _p, _dbl, _dbl, _int, _int, _p, C.POINTER(_int), C.POINTER(_dbl),
                           C.POINTER(_dbl), _p, _p, _p]),
     "dpcg_solve_batch": (_int, [_int, _p, _p, _p, _p, _dbl, _dbl, _int, _int, _int, _p, _p, _p, _p]),

@@ -396,6 +396,7 @@ extern "C" int dpcg_create(dpcg_handle_t *out, int64_t n, int64_t nnz, const int
 extern "C" int dpcg_destroy(dpcg_handle_t h) {
     if (!h) return DPCG_OK;
     SetupScope scope(nullptr, true);                      // (waits for the device: the arrays may be in use on any stream)
+    orphan_guesses(h);
     free_precond(h);
     free_csr(h->A);
     free_csr(h->A_user);
@@ -570,6 +571,7 @@ extern "C" int dpcg_update_values(dpcg_handle_t h, const void *val, int val_dtyp
     free_precond(h, true);
     free_ell(h->ell_a);
     drop_graph(h);
+    h->values_epoch += 1;                        // (a projected guess re-orthonormalises its basis before its next use)
     DPCG_CHECK_LAUNCH();
     return DPCG_OK;
 }

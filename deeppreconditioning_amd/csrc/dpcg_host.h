@@ -80,6 +80,7 @@ void fsai_detach(FsaiCache *c);                         // the handle's precondi
 void fsai_mark_attached(FsaiCache *c);
 void free_parked(dpcg_system *h);                       // dpcg_api.hip: the multicolour IC(0) parked by dpcg_update_values
 void free_levels(Levels &l);
+namespace dpcg { void orphan_guesses(dpcg_system *h); }   // dpcg_guess.hip: the handle is going away
 int count_levels_on_demand(dpcg_system *h);   // dpcg_precond.hip
 void free_plan(SpmvPlan &plan);
 void free_ell(SmallEll &e);

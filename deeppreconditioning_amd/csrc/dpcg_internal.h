@@ -228,6 +228,8 @@ struct ChipTrsvLists {
 };
 }  // namespace dpcg
 
+struct dpcg_guess;   // dpcg_guess.hip: a projected initial guess (dpcg_guess_*)
+
 struct dpcg_system {
     dpcg::CsrDev A;
     dpcg::SpmvPlan planA;
@@ -313,6 +315,10 @@ struct dpcg_system {
     hipGraphExec_t graph_exec = nullptr;
     int graph_key = -1;
     int graph_chunk = 0;
+    // dpcg_guess_*: dpcg_update_values counts the matrices the handle has held; a guess compares its own copy against it.  The
+    // guesses made for this handle (dpcg_destroy takes their buffers and their system away; the objects are the caller's)
+    uint64_t values_epoch = 0;
+    std::vector<dpcg_guess *> guesses;
 };
 
 namespace dpcg {

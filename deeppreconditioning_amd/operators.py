@@ -857,9 +857,19 @@ class CsrSystem:
         return float(ms.value)
 
     def solve(self, b, x0=None, *, rtol_sq: float = 1e-8, atol_sq: float = 0.0, max_iter: int = 1024, flags: int = 0,
-              x_true=None, want_history: bool = True) -> SolveResult:
-        """Run the PCG loop of cg.py:58-90 on the GPU (see dpcg_solve in include/dpcg.h)."""
+              x_true=None, want_history: bool = True, guess: "ProjectedGuess | None" = None) -> SolveResult:
+        """Run the PCG loop of cg.py:58-90 on the GPU (see dpcg_solve in include/dpcg.h).
+
+        `guess` (a `ProjectedGuess` of this system): the solve starts from the projection of b onto the span of the earlier
+        solutions and hands its own solution to the guess afterwards (a capped solve too; a breakdown does not).  Not together
+        with `x0`."""
         bv = self._vec(b)
+        if guess is not None:
+            if x0 is not None:
+                raise ValueError("pass either x0 or guess, not both")
+            if guess.system is not self:
+                raise ValueError("the guess belongs to another system")
+            x0 = guess.project(bv)
         x0v = None if x0 is None else self._vec(x0)
         xt = None if x_true is None else self._vec(x_true)
         x = torch.empty_like(bv)
@@ -874,6 +884,8 @@ class CsrSystem:
             err, self._precond.error = self._precond.error, None
             raise err
         k = iters.value
+        if guess is not None and status != L.BREAKDOWN:
+            guess.update(x)
         return SolveResult(x, k, status, res.value, sec.value, hist[: k + 1] if hist is not None else np.empty(0),
                            err[: k + 1] if err is not None else None)
 
@@ -927,6 +939,64 @@ class CsrSystem:
         kappa = tmax.value / tmin.value if tmin.value > 0 else float("nan")
         return SpectrumBounds(tmin.value, tmax.value, kappa, steps, status == L.OK, emin.value, emax.value,
                               alpha[:steps].copy(), beta[:steps].copy())
+
+
+class ProjectedGuess:
+    """Initial guesses for a SEQUENCE of solves on one system, projected from the solutions so far (dpcg_guess_*, include/dpcg.h;
+    P. F. Fischer, CMAME 163, 1998): `system.solve(b, guess=guess)` starts from the A-norm-best approximation of the solution in
+    the span of up to `depth` earlier ones.  The basis lives on the device in the caller's numbering; `update_values` is noticed
+    (the basis is re-orthonormalised against the new matrix before its next use).  No reference counterpart (cg.py:58 starts
+    from zeros)."""
+
+    def __init__(self, system: "CsrSystem", depth: int = 8, tol_dep: float = 1e-7):
+        self.system = system
+        self.depth = int(depth)
+        self._g = C.c_void_p()
+        with torch.cuda.device(system.device):
+            L.check(L.lib().dpcg_guess_create(system._h, int(depth), float(tol_dep), C.byref(self._g)))
+
+    def project(self, b) -> torch.Tensor:
+        """x0 = X~ (X~^T b); zeros while the basis is empty.  Raises DpcgError (ERR_INVALID) when b holds a non-finite value."""
+        bv = self.system._vec(b)
+        x0 = torch.empty_like(bv)
+        with torch.cuda.device(self.system.device):
+            L.check(L.lib().dpcg_guess_project(self._g, _dev_ptr(bv), _dev_ptr(x0), _stream()))
+        return x0
+
+    def update(self, x) -> None:
+        """Hand the solution of the system last projected for to the basis (appended, skipped as dependent, or a restart)."""
+        xv = self.system._vec(x)
+        with torch.cuda.device(self.system.device):
+            L.check(L.lib().dpcg_guess_update(self._g, _dev_ptr(xv), _stream()))
+
+    def reset(self) -> None:
+        L.check(L.lib().dpcg_guess_reset(self._g))
+
+    def info(self) -> dict:
+        out = (C.c_int32 * 8)()
+        L.check(L.lib().dpcg_guess_info(self._g, out))
+        return {"depth": out[0], "size": out[1], "restarts": out[2], "appended": out[3], "skipped": out[4], "dropped": out[5],
+                "reorthonormalisations": out[6], "values_epoch": out[7]}
+
+    def basis(self):
+        """(X~, W) as host arrays of shape (n, size), W = A X~ (for tests)."""
+        size = self.info()["size"]
+        X = np.zeros((self.system.n, size), order="F")
+        W = np.zeros((self.system.n, size), order="F")
+        with torch.cuda.device(self.system.device):
+            L.check(L.lib().dpcg_guess_get_basis(self._g, _np_ptr(X), _np_ptr(W)))
+        return X, W
+
+    def close(self) -> None:
+        if getattr(self, "_g", None) is not None and self._g.value:
+            L.lib().dpcg_guess_destroy(self._g)
+            self._g = C.c_void_p()
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def tridiag_ritz(alpha, beta):

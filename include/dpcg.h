@@ -412,6 +412,39 @@ int dpcg_spectrum(dpcg_handle_t h, int max_steps, double rtol, uint64_t seed, dp
  * arbitrary).  Implicit QL with Wilkinson shifts. */
 int dpcg_tridiag_ritz(int k, const double *alpha, const double *beta, double *theta, double *bottom);
 
+/* ---- projected initial guess for a SEQUENCE of systems on one handle ------------------------------------------------
+ * The reference starts every solve from zeros (cg.py:58).  In a time-stepping run ("same mesh, next time step") consecutive
+ * solutions lie close to the span of the last few; P. F. Fischer's projection (CMAME 163, 1998) starts the next solve from the
+ * A-norm-best approximation in that span.  The object keeps, per system, a basis X~ = [x~_0 .. x~_{l-1}], l <= depth, with
+ * x~_i^T A x~_j = delta_ij, and W = A X~, both on the device and in the CALLER's numbering (dpcg_reorder does not touch them).
+ *   project(b): c = X~^T b, x0 = X~ c (l = 0: zeros).  x0: device fp64[n], out; the object keeps a copy for the next update.
+ *   update(x):  d = x - x0, w = A d (the handle's SpMV), classical Gram-Schmidt twice in the A inner product (g = X~^T w,
+ *     d -= X~ g, w -= W g), s = <d, w>.  The direction is dependent -- skipped, the size stays -- when s <= tol_dep^2 <x, A x>
+ *     or s is not finite; otherwise d / sqrt(s) and w / sqrt(s) are appended.  A full basis (l == depth) restarts instead, as
+ *     Fischer does: it becomes the single vector x / ||x||_A (one SpMV).  The x0 of the last project is used only while the
+ *     basis it was formed from stands (no restart, re-orthonormalisation or reset in between); otherwise d = x.
+ *   new matrix values: dpcg_update_values moves the handle's values epoch; the next project (or update) sees that its own copy
+ *     is behind and first makes the basis consistent: W = A X~ by l SpMVs, then twice (CholQR2) the Gram matrix G = X~^T W on
+ *     the device, G = R^T R on the host -- direction j and all later ones are dropped at the first pivot <= tol_dep^2 G_jj --
+ *     and X~ <- X~ R^-1, W <- W R^-1 in place on the device.
+ * depth 1 .. 32, tol_dep > 0 (1e-7 is a good default); otherwise DPCG_ERR_INVALID.  Memory: 2 x depth x ld doubles from the block
+ * cache, ld = n rounded up to a multiple of 1024 (DPCG_ERR_NOMEM when they do not fit).  Every sum has one fixed order (no float
+ * atomics): the same sequence gives the same bits.  project and update read scalars back: each synchronises `stream` once.
+ * A non-finite value in b or x is DPCG_ERR_INVALID and leaves the basis (and the kept x0) as it was.  One thread and one stream
+ * at a time, as for the handle.  After dpcg_destroy of the system every call but dpcg_guess_destroy returns DPCG_ERR_STATE.
+ * dpcg_guess_reset empties the basis and the counters.  dpcg_guess_info: out = {depth, size, restarts, appended, skipped as
+ * dependent, dropped at a re-orthonormalisation, re-orthonormalisations (one per change of the matrix the object has seen,
+ * whatever the size), the values epoch the basis is consistent with}.  dpcg_guess_get_basis (for tests): the `size` columns of
+ * X~ and of W, column-major with n rows each, into host arrays (either may be NULL); waits for the device. */
+typedef struct dpcg_guess *dpcg_guess_t;
+int dpcg_guess_create(dpcg_handle_t h, int depth, double tol_dep, dpcg_guess_t *out);
+int dpcg_guess_project(dpcg_guess_t g, const double *b, double *x0, dpcg_stream_t stream);
+int dpcg_guess_update(dpcg_guess_t g, const double *x, dpcg_stream_t stream);
+int dpcg_guess_reset(dpcg_guess_t g);
+int dpcg_guess_info(dpcg_guess_t g, int32_t out[8]);
+int dpcg_guess_get_basis(dpcg_guess_t g, double *X_host, double *W_host);
+int dpcg_guess_destroy(dpcg_guess_t g);
+
 /* ---- the solve: cg.py:50-90 (PCG) and cg.py:20-47 (CG = PCG with M = I, test on r) ----------- */
 /*
  * b, x0 (may be NULL = zeros, cg.py:58), x (out, may be NULL): device fp64[n].  x is written in stream order: valid for
