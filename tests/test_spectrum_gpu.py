@@ -10,6 +10,7 @@ import scipy.sparse as sp
 import torch
 
 from oracle import oracle as O
+from spectrum_restatement import _hash, _lanczos_numpy  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -20,44 +21,6 @@ def D():
     assert torch.cuda.is_available(), "these tests need the GPU"
     pkg._lib.lib()
     return pkg
-
-
-def _hash(seed, idx):
-    """The start vector's counter-based hash (k_lz_start) restated in numpy: splitmix64's finaliser of a counter."""
-    with np.errstate(over="ignore"):
-        x = np.uint64(seed) * np.uint64(0x9E3779B97F4A7C15) + (idx.astype(np.uint64) + np.uint64(1)) * np.uint64(0xBF58476D1CE4E5B9)
-        x ^= x >> np.uint64(30)
-        x *= np.uint64(0xBF58476D1CE4E5B9)
-        x ^= x >> np.uint64(27)
-        x *= np.uint64(0x94D049BB133111EB)
-        x ^= x >> np.uint64(31)
-    return (x >> np.uint64(11)).astype(np.float64) * (1.0 / 9007199254740992.0) * 2.0 - 1.0
-
-
-def _lanczos_numpy(A, Mdense_apply, seed, k):
-    """fp64 restatement of the recurrence of dpcg_lanczos.hip (M inner product, CGS2)."""
-    n = A.shape[0]
-    v = _hash(seed, np.arange(n))
-    u = Mdense_apply(v)
-    nrm = np.sqrt(v @ u)
-    R, Z = [v / nrm], [u / nrm]
-    alpha, beta = [], [0.0]
-    for j in range(k):
-        w = A @ Z[j]
-        a = Z[j] @ w
-        w = w - a * R[j]
-        if j > 0:
-            w = w - beta[j] * R[j - 1]
-        for _ in range(2):
-            Rm, Zm = np.array(R).T, np.array(Z).T
-            w = w - Rm @ (Zm.T @ w)
-        u = Mdense_apply(w)
-        b = np.sqrt(w @ u)
-        alpha.append(a)
-        beta.append(b)
-        R.append(w / b)
-        Z.append(u / b)
-    return np.array(alpha), np.array(beta[1:])
 
 
 def _poisson2d_eigs(m):
