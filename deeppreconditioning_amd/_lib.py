@@ -25,6 +25,8 @@ PRECOND_NONE, PRECOND_JACOBI, PRECOND_CSR, PRECOND_LLT_MULTIPLY, PRECOND_LLT_SOL
 PRECOND_LU_MULTIPLY, PRECOND_LU_SOLVE = 7, 8
 PRECOND_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p)   # dpcg_precond_fn
 INIT_CHECK_R, SPMV_F32, NO_GRAPH, NO_SMALL, VAL32_IF_LOSSLESS, NO_FUSE, NO_TEAM, TEAM = 1, 2, 4, 8, 16, 32, 64, 128
+SINGLE_REDUCTION = 256
+RECURRENCES = ("standard", "single_reduction")      # dpcg_get_last_recurrence
 REORDER_NONE, REORDER_AUTO, REORDER_ALWAYS, REORDER_REGIONS = 0, 1, 2, 3
 ORDER_CALLER, ORDER_MULTICOLOR = 0, 1
 AMG_JACOBI, AMG_GAUSS_SEIDEL, AMG_CHEBYSHEV = 0, 1, 2
@@ -72,6 +74,7 @@ SIGNATURES = {
     "dpcg_get_lu_factors": (_int, [_p, C.POINTER(_i64), C.POINTER(_i64), _p, _p, _p, _p, _p, _p]),
     "dpcg_get_reduction_geometry": (_int, [_p, _p]),
     "dpcg_get_chip_info": (_int, [_p, _p, _p]),
+    "dpcg_get_last_recurrence": (_int, [_p, C.POINTER(_int)]),
     "dpcg_debug_occupy": (_int, [_int, C.c_double, _p]),
     "dpcg_debug_l2_gather": (_int, [_int, _int, C.POINTER(C.c_int32), _int, _int, _p, C.POINTER(_dbl), C.POINTER(_dbl), C.POINTER(_int)]),
     "dpcg_get_factor": (_int, [_p, _p, _p, _p]),

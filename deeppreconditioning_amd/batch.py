@@ -61,7 +61,12 @@ def solve_batch(systems: list[CsrSystem], rhs: list[torch.Tensor], x0: list | No
         L.check(L.lib().dpcg_solve_batch(count, handles, b_arr, x0_arr, x_arr, rtol_sq, atol_sq, int(max_iter),
                                          int(flags), int(n_streams), iters, res, sec, status))
     no_history = np.empty(0)
-    return [SolveResult(xs[i], iters[i], status[i], res[i], sec[i], no_history) for i in range(count)]
+    ran = []
+    for sysm in systems:                        # the recurrence every member RAN (a member that fell back says "standard")
+        word = C.c_int(0)
+        L.check(L.lib().dpcg_get_last_recurrence(sysm._h, C.byref(word)))
+        ran.append(L.RECURRENCES[word.value])
+    return [SolveResult(xs[i], iters[i], status[i], res[i], sec[i], no_history, None, ran[i]) for i in range(count)]
 
 
 @dataclass

@@ -42,7 +42,7 @@ def _system_and_device(A, b):
 
 
 def preconditioned_conjugate_gradient(A, b, M, x0=None, x_true=None, rtol=1e-8, max_iter=1024, *,
-                                      mixed_precision=False, compact_values=False, details=False):
+                                      mixed_precision=False, compact_values=False, details=False, recurrence="standard"):
     """PCG, cg.py:50-90.  Returns `(duration_seconds, iterations, info)`.
 
     `rtol` is compared with <r,r>/<b,b> (squared ratio, cg.py:71); the first test uses z0
@@ -51,7 +51,9 @@ def preconditioned_conjugate_gradient(A, b, M, x0=None, x_true=None, rtol=1e-8, 
     (fp64 everywhere else, BASELINE config 5); `compact_values` streams the matrix values as fp32
     when that is lossless (the reference's matrices are fp32 data upcast to fp64, test.py:68) --
     bit-identical results, 8 instead of 12 bytes per non-zero; `details=True` returns the full
-    `SolveResult` (status 0 converged / 1 max_iter / 2 breakdown, residual history, x).
+    `SolveResult` (status 0 converged / 1 max_iter / 2 breakdown, residual history, x); `recurrence="single_reduction"` asks for
+    Chronopoulos and Gear's single-synchronisation form of the loop (`CsrSystem.solve`: M = None or Jacobi on chip-sized systems,
+    other bits than the reference's recurrence, which stays the default).
 
     The plain return value follows the reference to the letter: `info` is always 0 (cg.py:90), and a NaN
     breakdown (b = 0, NaN input, singular M), on which the reference keeps looping because `nan < rtol` is
@@ -61,19 +63,21 @@ def preconditioned_conjugate_gradient(A, b, M, x0=None, x_true=None, rtol=1e-8, 
     system = _system_and_device(A, b)
     system.set_preconditioner(M)
     flags = (L.SPMV_F32 if mixed_precision else 0) | (L.VAL32_IF_LOSSLESS if compact_values else 0)
-    result = system.solve(b, x0, rtol_sq=float(rtol), max_iter=int(max_iter), flags=flags)
+    result = system.solve(b, x0, rtol_sq=float(rtol), max_iter=int(max_iter), flags=flags, recurrence=recurrence)
     if details:
         return result
     iterations = int(max_iter) if result.status == L.BREAKDOWN else result.iterations
     return result.seconds, iterations, 0
 
 
-def conjugate_gradient(A, b, x0=None, x_true=None, rtol=1e-8, max_iter=1024):
+def conjugate_gradient(A, b, x0=None, x_true=None, rtol=1e-8, max_iter=1024, *, recurrence="standard"):
     """Unpreconditioned CG, cg.py:20-47.  Returns `(errors, x_hat)` with
-    `errors[k] = (A-norm error of x_k or 0, <r_k,r_k>/<b,b>)` as 0-d tensors."""
+    `errors[k] = (A-norm error of x_k or 0, <r_k,r_k>/<b,b>)` as 0-d tensors.  `recurrence="single_reduction"` (keyword-only, not
+    together with `x_true`): see `preconditioned_conjugate_gradient`."""
     system = _system_and_device(A, b)
     system.set_preconditioner(None)
-    result = system.solve(b, x0, rtol_sq=float(rtol), max_iter=int(max_iter), flags=L.INIT_CHECK_R, x_true=x_true)
+    result = system.solve(b, x0, rtol_sq=float(rtol), max_iter=int(max_iter), flags=L.INIT_CHECK_R, x_true=x_true,
+                          recurrence=recurrence)
     res = torch.from_numpy(result.res_history.copy()).to(system.device)
     if result.err_history is not None:
         err = torch.from_numpy(result.err_history.copy()).to(system.device)

@@ -300,6 +300,8 @@ struct dpcg_system {
     double *chip_part = nullptr;             // the chip kernel's reduction slots (4 x 256 x 2 doubles) + 8 trace words + the error flag
     double *chip_zp = nullptr;               // ... and its published granules
     double *chip_rt = nullptr;               // M = L L^T multiplied on the chip: the published r and t = L^T r
+    double *chip_part2 = nullptr;            // the single-reduction chip kernel's second slot set (dpcg_chip_sr.hip)
+    int last_recurrence = 0;                 // what the last solve ran: 0 the standard recurrence, 1 the single-reduction one
     // M = L L^T solved on the chip (dpcg_chip_trsv.hip): the block lists of L and L^T, built at the first solve with this preconditioner
     // (trsv_state: 0 not tried yet, 1 built, -1 this factor does not fit the form) and dropped with it
     dpcg::ChipTrsvLists trsv_l, trsv_u;
@@ -509,6 +511,15 @@ struct ChipDesc {
     int *err;
     unsigned long long *dbg;   // DPCG_CHIP_TRACE=1: 8 words per workgroup, ticks (100 MHz) its thread 0 spent per phase of the updates; else null
 };
+// dpcg_chip_sr.hip: the resident fp64 form of the above with the single-reduction recurrence (DPCG_SINGLE_REDUCTION)
+struct ChipSrDesc {
+    ChipDesc c;                // zp: 2 x (n + 4096) self-validating granules {z, z ^ key}, all zero at launch
+    double *part2;             // the second slot set: chip_slot_doubles() doubles, preset to the "pending" pattern like c.part
+    double *xwork;             // n doubles: x of the own rows at 8 rows a thread (may be c.x)
+    unsigned int nonce;        // != 0, unique per launch: keys the granules
+};
+int chip_sr_max_row_len(int64_t n);
+int launch_pcg_chip_sr(const ChipSrDesc &d, int max_row_len, hipStream_t s, bool check_only = false);
 // dpcg_chip_trsv.hip: M applied by two triangular solves (L y = r, L^T z = y) inside the whole-chip kernel.  The block lists of one triangular
 // factor in the chip kernel's geometry: per chip wave (workgroup v, wave w: index 8 v + w) the blocks [first_blk[i], first_blk[i + 1]), each
 // {k | W << 8 | level << 16, lane mask lo, hi, first entry}; entries {val, col} compacted over a block's active lanes.

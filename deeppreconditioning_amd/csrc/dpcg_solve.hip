@@ -880,6 +880,126 @@ static int solve_chip_one(dpcg_system *h, const double *b, const double *x0, dou
     return sc.status;
 }
 
+// DPCG_SINGLE_REDUCTION: the single-reduction recurrence in the whole-chip kernel (dpcg_chip_sr.hip) -- opt-in, and only where the resident
+// fp64 form of the chip kernel is taken.  Why a system with the flag set cannot take it (nullptr: it can): the caller is told, the
+// other recurrence is never substituted silently.
+static const char *chip_sr_refusal(const dpcg_system *h, int flags, const double *x_true) {
+    if (x_true) return "the single-reduction recurrence does not track x_true";
+    if (flags & DPCG_SPMV_F32) return "the single-reduction recurrence is fp64 only (DPCG_SPMV_F32 is set)";
+    if (flags & (DPCG_NO_SMALL | DPCG_NO_GRAPH | DPCG_NO_TEAM | DPCG_NO_FUSE))
+        return "the single-reduction recurrence exists in the whole-chip kernel only (DPCG_NO_SMALL / DPCG_NO_GRAPH / DPCG_NO_TEAM / DPCG_NO_FUSE keep the launches)";
+    if (h->precond != DPCG_PRECOND_NONE && h->precond != DPCG_PRECOND_JACOBI)
+        return "the single-reduction recurrence takes M = I or Jacobi only";
+    if (h->A.n > chip_max_rows()) return "the single-reduction recurrence takes at most 1 048 576 rows";
+    if (!chip_eligible(h, flags, x_true)) return "the single-reduction recurrence needs a system of the whole-chip kernel's size (more than 65 536 rows, one workgroup per CU)";
+    if (h->planA.max_band > chip_max_band()) return "the single-reduction recurrence needs every column within 32 767 of its row";
+    if (h->planA.max_row_len > chip_sr_max_row_len(h->A.n))
+        return h->A.n > chip_max_rows() / 2 ? "the single-reduction recurrence takes rows of at most 5 entries beyond 524 288 rows"
+                                            : "the single-reduction recurrence takes rows of at most 7 entries";
+    return nullptr;
+}
+
+static int solve_chip_sr_one(dpcg_system *h, const double *b, const double *x0, double *x, double rtol_sq, double atol_sq,
+                             int max_iter, int flags, hipStream_t s, int *iters, double *final_res, double *seconds,
+                             double *res_history) {
+    const int64_t n = h->A.n;
+    DPCG_TRY(ensure_work(h, max_iter, false, false));
+    const int kSlots = chip_slot_doubles();
+    if (!h->chip_part) DPCG_TRY(dev_alloc(&h->chip_part, kSlots + 8 * 256 + 2 + 128));      // slots | trace words | flag | XCD ids
+    if (!h->chip_part2) DPCG_TRY(dev_alloc(&h->chip_part2, kSlots));
+    if (!h->chip_zp) DPCG_TRY(dev_alloc(&h->chip_zp, chip_zp_doubles(n)));
+    if (h->perm) {                         // b and x0 arrive in the caller's numbering
+        if (!h->pb) DPCG_TRY(dev_alloc(&h->pb, n));
+        launch_gather_f64(n, h->perm, b, h->pb, s);
+        b = h->pb;
+        if (x0) {
+            launch_gather_f64(n, h->perm, x0, h->t, s);
+            x0 = h->t;
+        }
+    }
+    ChipSrDesc ds;
+    memset(&ds, 0, sizeof(ds));
+    ChipDesc &d = ds.c;
+    d.n = (int)n;
+    d.precond = h->precond;
+    d.max_iter = max_iter;
+    d.init_check_r = (flags & DPCG_INIT_CHECK_R) ? 1 : 0;
+    d.hist_cap = h->hist_cap;
+    d.per = chip_rows_per_wg(n);
+    d.rp = h->A.rowptr; d.ci = h->A.col; d.val = h->A.val; d.dinv = h->dinv;
+    d.b = b; d.x0 = x0;
+    d.x = (x && !h->perm) ? x : h->x;
+    d.hist = h->hist;
+    d.zp = h->chip_zp;
+    d.rtol_sq = rtol_sq; d.atol_sq = atol_sq;
+    d.out = h->scal;
+    d.part = h->chip_part;
+    d.err = reinterpret_cast<int *>(h->chip_part + kSlots + 8 * 256);
+    d.band = h->planA.max_band;
+    d.rp_nnz = (int)std::min<int64_t>(h->A.nnz, 0x1fffffff);
+    static const bool plain_ok = [] { const char *e = getenv("DPCG_CHIP_LOCAL"); return !(e && e[0] == '0'); }();   // development: 0 = everything written through
+    d.xcc = plain_ok ? reinterpret_cast<int *>(h->chip_part + kSlots + 8 * 256 + 2) : nullptr;
+    ds.part2 = h->chip_part2;
+    ds.xwork = h->x;
+    static std::atomic<unsigned> launch_nonce{0x80000000u};
+    unsigned nonce = 0;
+    do { nonce = ++launch_nonce; } while (nonce == 0);
+    ds.nonce = nonce;
+    const int st0 = launch_pcg_chip_sr(ds, h->planA.max_row_len, s, true);            // refused up front when it cannot be resident
+    if (st0 != DPCG_OK) return st0;
+    launch_fill_pending(h->chip_part, kSlots, s);                                     // every reduction slot of both sets: "not written yet"
+    launch_fill_pending(h->chip_part2, kSlots, s);
+    DPCG_HIP(hipMemsetAsync(d.err, 0, 2 * sizeof(int), s));
+    // the granule table: zeros, which no key accepts (every key is odd) -- whatever an earlier solve of either recurrence left is gone
+    DPCG_HIP(hipMemsetAsync(h->chip_zp, 0, (size_t)chip_zp_doubles(n) * sizeof(double), s));
+    DPCG_HIP(hipStreamSynchronize(s));
+    // one whole-chip launch at a time per process (see solve_team_one)
+    std::lock_guard<std::mutex> one_team_launch(team_launch_mutex());
+    static hipEvent_t ev0 = nullptr, ev1 = nullptr;                                  // DPCG_CHIP_EVENTS=1: as solve_chip_one
+    const char *ev_env = getenv("DPCG_CHIP_EVENTS");
+    const bool events = ev_env && ev_env[0] == '1';
+    if (events && !ev0) {
+        DPCG_HIP(hipEventCreate(&ev0));
+        DPCG_HIP(hipEventCreate(&ev1));
+    }
+    const auto t0 = std::chrono::steady_clock::now();                                // (the launch is the loop)
+    if (events) DPCG_HIP(hipEventRecord(ev0, s));
+    DPCG_TRY(launch_pcg_chip_sr(ds, h->planA.max_row_len, s));
+    if (events) DPCG_HIP(hipEventRecord(ev1, s));
+    DPCG_HIP(hipMemcpyAsync(h->scal_host, h->scal, sizeof(Scalars), hipMemcpyDeviceToHost, s));
+    DPCG_HIP(hipStreamSynchronize(s));
+    const auto t1 = std::chrono::steady_clock::now();
+    if (events) {
+        float ms = 0.0f;
+        DPCG_HIP(hipEventElapsedTime(&ms, ev0, ev1));
+        h->chip_trace_x[5] = (double)ms;
+    }
+    DPCG_CHECK_LAUNCH();
+    const Scalars sc = *h->scal_host;
+    if (sc.status < 0) {
+        co_residency().timed_out();
+        set_error("chip solve (single reduction): a workgroup waited (20 ms) for one that never became resident");
+        return sc.status;
+    }
+    co_residency().launched_fine();
+    h->last_recurrence = 1;
+    // this kernel has no phase timing: what dpcg_get_chip_info reports of an earlier traced standard solve is not this solve's
+    for (int i = 0; i < 8; ++i) h->chip_trace_us[i] = 0.0;
+    for (int i = 0; i < 5; ++i) h->chip_trace_x[i] = 0.0;
+    if (!events) h->chip_trace_x[5] = 0.0;
+    if (seconds) *seconds = std::chrono::duration<double>(t1 - t0).count();
+    if (iters) *iters = sc.k;
+    if (final_res) *final_res = sc.res;
+    bool pending = false;
+    if (res_history) {
+        DPCG_HIP(hipMemcpyAsync(res_history, h->hist, (size_t)(sc.k + 1) * sizeof(double), hipMemcpyDeviceToHost, s));
+        pending = true;
+    }
+    if (x && h->perm) launch_scatter_f64(n, h->perm, h->x, x, s);                    // back to the caller's numbering
+    if (pending) DPCG_HIP(hipStreamSynchronize(s));
+    return sc.status;
+}
+
 // M = L L^T multiplied (the learned technique, IC multiplied) beyond the one-workgroup kernel: the whole chip, L and L^T resident
 static const CsrDev &llt_l(const dpcg_system *h) { return h->perm ? h->Lp : h->L; }
 static const CsrDev &llt_t(const dpcg_system *h) { return h->perm ? h->Ltp : h->Lt; }
@@ -1318,6 +1438,12 @@ extern "C" int dpcg_get_chip_info(dpcg_handle_t h, int32_t out[8], double trace_
     return DPCG_OK;
 }
 
+extern "C" int dpcg_get_last_recurrence(dpcg_handle_t h, int *recurrence) {
+    if (!h || !recurrence) return invalid("dpcg_get_last_recurrence: NULL argument");
+    *recurrence = h->last_recurrence;
+    return DPCG_OK;
+}
+
 static int check_solve_args(dpcg_handle_t h, const double *b, int max_iter, int flags, const double *x_true,
                             double *err_history) {
     if (!h || !b) return invalid("dpcg_solve: NULL handle or b");
@@ -1335,6 +1461,20 @@ extern "C" int dpcg_solve(dpcg_handle_t h, const double *b, const double *x0, do
                           double *err_history) {
     DPCG_TRY(check_solve_args(h, b, max_iter, flags, x_true, err_history));
     const bool one_launch_open = co_residency().open();      // (false during the cool-down after repeated co-residency timeouts)
+    if (flags & DPCG_SINGLE_REDUCTION) {
+        if (const char *why = chip_sr_refusal(h, flags, x_true)) return invalid(why);     // (nothing of the handle has been touched)
+    }
+    h->last_recurrence = 0;
+    if (flags & DPCG_SINGLE_REDUCTION) {
+        if (one_launch_open) {
+            const int st = solve_chip_sr_one(h, b, x0, x, rtol_sq, atol_sq, max_iter, flags, (hipStream_t)stream, iters, final_res,
+                                             seconds, res_history);
+            if (st != DPCG_ERR_STATE) return st;
+        }
+        // the workgroups never became co-resident: the launches, with the standard recurrence (dpcg_get_last_recurrence says so)
+        // (DPCG_TEAM would take the standard whole-chip kernel "whatever the other flags say" and wait out a second 20 ms: cleared too)
+        flags = (flags & ~(DPCG_SINGLE_REDUCTION | DPCG_TEAM)) | DPCG_NO_SMALL;
+    }
     const bool team_first = one_launch_open && team_eligible(h, flags, x_true) && ((flags & DPCG_TEAM) || single_team_default(h, flags));
     if (small_eligible(h, flags, x_true) && !team_first)
         return solve_small_one(h, b, x0, x, rtol_sq, atol_sq, max_iter, flags, (hipStream_t)stream, iters, final_res,
@@ -1388,6 +1528,31 @@ extern "C" int dpcg_solve_batch(int count, dpcg_handle_t *handles, const double 
     if (n_streams > 8) n_streams = 8;
     if (n_streams > count) n_streams = count;
     for (int i = 0; i < count; ++i) DPCG_TRY(check_solve_args(handles[i], b[i], max_iter, flags, nullptr, nullptr));
+    if (flags & DPCG_SINGLE_REDUCTION) {
+        for (int i = 0; i < count; ++i)
+            if (const char *why = chip_sr_refusal(handles[i], flags, nullptr)) return invalid(why);     // (nothing of any handle has been touched)
+    }
+    // every form below runs the standard recurrence; the single-reduction members set their own word (dpcg_get_last_recurrence)
+    for (int i = 0; i < count; ++i) handles[i]->last_recurrence = 0;
+    if (flags & DPCG_SINGLE_REDUCTION) {
+        // the flag holds for every system as it does for a single solve: refused when one is not eligible, else one whole-chip launch
+        // after the other (a member that cannot become co-resident goes through the launches with the standard recurrence)
+        int worst_sr = DPCG_OK;
+        for (int i = 0; i < count; ++i) {
+            int it = 0;
+            double fr = 0.0, sec = 0.0;
+            const int st = dpcg_solve(handles[i], b[i], x0 ? x0[i] : nullptr, x ? x[i] : nullptr, rtol_sq, atol_sq, max_iter, flags, nullptr,
+                                      &it, &fr, &sec, nullptr, nullptr, nullptr);
+            if (st < 0) return st;
+            if (iters) iters[i] = it;
+            if (final_res) final_res[i] = fr;
+            if (seconds) seconds[i] = sec;
+            if (status) status[i] = st;
+            worst_sr = std::max(worst_sr, st);
+        }
+        DPCG_HIP(hipStreamSynchronize(nullptr));
+        return worst_sr;
+    }
     {   // a handle owns ONE set of work vectors: the same handle twice would share them across streams
         std::vector<dpcg_handle_t> sorted(handles, handles + count);
         std::sort(sorted.begin(), sorted.end());

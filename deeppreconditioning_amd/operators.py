@@ -579,6 +579,7 @@ class SolveResult:
     seconds: float       # wall time of the iteration loop, device-synchronised (cg.py:69,88)
     res_history: np.ndarray
     err_history: np.ndarray | None = None
+    recurrence: str = "standard"   # the recurrence that RAN: "single_reduction" only when asked for and the whole-chip kernel took it
 
 
 @dataclass
@@ -857,12 +858,22 @@ class CsrSystem:
         return float(ms.value)
 
     def solve(self, b, x0=None, *, rtol_sq: float = 1e-8, atol_sq: float = 0.0, max_iter: int = 1024, flags: int = 0,
-              x_true=None, want_history: bool = True, guess: "ProjectedGuess | None" = None) -> SolveResult:
+              x_true=None, want_history: bool = True, guess: "ProjectedGuess | None" = None,
+              recurrence: str = "standard") -> SolveResult:
         """Run the PCG loop of cg.py:58-90 on the GPU (see dpcg_solve in include/dpcg.h).
+
+        `recurrence="single_reduction"` (DPCG_SINGLE_REDUCTION): Chronopoulos and Gear's form of CG in the whole-chip kernel -- one
+        chip-wide exchange an update instead of two, other bits than the reference's recurrence.  M = I or Jacobi, fp64, systems the
+        resident whole-chip form takes; anything else raises DpcgError (ERR_INVALID) with the reason.  `SolveResult.recurrence` names
+        the recurrence that ran ("standard" when the kernel could not become co-resident and the launches took over).
 
         `guess` (a `ProjectedGuess` of this system): the solve starts from the projection of b onto the span of the earlier
         solutions and hands its own solution to the guess afterwards (a capped solve too; a breakdown does not).  Not together
         with `x0`."""
+        if recurrence not in L.RECURRENCES:
+            raise ValueError(f"recurrence must be one of {L.RECURRENCES}, not {recurrence!r}")
+        if recurrence == "single_reduction":
+            flags = int(flags) | L.SINGLE_REDUCTION
         bv = self._vec(b)
         if guess is not None:
             if x0 is not None:
@@ -886,8 +897,10 @@ class CsrSystem:
         k = iters.value
         if guess is not None and status != L.BREAKDOWN:
             guess.update(x)
+        ran = C.c_int(0)
+        L.check(L.lib().dpcg_get_last_recurrence(self._h, C.byref(ran)))
         return SolveResult(x, k, status, res.value, sec.value, hist[: k + 1] if hist is not None else np.empty(0),
-                           err[: k + 1] if err is not None else None)
+                           err[: k + 1] if err is not None else None, L.RECURRENCES[ran.value])
 
     def amg_hierarchy(self) -> AmgHierarchy:
         """The smoothed-aggregation hierarchy of the attached `SmoothedAggregation` preconditioner (DpcgError otherwise)."""

@@ -75,8 +75,24 @@ enum dpcg_solve_flags {
                                 x += alpha p (cg.py:79); same arithmetic, bit-identical results              */
     DPCG_NO_TEAM = 64,       /* do not use the one-launch whole-solve kernel for mid-size systems (6 145 .. 65 536 rows,
                                 M = I or Jacobi: a team of 32 workgroups per system, up to eight systems per launch) */
-    DPCG_TEAM = 128          /* use that kernel whatever the other flags say (it serves one system and batches by default:
+    DPCG_TEAM = 128,         /* use that kernel whatever the other flags say (it serves one system and batches by default:
                                 5.0-9.3 us per update against 9.6-14.6 for the launches; eight teams together 4.4x their rate) */
+    DPCG_SINGLE_REDUCTION = 256  /* opt-in: the single-synchronisation recurrence of Chronopoulos and Gear (1989) in the whole-chip
+                                kernel (dpcg_chip_sr.hip) -- ONE chip-wide exchange an update instead of two.  M = I or Jacobi, fp64:
+                                  r0 = b - A x0; z0 = dinv o r0 (M = I: z = r); p = q = 0
+                                  k = 0, 1, ...: s = A z_k; gamma = <r,z>, delta = <z,s>, rho = <r,r> summed together (the first
+                                    test on <z0,z0> unless DPCG_INIT_CHECK_R); history[k] = rho / <b,b> and the test of cg.py:71;
+                                    stop -> count = k;  beta = gamma / gamma_prev (beta_0 = 0);
+                                    den = delta - (beta * gamma) / alpha_prev (k = 0: delta); alpha = gamma / den;
+                                    p = z + beta p; q = s + beta q; x += alpha p; r -= alpha q; z = dinv o r
+                                den equals <p,Ap> in exact arithmetic and, like the standard kernel's <p,Ap>, is not examined: a NaN
+                                residual ends the solve with DPCG_BREAKDOWN, anything else runs to max_iter.  Count, history and
+                                status keep their meaning; the bits differ from the standard recurrence's.  Taken only where the
+                                resident fp64 whole-chip form is (65 537 .. 1 048 576 rows, rows of <= 7 entries -- <= 5 beyond 524 288 rows -- within 32 767
+                                columns of the diagonal, no x_true, not with DPCG_SPMV_F32 / DPCG_NO_SMALL / DPCG_NO_GRAPH /
+                                DPCG_NO_TEAM / DPCG_NO_FUSE): anything else is refused with DPCG_ERR_INVALID and a message that
+                                names the reason.  When the workgroups cannot become co-resident the call solves through the
+                                launches with the STANDARD recurrence; dpcg_get_last_recurrence says which one ran. */
 };
 
 /* ---- library ------------------------------------------------------------------------------- */
@@ -349,8 +365,12 @@ int dpcg_get_reduction_geometry(dpcg_handle_t h, int32_t out[16]);
  * the environment, microseconds per update that workgroup 0 spent in the phases of the last chip solve -- [0] q = A p (the SpMV
  * phase), [1] sum <p,Ap> incl. its barrier, [2] vector updates + publishing, [3] sum <r,z>, <r,r> incl. its barrier, [4] the whole
  * loop, [5] / [6] of [1] / [3]: waiting for the other workgroups' slots, [7] = the number of updates.  No reference counterpart
- * (the reference's loop is host Python, cg.py:70-87). */
+ * (the reference's loop is host Python, cg.py:70-87).  A DPCG_SINGLE_REDUCTION solve has no phase timing: it zeroes trace_us and
+ * bit 0 of out[6], and out[7] unless DPCG_CHIP_EVENTS=1 measured that kernel. */
 int dpcg_get_chip_info(dpcg_handle_t h, int32_t out[8], double trace_us[8]);
+/* The recurrence the handle's last dpcg_solve / dpcg_solve_batch member ran: 0 = the standard one (cg.py:70-87), 1 = the
+ * single-reduction one (DPCG_SINGLE_REDUCTION).  0 before the first solve.  No reference counterpart. */
+int dpcg_get_last_recurrence(dpcg_handle_t h, int *recurrence);
 /* Test hook: enqueue on `stream` a kernel of `workgroups` workgroups that each take a whole CU (all of its LDS) and spin for
  * `milliseconds` -- what a long-running kernel of another stream or process does to the co-residency the one-launch solves (team,
  * chip) rely on.  They bound every wait (20 ms) and fall back to the multi-launch path; the tests hold them to that with this call.
