@@ -1,6 +1,8 @@
-// Host-side internals shared by dpcg_api.hip, dpcg_precond.hip and dpcg_solve.hip (not part of the ABI).
+// Host-side internals shared by dpcg_api.hip, dpcg_precond.hip, dpcg_solve.hip and dpcg_solve_chip.hip (not part of the ABI).
 #pragma once
 
+#include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -131,6 +133,59 @@ int apply_precond(dpcg_system *h, const double *r, double *z, hipStream_t s, boo
 // number of <r,z> partials an in-loop apply of the handle's preconditioner leaves (vec_grid when it leaves none)
 int rz_partial_count(const dpcg_system *h);
 int check_spin_errors(dpcg_system *h, hipStream_t s);
+
+// ---- the one-launch forms (dpcg_solve.hip: one workgroup, one team; dpcg_solve_chip.hip: the whole chip) --------------------------------
+bool device_has_cus(int cus);
+std::mutex &team_launch_mutex();          // one team / whole-chip launch at a time per process
+// Back-off of the one-launch forms (one workgroup team / whole chip): they assume that all of their workgroups become co-resident, and
+// a launch that cannot (RCCL kernels or another process holding CUs, a long kernel on another stream) spins for the full 20 ms bound
+// before the call goes on through the launches.  Three such timeouts in a row and the one-launch forms are skipped for a cool-down
+// (2 s, doubling up to 32 s while the re-probes keep failing); a launch that completes clears it.  One warning per process.
+struct CoResidency {
+    std::atomic<int> misses{0};
+    std::atomic<long long> closed_until_ns{0};
+    std::atomic<int> cooldown_s{2};
+    std::atomic<bool> warned{false};
+    static long long now_ns() { return std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+    bool open() const { return now_ns() >= closed_until_ns.load(std::memory_order_relaxed); }
+    void launched_fine() {
+        misses.store(0, std::memory_order_relaxed);
+        cooldown_s.store(2, std::memory_order_relaxed);
+    }
+    void timed_out() {
+        if (misses.fetch_add(1, std::memory_order_relaxed) + 1 < 3) return;
+        const int cd = cooldown_s.load(std::memory_order_relaxed);
+        closed_until_ns.store(now_ns() + (long long)cd * 1000000000ll, std::memory_order_relaxed);
+        cooldown_s.store(std::min(2 * cd, 32), std::memory_order_relaxed);
+        misses.store(2, std::memory_order_relaxed);            // (the re-probe after the cool-down closes it again at its first timeout)
+        if (!warned.exchange(true))
+            fprintf(stderr, "[dpcg] the one-launch solve kernels could not become co-resident three times in a row (somebody else holds CUs): "
+                            "solving through the multi-launch path, re-probing every %d s and up\n", cd);
+    }
+};
+CoResidency &co_residency();
+// which systems take a whole-chip form, whether a plain call does, and why DPCG_SINGLE_REDUCTION cannot be honoured (nullptr: it can)
+bool chip_eligible(const dpcg_system *h, int flags, const double *x_true);
+bool chip_llt_eligible(const dpcg_system *h, int flags, const double *x_true);
+bool chip_trsv_shape(const dpcg_system *h, int flags, const double *x_true);
+bool chip_default(const dpcg_system *h, int flags);
+const char *chip_sr_refusal(const dpcg_system *h, int flags, const double *x_true);
+void free_chip_trsv(dpcg_system *h);               // the plan of the triangular-solve form (goes with the preconditioner)
+// one solve as dpcg_solve takes it (b, x0 and x in the caller's numbering; the last four may be null)
+struct SolveCall {
+    const double *b, *x0;
+    double *x;
+    double rtol_sq, atol_sq;
+    int max_iter, flags;
+    hipStream_t s;
+    int *iters;
+    double *final_res, *seconds, *res_history;
+};
+// ... by a whole-chip form; DPCG_ERR_STATE: not taken (refused up front, or never co-resident), the caller goes on with the launches
+int solve_chip_one(dpcg_system *h, SolveCall c);          // M = I / Jacobi
+int solve_chip_sr_one(dpcg_system *h, SolveCall c);       // ... with the single-reduction recurrence
+int solve_chip_llt_one(dpcg_system *h, SolveCall c);      // M = L L^T multiplied
+int solve_chip_trsv_one(dpcg_system *h, SolveCall c);     // M = (L L^T)^-1 by two triangular solves
 // dpcg_amg.hip: the smoothed-aggregation hierarchy -- free, launches of one V-cycle, sum over levels of nnz(A_l) + 2 nnz(P_l), the apply
 // (part_rz: the last kernel leaves the partials of <r, z>), and how many partials an in-loop apply leaves (0: none)
 void free_amg(AmgState *&S);
