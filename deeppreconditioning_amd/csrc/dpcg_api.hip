@@ -191,9 +191,17 @@ int make_plan(const CsrDev &A, SpmvPlan &plan, hipStream_t s, bool allow_tile) {
         launch_band_and_len(A, d_bl, s);
         DPCG_HIP(hipMemcpyAsync(h_bl, d_bl, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
         DPCG_HIP(hipStreamSynchronize(s));
-        dev_free(d_bl);
         plan.max_band = h_bl[0];
         plan.max_row_len = h_bl[1];
+        if (h_bl[1] >= 1 && h_bl[1] <= 9 && h_bl[0] <= chip_max_band()) {     // a shape the resident chip kernel may take: which of its two products
+            DPCG_HIP(hipMemsetAsync(d_bl, 0, 2 * sizeof(int), s));
+            launch_centred_pairs(A, h_bl[1], d_bl, s);
+            DPCG_HIP(hipMemcpyAsync(h_bl, d_bl, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
+            DPCG_HIP(hipStreamSynchronize(s));
+            plan.chip_centred_pairs = h_bl[0];
+            plan.chip_pairs = h_bl[1];
+        }
+        dev_free(d_bl);
     }
     dev_free(d_max);
     const char *force = getenv("DPCG_SPMV_KERNEL");

@@ -52,7 +52,9 @@ using namespace chip;
 namespace {
 
 // RPT: rows per thread (2, 4, 8); WMAX: entry slots per row (5, 7; 9 up to four rows a thread: unstructured meshes); JAC: M = diag(1 / a_ii) (else M = I: z = r, no dinv registers).
-template <int RPT, int WMAX, bool JAC, int MODE>
+// CEN: the instantiation whose product takes same-wave operands from registers (rows stored around a centre, below); without it the
+// kernel has the packed layout alone and no branch in its product.  The host chooses per system (solve_chip_one).
+template <int RPT, int WMAX, bool JAC, int MODE, bool CEN>
 __global__ __launch_bounds__(kChipThreads) void k_pcg_chip(const ChipDesc d) {
     constexpr bool TRACE = MODE == 1;      // (development -- MODE 2: q = p instead of the gathers, the loop never stops before max_iter; MODE 3: the gathers
                                            // issued, but every one out of range: no memory request, zeros returned)
@@ -91,7 +93,10 @@ __global__ __launch_bounds__(kChipThreads) void k_pcg_chip(const ChipDesc d) {
     // ---- the matrix slice and the vectors of the own rows: read once ------------------------------------------------------
     double vr[NREG > 0 ? NREG : 1];
     unsigned dl[(NS + 1) / 2];
-    constexpr int LB = WMAX > 7 ? 8 : 4;    // bits per row in `lens`: the top one = the row exists, below it the length
+    // bits per row in `lens`: the top one = the row exists, below it the length -- or, for a row stored around a centre (below), what its
+    // slots hold: entries before the centre (2 bits), the row - 1 entry (bit 2), the row + 1 entry (bit 3), entries behind it (bits 4-5)
+    constexpr bool CENTRE = CEN && !STREAM;
+    constexpr int LB = CENTRE ? 8 : (WMAX > 7 ? 8 : 4);
     constexpr unsigned LV = 1u << (LB - 1), LM = LV - 1u;
     static_assert(LB * RPT <= 64, "row lengths of a thread in one or two registers");
     typedef typename std::conditional<(LB * RPT > 32), unsigned long long, unsigned>::type lens_t;
@@ -118,26 +123,98 @@ __global__ __launch_bounds__(kChipThreads) void k_pcg_chip(const ChipDesc d) {
         p[k] = q[k] = 0.0;
         if (JAC) dv[k] = valid ? di : 1.0;
     }
+    // ---- rows stored around a CENTRE.  Consecutive lanes own consecutive rows: the operand of a row's diagonal entry is the lane's own
+    // p[k], those of its row -+ 1 entries are p[k] of the lanes beside it -- the owner's bits, in registers of this very wave.  A row whose
+    // entries, in the order the caller stored them, read A.., [row - 1], row, [row + 1], B.. (at most jS - 1 of A, WMAX - jS - 2 of B) keeps
+    // A from slot 0, row - 1 / row / row + 1 in slots jS - 1 / jS / jS + 1 and B from slot jS + 2; the slots between are holes (no entry:
+    // never summed).  The sum still runs in the row's own order.  Where EVERY existing row of a wave's slot-row k is such a row (a vote,
+    // once per solve: bit k of `cmask`, the same for the whole wave), the product takes those three operands from registers and gathers
+    // the others; any other (wave, k) keeps the packed layout and gathers everything.  The column field of slot jS is free then and says
+    // what the lane asks of the EDGE gather: lane 0's row - 1 and the last existing lane's row + 1 lie outside the wave (32 767 / 32 769:
+    // the granule of that column; 0: nothing).  A slot-row with ONE existing row would need both of one gather and stays packed.
+    // (One decision per WAVE and two straight-line products instead of a branch per slot-row was built and measured: slower on both
+    // paths)
+    // (MODE 3 with CEN: the loads that are still issued go out of range, the shared operands are taken as in MODE 0)
+    constexpr int jS = WMAX / 2;
+    unsigned cmask = 0;
+    int jd_k[RPT];
+    if (CENTRE) {
+        unsigned exists = 0;
+#pragma unroll
+        for (int k = 0; k < RPT; ++k) {
+            const int i = row0 + k * kChipThreads, len = len_k[k];
+            const bool valid = ((unsigned)(lens >> (LB * k)) & LV) != 0;
+            int cj[WMAX];
+#pragma unroll
+            for (int j = 0; j < WMAX; ++j) cj[j] = d.ci[j < len ? rs_k[k] + j : 0];
+            int jd = WMAX;                                         // the first entry on the diagonal
+#pragma unroll
+            for (int j = WMAX - 1; j >= 0; --j)
+                if (j < len && cj[j] == i) jd = j;
+            bool has_l = false, has_r = false;
+#pragma unroll
+            for (int j = 0; j < WMAX; ++j) {
+                if (j + 1 == jd && cj[j] == i - 1) has_l = true;
+                if (j == jd + 1 && j < len && cj[j] == i + 1) has_r = true;
+            }
+            const int n_a = jd - (has_l ? 1 : 0), n_b = len - jd - 1 - (has_r ? 1 : 0);
+            const bool fits = valid && jd < WMAX && n_a <= jS - 1 && n_b <= WMAX - jS - 2;
+            const unsigned long long rows = __ballot(valid);
+            const bool centred = d.shared && __ballot(valid && !fits) == 0ull && __popcll(rows) != 1;
+            if (rows != 0ull) exists |= 1u << k;
+            jd_k[k] = jd;
+            if (centred) {
+                cmask |= 1u << k;
+                const unsigned what = valid ? (unsigned)n_a | (has_l ? 4u : 0u) | (has_r ? 8u : 0u) | (unsigned)n_b << 4 : 0u;
+                lens = (lens & ~((lens_t)LM << (LB * k))) | (lens_t)what << (LB * k);
+            }
+        }
+        cmask = (unsigned)__builtin_amdgcn_readfirstlane((int)cmask);
+        // (what dpcg_get_chip_info reports: per wave, the slot-rows on the centred path | those with a row at all << 8)
+        if (d.shared_out && (t & 63) == 0) d.shared_out[v * (kChipThreads / 64) + (t >> 6)] = __popc(cmask & exists) | __popc(exists) << 8;
+    }
+    if (!CENTRE && !STREAM && d.shared_out) {                    // (the packed instantiation reports its slot-rows alike: none of them centred)
+        unsigned exists = 0;
+#pragma unroll
+        for (int k = 0; k < RPT; ++k)
+            if (__ballot(((unsigned)(lens >> (LB * k)) & LV) != 0) != 0ull) exists |= 1u << k;
+        if ((t & 63) == 0) d.shared_out[v * (kChipThreads / 64) + (t >> 6)] = __popc(exists) << 8;
+    }
 #pragma unroll
     for (int k = 0; k < RPT; ++k) {
         if ((unsigned)(lens >> (LB * k)) & LV) bb_loc += r[k] * r[k];
         if (STREAM) continue;
         const int i = row0 + k * kChipThreads;
+        const bool centred = CENTRE && ((cmask >> k) & 1u);
+        const unsigned what = (unsigned)(lens >> (LB * k)) & LM;
+        const int has_l = (what >> 2) & 1, has_r = (what >> 3) & 1;
+        int src[WMAX];                                             // the entry of the row that slot j holds (beyond the row: a hole)
         int cj[WMAX];
         double aj[WMAX];
 #pragma unroll
         for (int j = 0; j < WMAX; ++j) {
-            const int e = j < len_k[k] ? rs_k[k] + j : 0;          // (entry 0 exists: nnz >= n >= 1)
+            src[j] = j;
+            if (centred) {
+                if (j < jS - 1) src[j] = j < (int)(what & 3u) ? j : WMAX;
+                else if (j == jS - 1) src[j] = has_l ? jd_k[k] - 1 : WMAX;
+                else if (j == jS) src[j] = jd_k[k];
+                else if (j == jS + 1) src[j] = has_r ? jd_k[k] + 1 : WMAX;
+                else src[j] = j - jS - 2 < (int)((what >> 4) & 3u) ? jd_k[k] + 1 + has_r + (j - jS - 2) : WMAX;
+            }
+            const int e = src[j] < len_k[k] ? rs_k[k] + src[j] : 0;          // (entry 0 exists: nnz >= n >= 1)
             cj[j] = d.ci[e];
             aj[j] = d.val[e];
         }
+        // the edge gather of a centred slot-row: lane 0 asks for row - 1, the last existing lane of the wave for row + 1
+        const bool last = (t & 63) == 63 || !(k * kChipThreads + t + 1 < d.per && i + 1 < d.n);
+        const unsigned edge = ((t & 63) == 0 && has_l) ? 32767u : ((last && has_r) ? 32769u : 0u);
 #pragma unroll
         for (int j = 0; j < WMAX; ++j) {
             const int s = k * WMAX + j;
-            const bool on = j < len_k[k];
+            const bool on = src[j] < len_k[k];
             const int c = on ? cj[j] : i;
             const double a = on ? (F32 ? (double)(float)aj[j] : aj[j]) : 0.0;
-            const unsigned del = (unsigned)(c - i + 32768) & 0xffffu;
+            const unsigned del = (centred && j == jS) ? edge : (unsigned)(c - i + 32768) & 0xffffu;
             if (s & 1) dl[s >> 1] |= del << 16;
             else dl[s >> 1] = del;
             if (s < NREG) vr[s < NREG ? s : 0] = a;
@@ -169,14 +246,39 @@ __global__ __launch_bounds__(kChipThreads) void k_pcg_chip(const ChipDesc d) {
         asm volatile("" : "+v"(lens));       // (and the 56 `j < len` lane masks)
         auto request = [&](int k, u32x4 (&gk)[WMAX]) {
             const int rowk = row0 + k * kChipThreads;
+            if (CENTRE && ((cmask >> k) & 1u)) {                   // (the same for the whole wave) centred: WMAX - 3 gathers and the edge gather
 #pragma unroll
-            for (int j = 0; j < WMAX; ++j) {
-                const int s = k * WMAX + j;
-                const int del = (int)((dl[s >> 1] >> (16 * (s & 1))) & 0xffffu);
-                const int c = rowk + del - 32768;
-                const bool own = (unsigned)(c - glo_l) < (unsigned)span_l;              // the column's owner is in this group: the plain copy
-                gk[j] = __builtin_amdgcn_raw_buffer_load_b128(zp_rs, MODE == 3 ? (int)0x7ffffff0 : c * 16 + (own ? local_shift : remote_base), 0, kSc1);
+                for (int j = 0; j < WMAX; ++j) {
+                    if (j == jS - 1 || j == jS + 1) continue;
+                    const int s = k * WMAX + j;
+                    const int del = (int)((dl[s >> 1] >> (16 * (s & 1))) & 0xffffu);
+                    const int c = rowk + del - 32768;
+                    const bool own = (unsigned)(c - glo_l) < (unsigned)span_l;
+                    int off = c * 16 + (own ? local_shift : remote_base);
+                    if (j == jS) off = del == 0 ? (int)0x7ffffff0 : off;            // a lane inside the wave asks for nothing: out of range, zeros
+                    gk[j] = __builtin_amdgcn_raw_buffer_load_b128(zp_rs, MODE == 3 ? (int)0x7ffffff0 - 16 * j : off, 0, kSc1);
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < WMAX; ++j) {
+                    const int s = k * WMAX + j;
+                    const int del = (int)((dl[s >> 1] >> (16 * (s & 1))) & 0xffffu);
+                    const int c = rowk + del - 32768;
+                    const bool own = (unsigned)(c - glo_l) < (unsigned)span_l;              // the column's owner is in this group: the plain copy
+                    gk[j] = __builtin_amdgcn_raw_buffer_load_b128(zp_rs, MODE == 3 ? (int)0x7ffffff0 : c * 16 + (own ? local_shift : remote_base), 0, kSc1);
+                }
             }
+        };
+        // the value of the lane below / above (DPP wave_shr:1 / wave_shl:1); lane 0 / lane 63 have none and keep `edge`
+        auto from_lane_below = [](double val, double edge) -> double {
+            const int lo = __builtin_amdgcn_update_dpp(__double2loint(edge), __double2loint(val), 0x138, 0xf, 0xf, false);
+            const int hi = __builtin_amdgcn_update_dpp(__double2hiint(edge), __double2hiint(val), 0x138, 0xf, 0xf, false);
+            return __hiloint2double(hi, lo);
+        };
+        auto from_lane_above = [](double val, double edge) -> double {
+            const int lo = __builtin_amdgcn_update_dpp(__double2loint(edge), __double2loint(val), 0x130, 0xf, 0xf, false);
+            const int hi = __builtin_amdgcn_update_dpp(__double2hiint(edge), __double2hiint(val), 0x130, 0xf, 0xf, false);
+            return __hiloint2double(hi, lo);
         };
         request(0, g[0]);
 #pragma unroll
@@ -185,19 +287,49 @@ __global__ __launch_bounds__(kChipThreads) void k_pcg_chip(const ChipDesc d) {
             __builtin_amdgcn_sched_barrier(0);                     // (keeps the scheduler from hoisting every row's gathers to the top:
             const int len = (int)((unsigned)(lens >> (LB * k)) & LM);        //  two rows' granules in flight is what the registers hold)
             double acc = 0.0;
+            if (CENTRE && ((cmask >> k) & 1u)) {
+                // p[k] IS p_k of the own row: cg.py:83 as its owner evaluated it, which the gather only repeats.  (Two places where a
+                // gather would give other bits: the product with x0 runs with p[k] = x0, see there; and in the first update p[k] = z_0
+                // where the granule gives z_0 + 0 * 0, which differs for z_0 = -0.0 alone -- the sign of a zero product, and acc, which
+                // starts at +0.0, is the same sum with either.)
+                const double mine = F32 ? (double)(float)p[k] : p[k];
+                const double e64 = lo_f64(g[k & 1][jS]) + beta * hi_f64(g[k & 1][jS]);
+                const double edge = F32 ? (double)(float)e64 : e64;
+                const int s_c = k * WMAX + jS;
+                const bool edge_above = ((dl[s_c >> 1] >> (16 * (s_c & 1))) & 0xffffu) == 32769u;
+                const double below = from_lane_below(mine, edge);
+                const double above_w = from_lane_above(mine, edge);
+                const double above = edge_above ? edge : above_w;     // (the last existing lane of a wave that is not full)
 #pragma unroll
-            for (int j = 0; j < WMAX; ++j) {
-                const int s = k * WMAX + j;
-                const double a = s < NREG ? vr[s < NREG ? s : 0] : (F32_SLOTS ? (double)lft[(s - NREG) * kChipThreads] : lvt[(s - NREG) * kChipThreads]);
-                const double pc64 = lo_f64(g[k & 1][j]) + beta * hi_f64(g[k & 1][j]);  // = p_k[c], cg.py:83
-                const double pc = F32 ? (double)(float)pc64 : pc64;
-                if (j < len) acc += a * pc;
+                for (int j = 0; j < WMAX; ++j) {
+                    const int s = k * WMAX + j;
+                    const double a = s < NREG ? vr[s < NREG ? s : 0] : (F32_SLOTS ? (double)lft[(s - NREG) * kChipThreads] : lvt[(s - NREG) * kChipThreads]);
+                    double pc;
+                    bool on;
+                    if (j == jS - 1) { pc = below; on = (len & 4) != 0; }
+                    else if (j == jS) { pc = mine; on = row_on(k); }
+                    else if (j == jS + 1) { pc = above; on = (len & 8) != 0; }
+                    else {
+                        const double pc64 = lo_f64(g[k & 1][j]) + beta * hi_f64(g[k & 1][j]);
+                        pc = F32 ? (double)(float)pc64 : pc64;
+                        on = j < jS ? j < (len & 3) : j - jS - 2 < ((len >> 4) & 3);
+                    }
+                    if (on) acc += a * pc;
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < WMAX; ++j) {
+                    const int s = k * WMAX + j;
+                    const double a = s < NREG ? vr[s < NREG ? s : 0] : (F32_SLOTS ? (double)lft[(s - NREG) * kChipThreads] : lvt[(s - NREG) * kChipThreads]);
+                    const double pc64 = lo_f64(g[k & 1][j]) + beta * hi_f64(g[k & 1][j]);  // = p_k[c], cg.py:83
+                    const double pc = F32 ? (double)(float)pc64 : pc64;
+                    if (j < len) acc += a * pc;
+                }
             }
             q[k] = acc;
             __builtin_amdgcn_sched_barrier(0);
         }
     };
-
     // ---- MODE 5: the streamed product, wave by wave: the 64 rows a wave owns in a slot are 64 CONSECUTIVE rows, their entries one
     // contiguous run of col / val.  Lane l takes entry e0 + l, gathers the granule of its column, parks value x p in the WAVE's part
     // of the LDS, and then adds its own row's products in column order.  No workgroup barrier: the eight waves run their slots
@@ -400,7 +532,15 @@ __global__ __launch_bounds__(kChipThreads) void k_pcg_chip(const ChipDesc d) {
         alive = chip_sum2(0.0, 0.0, true, dummy, dummy2);
         if (alive) {
             if (STREAM) spmv_stream(0.0);
-            else spmv(0.0);
+            else {
+                // (the granules hold {x0, 0}: the operands that the centred path takes from p[k] are x0 of the own rows.  x0 = -0.0 is
+                // +0.0 in the granule's x0 + 0 * 0: the sign of a zero product again)
+#pragma unroll
+                for (int k = 0; k < RPT; ++k) p[k] = x[k];
+                spmv(0.0);
+#pragma unroll
+                for (int k = 0; k < RPT; ++k) p[k] = 0.0;
+            }
 #pragma unroll
             for (int k = 0; k < RPT; ++k) r[k] = r[k] - q[k];
             alive = chip_sum2(0.0, 0.0, false, dummy, dummy2);    // everybody has read x0 out of the granules before z_0 overwrites them
@@ -542,7 +682,7 @@ __global__ __launch_bounds__(kBlock) void k_band_and_len(int64_t n, const int32_
     }
 }
 
-template <int RPT, int WMAX, bool JAC, int MODE>
+template <int RPT, int WMAX, bool JAC, int MODE, bool CEN = false>
 int chip_launch(const ChipDesc &d, hipStream_t s, bool check_only) {
     constexpr int NS = RPT * WMAX;
     constexpr int kLdsCap = MODE == 4 ? 2 * kChipLdsSlots : kChipLdsSlots;        // (MODE 4: 4-byte value slots)
@@ -554,17 +694,17 @@ int chip_launch(const ChipDesc &d, hipStream_t s, bool check_only) {
     const int lds_attr = (MODE == 5 || MODE == 6) ? lds_max5 : lds;
     static int resident = -1;              // workgroups the occupancy query admits per CU (once per instantiation)
     if (resident < 0) {
-        if (hipFuncSetAttribute((const void *)k_pcg_chip<RPT, WMAX, JAC, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_attr) != hipSuccess)
+        if (hipFuncSetAttribute((const void *)k_pcg_chip<RPT, WMAX, JAC, MODE, CEN>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_attr) != hipSuccess)
             return DPCG_ERR_HIP;
         int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_pcg_chip<RPT, WMAX, JAC, MODE>, kChipThreads, (size_t)lds_attr) !=
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_pcg_chip<RPT, WMAX, JAC, MODE, CEN>, kChipThreads, (size_t)lds_attr) !=
             hipSuccess)
             return DPCG_ERR_HIP;
         resident = per_cu;
     }
     if (resident < 1) return DPCG_ERR_STATE;       // the kernel does not fit a CU: refused up front
     if (check_only) return DPCG_OK;
-    hipLaunchKernelGGL((k_pcg_chip<RPT, WMAX, JAC, MODE>), dim3(kChipWGs), dim3(kChipThreads), (size_t)lds, s, d);
+    hipLaunchKernelGGL((k_pcg_chip<RPT, WMAX, JAC, MODE, CEN>), dim3(kChipWGs), dim3(kChipThreads), (size_t)lds, s, d);
     return DPCG_OK;
 }
 
@@ -694,6 +834,40 @@ int chip_threads() { return kChipThreads; }
 int chip_slot_doubles() { return kChipSlotBytes / 8; }
 int64_t chip_zp_doubles(int64_t n) { return 4 * (n + kChipZpPad); }
 
+// (wave, slot-row) pairs of the chip kernel's geometry -- workgroup v owns rows [v per, (v + 1) per), a pair 64 consecutive ones of them --
+// whose rows are all stored around a centre and are more than one (the kernel's own vote, k_pcg_chip), and the pairs with a row at all:
+// what decides which instantiation a system takes.  One wave per pair.
+__global__ __launch_bounds__(kBlock) void k_centred_pairs(int n, int per, int wmax, const int32_t *__restrict__ rp, const int32_t *__restrict__ ci,
+                                                          int *out /* [0] centred pairs, [1] pairs */) {
+    const int per_wg = (per + 63) / 64;                          // pairs of a workgroup's rows
+    const int pair = (int)((blockIdx.x * (unsigned)kBlock + threadIdx.x) >> 6), lane = threadIdx.x & 63;
+    if (pair >= kChipWGs * per_wg) return;
+    const int v = pair / per_wg, loc = (pair % per_wg) * 64 + lane, i = v * per + loc;
+    const bool valid = loc < per && i < n;
+    bool fits = false;
+    if (valid) {
+        const int rs = rp[i], len = rp[i + 1] - rs, js = wmax / 2;
+        int jd = -1;
+        for (int j = len - 1; j >= 0; --j)
+            if (ci[rs + j] == i) jd = j;
+        if (jd >= 0) {
+            const int has_l = (jd >= 1 && ci[rs + jd - 1] == i - 1) ? 1 : 0, has_r = (jd + 1 < len && ci[rs + jd + 1] == i + 1) ? 1 : 0;
+            fits = jd - has_l <= js - 1 && len - jd - 1 - has_r <= wmax - js - 2;
+        }
+    }
+    const unsigned long long rows = __ballot(valid), bad = __ballot(valid && !fits);
+    if (lane == 0 && rows != 0ull) {
+        atomicAdd(&out[1], 1);
+        if (bad == 0ull && __popcll(rows) != 1) atomicAdd(&out[0], 1);
+    }
+}
+
+void launch_centred_pairs(const CsrDev &A, int max_row_len, int *out2_zeroed_dev, hipStream_t s) {
+    const int per = (int)((A.n + kChipWGs - 1) / kChipWGs), wmax = max_row_len <= 5 ? 5 : (max_row_len <= 7 ? 7 : 9);
+    const int pairs = kChipWGs * ((per + 63) / 64);
+    hipLaunchKernelGGL(k_centred_pairs, dim3((pairs * 64 + kBlock - 1) / kBlock), dim3(kBlock), 0, s, (int)A.n, per, wmax, A.rowptr, A.col, out2_zeroed_dev);
+}
+
 void launch_band_and_len(const CsrDev &A, int *out2_zeroed_dev, hipStream_t s) {
     int64_t g = (A.n + kBlock - 1) / kBlock;
     if (g > 512) g = 512;
@@ -723,11 +897,17 @@ int launch_pcg_chip(const ChipDesc &d, int max_row_len, hipStream_t s, bool chec
 #undef DPCG_CHIP_S2
 #undef DPCG_CHIP_S3
     }
-    const int mode = d.bench == 3 ? 3 : (d.bench ? 2 : (d.dbg != nullptr ? 1 : (d.f32 ? 4 : 0)));
+    // (DPCG_CHIP_BENCH=3: every entry's gather issued out of range, the packed layout -- what bench.py's phases subtract; =4: the same
+    // variant of the instantiation the system takes: with shared operands, only the loads that are still issued)
+    const int mode = (d.bench == 3 || d.bench == 4) ? 3 : (d.bench ? 2 : (d.dbg != nullptr ? 1 : (d.f32 ? 4 : 0)));
     if (max_row_len < 1 || max_row_len > ((rpt <= 4 || mode == 4) ? 9 : 7) || d.per < 1 || d.per > kChipThreads * kChipMaxRpt) return DPCG_ERR_INVALID;
     if (d.f32 && (mode != 4 || d.x0)) return DPCG_ERR_INVALID;
-    if (rpt > 4 && max_row_len > 7) return jac ? chip_launch<8, 9, true, 4>(d, s, check_only) : chip_launch<8, 9, false, 4>(d, s, check_only);   // (4-byte slots)
-#define DPCG_CHIP_T(RPTV, WV, JV) (mode == 4 ? chip_launch<RPTV, WV, JV, 4>(d, s, check_only) : mode == 3 ? chip_launch<RPTV, WV, JV, 3>(d, s, check_only) : mode == 2 ? chip_launch<RPTV, WV, JV, 2>(d, s, check_only) : (mode == 1 ? chip_launch<RPTV, WV, JV, 1>(d, s, check_only) : chip_launch<RPTV, WV, JV, 0>(d, s, check_only)))
+    const bool cen = d.shared != 0 && mode != 2 && mode != 1 && d.bench != 3;    // (the traced variant lives at the register limit as it is: packed)
+    if (rpt > 4 && max_row_len > 7)                               // (4-byte slots)
+        return jac ? (cen ? chip_launch<8, 9, true, 4, true>(d, s, check_only) : chip_launch<8, 9, true, 4>(d, s, check_only))
+                   : (cen ? chip_launch<8, 9, false, 4, true>(d, s, check_only) : chip_launch<8, 9, false, 4>(d, s, check_only));
+#define DPCG_CHIP_C(RPTV, WV, JV, MV) (cen ? chip_launch<RPTV, WV, JV, MV, true>(d, s, check_only) : chip_launch<RPTV, WV, JV, MV>(d, s, check_only))
+#define DPCG_CHIP_T(RPTV, WV, JV) (mode == 4 ? DPCG_CHIP_C(RPTV, WV, JV, 4) : mode == 3 ? DPCG_CHIP_C(RPTV, WV, JV, 3) : mode == 2 ? chip_launch<RPTV, WV, JV, 2>(d, s, check_only) : (mode == 1 ? chip_launch<RPTV, WV, JV, 1>(d, s, check_only) : DPCG_CHIP_C(RPTV, WV, JV, 0)))
 #define DPCG_CHIP_W(RPTV, WV) (jac ? DPCG_CHIP_T(RPTV, WV, true) : DPCG_CHIP_T(RPTV, WV, false))
 #define DPCG_CHIP_R(RPTV) (max_row_len <= 5 ? DPCG_CHIP_W(RPTV, 5) : DPCG_CHIP_W(RPTV, 7))
 #define DPCG_CHIP_R9(RPTV) (max_row_len <= 5 ? DPCG_CHIP_W(RPTV, 5) : (max_row_len <= 7 ? DPCG_CHIP_W(RPTV, 7) : DPCG_CHIP_W(RPTV, 9)))
@@ -738,6 +918,7 @@ int launch_pcg_chip(const ChipDesc &d, int max_row_len, hipStream_t s, bool chec
 #undef DPCG_CHIP_R9
 #undef DPCG_CHIP_W
 #undef DPCG_CHIP_T
+#undef DPCG_CHIP_C
 }
 
 }  // namespace dpcg

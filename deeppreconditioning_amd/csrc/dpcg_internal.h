@@ -59,6 +59,7 @@ struct SpmvPlan {
     int cyclic = 0;                    // x-tile kernel: row blocks dealt out cyclically (b, b + G, ...) instead of in slabs; 2: XCD runs inside a pass (see k_spmv_tile)
     int max_row_len = 0;               // longest row (the team / chip kernels keep rows of <= 7 entries on chip); systems of <= 1 048 576 rows
     int max_band = -1;                 // largest |col - row| (the chip kernel keeps columns as 16-bit offsets from the row); -1: not measured
+    int chip_pairs = 0, chip_centred_pairs = 0;   // the chip kernel's (wave, slot-row) pairs and those whose rows are all stored around a centre (resident shapes)
 };
 
 // Device-resident scalar state of one solve.  Only block 0 of a kernel writes it; everybody else
@@ -311,6 +312,7 @@ struct dpcg_system {
     int32_t *trsv_fcol = nullptr, *trsv_fmeta = nullptr;
     int trsv_rpt = 0, trsv_wmax = 0, trsv_band = 0, trsv_tstride = 512;
     int trsv_state = 0;
+    bool chip_shared_known = false;          // the last solve was a resident standard chip solve: its waves' counts of centred slot-rows are in chip_part
     double chip_trace_x[8] = {0, 0, 0, 0, 0, 0, 0, 0};    // ... over the 256 workgroups: SpMV phase max / mean, publish max / mean, `local`
     double chip_trace_us[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // DPCG_CHIP_TRACE: us per update by phase of the last chip solve ([7] = updates)
     dpcg::SmallEll ell_a, ell_m, ell_t;      // slab-ELL copies of A, M (or L), L^T for the small-system kernel
@@ -510,6 +512,9 @@ struct ChipDesc {
     double *part;              // chip_slot_doubles() doubles, all preset to the "pending" pattern at launch
     int *err;
     unsigned long long *dbg;   // DPCG_CHIP_TRACE=1: 8 words per workgroup, ticks (100 MHz) its thread 0 spent per phase of the updates; else null
+    int shared;                // the resident forms: operands that the gathering wave holds itself (the own row's, those of the rows beside it) come from
+                               // its registers, for the slot-rows whose rows are all stored around a centre; 0 (DPCG_CHIP_SHARED=0): everything is gathered
+    int *shared_out;           // 2 048 words, one per wave: slot-rows on that path | slot-rows with a row at all << 8 (null: not reported)
 };
 // dpcg_chip_sr.hip: the resident fp64 form of the above with the single-reduction recurrence (DPCG_SINGLE_REDUCTION)
 struct ChipSrDesc {
@@ -598,6 +603,7 @@ int chip_threads();
 int chip_slot_doubles();          // reduction slots (doubles) of a chip solve
 int64_t chip_zp_doubles(int64_t n);  // granule storage (doubles) of a chip solve
 void launch_band_and_len(const CsrDev &A, int *out2_zeroed_dev, hipStream_t s);
+void launch_centred_pairs(const CsrDev &A, int max_row_len, int *out2_zeroed_dev, hipStream_t s);   // rows of <= 9 entries, n <= 1 048 576
 int launch_pcg_chip(const ChipDesc &d, int max_row_len, hipStream_t s, bool check_only = false);
 int launch_occupy(int workgroups, double ms, hipStream_t s);
 int team_max_rows();

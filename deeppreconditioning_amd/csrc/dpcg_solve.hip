@@ -732,6 +732,7 @@ extern "C" int dpcg_solve(dpcg_handle_t h, const double *b, const double *x0, do
         if (const char *why = chip_sr_refusal(h, flags, x_true)) return invalid(why);     // (nothing of the handle has been touched)
     }
     h->last_recurrence = 0;
+    h->chip_shared_known = false;            // (set by the resident standard chip solve, dpcg_get_chip_info)
     if (flags & DPCG_SINGLE_REDUCTION) {
         if (one_launch_open) {
             const int st = solve_chip_sr_one(h, {b, x0, x, rtol_sq, atol_sq, max_iter, flags, (hipStream_t)stream, iters, final_res,
@@ -799,6 +800,7 @@ extern "C" int dpcg_solve_batch(int count, dpcg_handle_t *handles, const double 
     }
     // every form below runs the standard recurrence; the single-reduction members set their own word (dpcg_get_last_recurrence)
     for (int i = 0; i < count; ++i) handles[i]->last_recurrence = 0;
+    for (int i = 0; i < count; ++i) handles[i]->chip_shared_known = false;
     if (flags & DPCG_SINGLE_REDUCTION) {
         // the flag holds for every system as it does for a single solve: refused when one is not eligible, else one whole-chip launch
         // after the other (a member that cannot become co-resident goes through the launches with the standard recurrence)

@@ -207,11 +207,14 @@ static int ensure_chip_trsv(dpcg_system *h, hipStream_t s) {
 // ------------------------------------------------------------------------------------------------
 // the host path the four forms share
 // ------------------------------------------------------------------------------------------------
-// chip_part on a handle: the reduction slots, 8 trace words per workgroup (DPCG_CHIP_TRACE), the two-int error flag, the workgroups' XCD ids
+// chip_part on a handle: the reduction slots, 8 trace words per workgroup (DPCG_CHIP_TRACE), the two-int error flag, the workgroups' XCD ids,
+// one word per wave of the standard form (its slot-rows whose shared operands come from registers)
 struct ChipPart {
     double *base;
     static int slots() { return chip_slot_doubles(); }
-    static int64_t doubles() { return slots() + 8 * 256 + 2 + 128; }
+    static int waves() { return chip_workgroups() * chip_threads() / 64; }
+    static int64_t doubles() { return slots() + 8 * 256 + 2 + 128 + waves() / 2; }
+    int *shared() const { return reinterpret_cast<int *>(base + slots() + 8 * 256 + 2 + 128); }
     unsigned long long *dbg() const { return reinterpret_cast<unsigned long long *>(base + slots()); }
     int *err() const { return reinterpret_cast<int *>(base + slots() + 8 * 256); }
     int *xcc() const { return reinterpret_cast<int *>(base + slots() + 8 * 256 + 2); }
@@ -229,6 +232,17 @@ static unsigned next_chip_nonce() {
 static bool chip_trace_on() {
     static const bool on = [] { const char *e = getenv("DPCG_CHIP_TRACE"); return e && e[0] == '1'; }();
     return on;
+}
+// Which product a resident system takes.  A slot-row whose rows are all stored around a centre is ~4 % faster with same-wave operands from
+// registers; one that is not pays ~6.5 % for the branch in that instantiation (100^3, measured: DESIGN section 3).  So the instantiation with
+// the centred path is taken where at least 62 % of the system's (wave, slot-row) pairs are centred (6.5 / (4 + 6.5)), the packed one --
+// the kernel as it was -- elsewhere.  DPCG_CHIP_SHARED=0 / =1 (development, A/B): never / always.  Unlike the other DPCG_CHIP_* switches
+// it is read at every solve, so that one process can measure both; set it before the solves start, not from another thread during one.
+static bool chip_shared_on(const dpcg_system *h) {
+    const char *e = getenv("DPCG_CHIP_SHARED");
+    if (e && e[0] == '0') return false;
+    if (e && e[0] == '1') return true;
+    return h->planA.chip_pairs > 0 && 50ll * h->planA.chip_centred_pairs >= 31ll * h->planA.chip_pairs;
 }
 static bool chip_local_ok() {          // DPCG_CHIP_LOCAL=0 (development): everything written through
     static const bool on = [] { const char *e = getenv("DPCG_CHIP_LOCAL"); return !(e && e[0] == '0'); }();
@@ -386,8 +400,14 @@ int solve_chip_one(dpcg_system *h, SolveCall c) {
     if (d.f32 && (d.bench || trace || c.x0)) return DPCG_ERR_STATE;                      // (the caller goes on with the launches)
     if (d.stream_cap > 0 && (d.bench || trace)) return DPCG_ERR_STATE;
     d.dbg = trace ? ChipPart{h->chip_part}.dbg() : nullptr;
+    d.shared = chip_shared_on(h) ? 1 : 0;
+    d.shared_out = d.stream_cap > 0 ? nullptr : ChipPart{h->chip_part}.shared();
+    h->chip_shared_known = false;
     return chip_run(h, c, form, [&](bool check_only) { return launch_pcg_chip(d, h->planA.max_row_len, c.s, check_only); },
-                    [&](const Scalars &sc, bool) { return d.dbg ? read_chip_trace(h, d.dbg, sc) : DPCG_OK; });
+                    [&](const Scalars &sc, bool) {
+                        h->chip_shared_known = d.shared_out != nullptr;
+                        return d.dbg ? read_chip_trace(h, d.dbg, sc) : DPCG_OK;
+                    });
 }
 
 int solve_chip_sr_one(dpcg_system *h, SolveCall c) {
@@ -538,7 +558,7 @@ extern "C" int dpcg_debug_l2_gather(int granules_per_group, int reps, const int3
     return DPCG_OK;
 }
 
-extern "C" int dpcg_get_chip_info(dpcg_handle_t h, int32_t out[8], double trace_us[8]) {
+extern "C" int dpcg_get_chip_info(dpcg_handle_t h, int32_t out[10], double trace_us[8]) {
     if (!h || !out) return invalid("dpcg_get_chip_info: NULL argument");
     if (chip_trsv_shape(h, 0, nullptr) && h->trsv_state == 0) (void)ensure_chip_trsv(h, nullptr);     // (whether the factor fits is known once its lists exist)
     const bool el = chip_eligible(h, 0, nullptr) || chip_llt_eligible(h, 0, nullptr) || (chip_trsv_shape(h, 0, nullptr) && h->trsv_state == 1);
@@ -557,5 +577,13 @@ extern "C" int dpcg_get_chip_info(dpcg_handle_t h, int32_t out[8], double trace_
                        chip_rows_per_wg(h->A.n) <= chip_threads() / 2 && chip_llt_tagged();
     out[6] = (int)h->chip_trace_x[4] | ((split ? 2 : 1) << 8);
     out[7] = (int)(h->chip_trace_x[5] * 1.0e6);             // DPCG_CHIP_EVENTS=1: the last chip kernel between HIP events on its stream, ns
+    // the last solve, if it was a resident standard chip solve: (wave, slot-row) pairs whose shared operands came from registers, of those
+    // with a row at all (0 of 0: no such solve yet)
+    out[8] = out[9] = 0;
+    if (h->chip_shared_known && h->chip_part) {
+        std::vector<int32_t> w(ChipPart::waves());
+        DPCG_HIP(hipMemcpy(w.data(), ChipPart{h->chip_part}.shared(), w.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        for (int32_t x : w) { out[8] += x & 255; out[9] += (x >> 8) & 255; }
+    }
     return DPCG_OK;
 }

@@ -366,8 +366,11 @@ int dpcg_get_reduction_geometry(dpcg_handle_t h, int32_t out[16]);
  * phase), [1] sum <p,Ap> incl. its barrier, [2] vector updates + publishing, [3] sum <r,z>, <r,r> incl. its barrier, [4] the whole
  * loop, [5] / [6] of [1] / [3]: waiting for the other workgroups' slots, [7] = the number of updates.  No reference counterpart
  * (the reference's loop is host Python, cg.py:70-87).  A DPCG_SINGLE_REDUCTION solve has no phase timing: it zeroes trace_us and
- * bit 0 of out[6], and out[7] unless DPCG_CHIP_EVENTS=1 measured that kernel. */
-int dpcg_get_chip_info(dpcg_handle_t h, int32_t out[8], double trace_us[8]);
+ * bit 0 of out[6], and out[7] unless DPCG_CHIP_EVENTS=1 measured that kernel.  out[8] of out[9]: where the handle's LAST solve was a resident
+ * standard chip solve, the (wave, slot-row) pairs of it that took the operands their wave holds (the own rows' p and those of the rows beside
+ * them) from its registers instead of gathering them, of the pairs that have a row at all (DPCG_CHIP_SHARED=0 in the environment: 0 of them);
+ * 0 of 0 after any other solve. */
+int dpcg_get_chip_info(dpcg_handle_t h, int32_t out[10], double trace_us[8]);
 /* The recurrence the handle's last dpcg_solve / dpcg_solve_batch member ran: 0 = the standard one (cg.py:70-87), 1 = the
  * single-reduction one (DPCG_SINGLE_REDUCTION).  0 before the first solve.  No reference counterpart. */
 int dpcg_get_last_recurrence(dpcg_handle_t h, int *recurrence);

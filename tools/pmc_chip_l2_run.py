@@ -21,7 +21,7 @@ for _ in range(6):
     r = s.solve(b, want_history=False)
 its = r.iterations
 if "--variants" in sys.argv:
-    for env in ("1", "3"):
+    for env in ("1", "3", "4"):
         os.environ["DPCG_CHIP_BENCH"] = env
         for _ in range(6):
             s.solve(b, max_iter=its, want_history=False)
