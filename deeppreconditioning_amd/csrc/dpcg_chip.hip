@@ -214,9 +214,7 @@ __global__ __launch_bounds__(kChipThreads) void k_pcg_chip(const ChipDesc d) {
             const bool on = src[j] < len_k[k];
             const int c = on ? cj[j] : i;
             const double a = on ? (F32 ? (double)(float)aj[j] : aj[j]) : 0.0;
-            const unsigned del = (centred && j == jS) ? edge : (unsigned)(c - i + 32768) & 0xffffu;
-            if (s & 1) dl[s >> 1] |= del << 16;
-            else dl[s >> 1] = del;
+            put_col_offset(dl, s, (centred && j == jS) ? edge : (unsigned)(c - i + 32768) & 0xffffu);
             if (s < NREG) vr[s < NREG ? s : 0] = a;
             else if (F32_SLOTS) chip_lf[(s - NREG) * kChipThreads + t] = (float)a;
             else chip_lv[(s - NREG) * kChipThreads + t] = a;
@@ -636,12 +634,7 @@ __global__ __launch_bounds__(kChipThreads) void k_pcg_chip(const ChipDesc d) {
         o[5] = s_tk[5]; o[6] = s_tk[6]; o[7] = local ? 1ull : 0ull;
     }
     if (v == 0 && t == 0) {
-        Scalars *sc = d.out;
-        sc->k = k_done;
-        sc->res = res;
-        sc->bb = bb;
-        sc->status = alive ? status : DPCG_ERR_STATE;
-        sc->done = 1;
+        store_scalars(d.out, k_done, res, bb, alive, status);
     }
 }
 
@@ -692,20 +685,7 @@ int chip_launch(const ChipDesc &d, hipStream_t s, bool check_only) {
     const int lds_max5 = chip_stream_max_row_len() * kChipThreads * (int)sizeof(double) + RPT * kChipThreads * 8 + 1024 + (kChipThreads / 64) * kChipStreamGroups * 16;
     const int lds = (MODE == 5 || MODE == 6) ? (kChipThreads / 64) * d.stream_cap * (int)sizeof(double) + RPT * kChipThreads * 8 + 1024 + (kChipThreads / 64) * kChipStreamGroups * 16 : NLDS * kChipThreads * (MODE == 4 ? (int)sizeof(float) : (int)sizeof(double));
     const int lds_attr = (MODE == 5 || MODE == 6) ? lds_max5 : lds;
-    static int resident = -1;              // workgroups the occupancy query admits per CU (once per instantiation)
-    if (resident < 0) {
-        if (hipFuncSetAttribute((const void *)k_pcg_chip<RPT, WMAX, JAC, MODE, CEN>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_attr) != hipSuccess)
-            return DPCG_ERR_HIP;
-        int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_pcg_chip<RPT, WMAX, JAC, MODE, CEN>, kChipThreads, (size_t)lds_attr) !=
-            hipSuccess)
-            return DPCG_ERR_HIP;
-        resident = per_cu;
-    }
-    if (resident < 1) return DPCG_ERR_STATE;       // the kernel does not fit a CU: refused up front
-    if (check_only) return DPCG_OK;
-    hipLaunchKernelGGL((k_pcg_chip<RPT, WMAX, JAC, MODE, CEN>), dim3(kChipWGs), dim3(kChipThreads), (size_t)lds, s, d);
-    return DPCG_OK;
+    return chip_launch_resident<k_pcg_chip<RPT, WMAX, JAC, MODE, CEN>>(lds, d, s, check_only, lds_attr);
 }
 
 }  // namespace
@@ -755,9 +735,7 @@ __global__ __launch_bounds__(kChipThreads) void k_l2_gather_probe(double *table,
     const int glo = grp * per_group;
     const int rglo = sc1_only == 2 ? ((grp + 1) & 7) * per_group : glo;      // (2: gather the part the NEXT group wrote through -- another XCD's)
     const __amdgpu_buffer_rsrc_t rs = chip_rsrc(table, 8u * (unsigned)per_group * 16u);
-    Exchange X;
-    X.part_rs = chip_rsrc(part, (unsigned)kChipSlotBytes);
-    X.v = v; X.grp = grp; X.rank = rank; X.sh = sh; X.s_res = s_res; X.s_flag = &s_flag; X.err = err;
+    Exchange X = make_exchange(part, v, grp, rank, sh, s_res, &s_flag, err);
     bool alive = true;
     const bool local = groups_on_one_xcd(X, xcc, alive) && !sc1_only;
     X.local = local;

@@ -1,5 +1,8 @@
-// Device-side pieces shared by the whole-chip solve kernels (dpcg_chip.hip: M = I / Jacobi; dpcg_chip_llt.hip: M = L L^T multiplied):
-// geometry, the 16-byte granule helpers, and the two-hop chip-wide exchange that is both their reduction and their barrier.
+// Device-side pieces shared by the five whole-chip solve kernels -- k_pcg_chip (dpcg_chip.hip: M = I / Jacobi), k_pcg_chip_sr
+// (dpcg_chip_sr.hip: the single-reduction recurrence), k_pcg_chip_llt (dpcg_chip_llt.hip: M = L L^T multiplied), k_pcg_chip_trsv and
+// k_pcg_chip_trsv_res (dpcg_chip_trsv.hip: M applied by two triangular solves): the geometry, the slot packing of a matrix slice, the
+// 16-byte granules, their two copies and the key of the self-validating ones, the bounded wait, the two-hop chip-wide exchange that is
+// both their reduction and their barrier, what workgroup 0 leaves for the host, and the one host launcher.  Which pieces are NOT shared, and why: DESIGN section 3, "shared device code".
 // Include from .hip files only.
 #pragma once
 
@@ -12,6 +15,7 @@ constexpr int kChipWGs = 256;           // one workgroup per CU
 constexpr int kChipThreads = 512;       // 8 waves: two per SIMD, 256 vector registers per lane
 constexpr int kChipMaxRpt = 8;          // rows per thread: n <= 256 * 512 * 8
 constexpr int kChipLdsSlots = 39;       // 8-byte value slots per thread kept in LDS: 39 * 512 * 8 = 159 744 B of the CU's 163 840
+constexpr int kChipStreamGroups = 64;   // groups of 192 entries a wave walks per update in the streamed form (8 slots x 64 rows x 24 entries / 192)
 constexpr unsigned long long kChipSpinTicks = 2000000ull;               // 20 ms of the 100 MHz constant clock
 constexpr unsigned long long kChipPending = 0x7ff8dead0badbeefULL;      // a quiet NaN that no arithmetic here produces
 constexpr int kChipZpPad = 4096;        // granules of slack behind each copy (group shifts; rows that do not exist gather there)
@@ -21,7 +25,6 @@ constexpr int kSc1 = 16;                // cache-policy operand of the buffer bu
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-constexpr int kChipStreamGroups = 64;      // groups of 192 entries a wave walks per update in the streamed form (8 slots x 64 rows x 24 entries / 192)
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t chip_rsrc(const void *p, unsigned bytes) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, (int)bytes, 0x00020000);
@@ -42,6 +45,85 @@ __device__ __forceinline__ bool is_pending(const u32x4 &g) {
            (g.z == (unsigned)(kChipPending & 0xffffffffu) && g.w == (unsigned)(kChipPending >> 32));
 }
 
+// The workgroup's place in the solve.  Workgroup v (its "virtual" index: blocks b, b + 8, ... share an XCD, and v = 32 grp + rank gives each
+// XCD one contiguous eighth of the rows) owns rows [v * per, (v + 1) * per); the thread whose row slot in the workgroup is `tr` owns rows
+// row0 + 512 k.
+struct ChipGeom {
+    int v, grp, rank;
+    int row0;                  // row of slot k: row0 + 512 k
+    int glo, ghi;              // the group's rows: [glo, ghi)
+    int remote_base;           // byte offset of the written-through copy of a granule buffer, behind the plainly stored one
+};
+__device__ __forceinline__ ChipGeom chip_geom(int per, int n, int tr) {
+    ChipGeom G;
+    G.v = ((int)blockIdx.x & 7) * (kChipWGs / 8) + ((int)blockIdx.x >> 3);
+    G.row0 = G.v * per + tr;
+    G.grp = (int)blockIdx.x & 7;
+    G.rank = (int)blockIdx.x >> 3;
+    G.glo = G.grp * (kChipWGs / 8) * per;
+    G.ghi = (G.glo + (kChipWGs / 8) * per < n) ? G.glo + (kChipWGs / 8) * per : n;
+    G.remote_base = (n + kChipZpPad) * 16;
+    return G;
+}
+
+// A thread's slice of a matrix: per entry slot a 16-bit column offset from the row (two to a register) and a value -- in registers for the
+// slots below NREG, in the LDS behind them (lds_t: the value array + the thread's column).
+template <int NDL>
+__device__ __forceinline__ void put_col_offset(unsigned (&dl)[NDL], int s, unsigned del) {
+    if (s & 1) dl[s >> 1] |= del << 16;
+    else dl[s >> 1] = del;
+}
+template <int NREG, int NDL, int NVR>
+__device__ __forceinline__ void put_slot(int s, int i, int c, double a, unsigned (&dl)[NDL], double (&vr)[NVR], double *lds_t) {
+    put_col_offset(dl, s, (unsigned)(c - i + 32768) & 0xffffu);
+    if (s < NREG) vr[s < NREG ? s : 0] = a;
+    else lds_t[(s - NREG) * kChipThreads] = a;
+}
+// SELF-VALIDATING granules {value, value ^ key}: the key is a function of the launch (nonce) and of the publication's generation, and
+// always odd -- the zeros a table holds at launch are never accepted.  A reader takes a granule only when its halves differ by exactly
+// the key it expects (dpcg_chip_llt.hip explains what that refuses).
+__device__ __forceinline__ unsigned long long granule_key(unsigned nonce, unsigned gen) {
+    return (((unsigned long long)nonce << 32) | (unsigned long long)gen) * 0x9E3779B97F4A7C15ull | 1ull;
+}
+__device__ __forceinline__ u32x4 tagged_granule(double val, unsigned long long key) {
+    const unsigned long long bits = (unsigned long long)__double_as_longlong(val), tag = bits ^ key;
+    u32x4 w;
+    w.x = (unsigned)bits; w.y = (unsigned)(bits >> 32); w.z = (unsigned)tag; w.w = (unsigned)(tag >> 32);
+    return w;
+}
+// The two copies of a row's granule (o: 16 x the row): the plain one inside the group (group g's part shifted by 128 g bytes) when every
+// group sits on one XCD, the written-through one behind it (remote_base) when another group gathers the row.
+__device__ __forceinline__ void store_granule(const u32x4 &w, const __amdgpu_buffer_rsrc_t &rs, int o, int grp, int remote_base, bool local, bool far) {
+    if (local) __builtin_amdgcn_raw_buffer_store_b128(w, rs, o + grp * 128, 0, 0);
+    if (far) __builtin_amdgcn_raw_buffer_store_b128(w, rs, o + remote_base, 0, kSc1);
+}
+
+// what thread 0 of workgroup 0 leaves for the host when the solve ends (alive: no wait ran out)
+__device__ __forceinline__ void store_scalars(Scalars *sc, int k, double res, double bb, bool alive, int status) {
+    sc->k = k;
+    sc->res = res;
+    sc->bb = bb;
+    sc->status = alive ? status : DPCG_ERR_STATE;
+    sc->done = 1;
+}
+
+// The bounded wait of a spin loop: asked once per spin.  Every 256 spins it reads the clock; past kChipSpinTicks (20 ms), or when a wait
+// ran out somewhere else, the lane that notices raises the device flag and the caller gives up.
+struct BoundedWait {
+    unsigned spins = 0;
+    unsigned long long t0 = 0;
+    __device__ __forceinline__ bool give_up(int *err) {
+        if ((++spins & 255u) == 0) {
+            const unsigned long long now = wall_clock64();
+            if (t0 == 0) t0 = now;
+            else if (now - t0 > kChipSpinTicks || __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
+                atomicExch(err, 1);
+                return true;
+            }
+        }
+        return false;
+    }
+};
 
 // State of a workgroup's side of the chip-wide exchange.  LDS: sh = 2 x 16 doubles (block sums, two halves in turn), s_res = 2 x 2
 // doubles (the reduced pair, two sets in turn), s_flag one int.
@@ -57,6 +139,12 @@ struct Exchange {
     int *err;                               // device flag: a wait ran out somewhere
     unsigned long long *wait_acc = nullptr; // trace: LDS word that thread 0 adds the slot-polling time to (null: no trace)
 };
+__device__ __forceinline__ Exchange make_exchange(const void *part, int v, int grp, int rank, double *sh, double (*s_res)[2], int *s_flag, int *err) {
+    Exchange X;
+    X.part_rs = chip_rsrc(part, (unsigned)kChipSlotBytes);
+    X.v = v; X.grp = grp; X.rank = rank; X.sh = sh; X.s_res = s_res; X.s_flag = s_flag; X.err = err;
+    return X;
+}
 
 // polls one slot per lane (lanes < count of wave 0) until none is pending; false when the wait ran out
 __device__ __forceinline__ bool poll_slots(const Exchange &X, u32x4 &sv, int off, int count) {
@@ -64,19 +152,11 @@ __device__ __forceinline__ bool poll_slots(const Exchange &X, u32x4 &sv, int off
     const bool mine = t < count;
     sv = pack_f64x2(0.0, 0.0);
     if (mine) sv = __builtin_amdgcn_raw_buffer_load_b128(X.part_rs, off, 0, kSc1);
-    unsigned spins = 0;
-    unsigned long long t0 = 0;
+    BoundedWait wait;
     while (__ballot(mine && is_pending(sv)) != 0) {
         __builtin_amdgcn_s_sleep(1);
         if (mine && is_pending(sv)) sv = __builtin_amdgcn_raw_buffer_load_b128(X.part_rs, off, 0, kSc1);
-        if ((++spins & 255u) == 0) {
-            const unsigned long long now = wall_clock64();
-            if (t0 == 0) t0 = now;
-            else if (now - t0 > kChipSpinTicks || __hip_atomic_load(X.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-                atomicExch(X.err, 1);
-                return false;
-            }
-        }
+        if (wait.give_up(X.err)) return false;
     }
     return true;
 }
@@ -172,6 +252,44 @@ __device__ __forceinline__ bool groups_on_one_xcd(Exchange &X, int *xcc, bool &a
         same = mine == first ? 1 : 0;
     }
     return __syncthreads_and(same) != 0;
+}
+
+// ... and what follows from it, once per solve: X.local, and far_rows -- bit k: row k of this thread (row0 + 512 k) lies within the band of
+// the first or last row of its group [glo, ghi), so another group gathers it and it needs the written-through copy (all rows unless
+// every group sits on one XCD).  Returns `local`.
+template <int RPT>
+__device__ __forceinline__ bool place_groups(Exchange &X, int *xcc, int row0, int glo, int ghi, int band, unsigned &far_rows, bool &alive) {
+    const bool local = groups_on_one_xcd(X, xcc, alive);
+    X.local = local;
+    if (local) {
+        far_rows = 0;
+#pragma unroll
+        for (int k = 0; k < RPT; ++k) {
+            const int i = row0 + k * kChipThreads;
+            if (i < glo + band || i >= ghi - band) far_rows |= 1u << k;
+        }
+    }
+    return local;
+}
+
+// The host side of every whole-chip kernel: one launch of 256 x 512 whose workgroups must ALL be resident.  Sets the dynamic-LDS
+// attribute and asks the occupancy query once per kernel (lds_attr: the largest buffer the instantiation may be launched with, where that
+// is more than this launch's lds_bytes);
+// DPCG_ERR_STATE when the kernel does not fit a CU -- refused up front.  check_only: the query alone.
+template <auto Kernel, class Desc>
+int chip_launch_resident(int lds_bytes, const Desc &d, hipStream_t s, bool check_only, int lds_attr = -1) {
+    static int resident = -1;              // workgroups the occupancy query admits per CU (once per instantiation)
+    if (lds_attr < 0) lds_attr = lds_bytes;
+    if (resident < 0) {
+        if (hipFuncSetAttribute((const void *)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_attr) != hipSuccess) return DPCG_ERR_HIP;
+        int per_cu = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)Kernel, kChipThreads, (size_t)lds_attr) != hipSuccess) return DPCG_ERR_HIP;
+        resident = per_cu;
+    }
+    if (resident < 1) return DPCG_ERR_STATE;
+    if (check_only) return DPCG_OK;
+    hipLaunchKernelGGL(Kernel, dim3(kChipWGs), dim3(kChipThreads), (size_t)lds_bytes, s, d);
+    return DPCG_OK;
 }
 
 }  // namespace chip

@@ -28,8 +28,6 @@ using namespace chip;
 
 namespace {
 
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
 // RPT: rows per thread (1, 2); WA: entry slots per row of A (5, 7); WL: entry slots per row of L and of L^T (4, 8, 16).
 // SPLIT (RPT == 1, <= 256 rows per workgroup -- config 2: otherwise half the lanes would idle while the others gather and validate 2 x 16
 // granules a row): TWO lanes per row.  Both hold the row's vectors and compute q = A p (redundantly); of a factor row lane h of the
@@ -51,11 +49,7 @@ __global__ __launch_bounds__(kChipThreads) void k_pcg_chip_llt(const ChipLltDesc
     const int tr = SPLIT ? (t >> 1) : t;                             // the thread's row slot in the workgroup
     const int half = SPLIT ? (t & 1) : 0;
     const bool counts = half == 0;                                   // (of a pair, the even lane publishes and counts in the dot products)
-    const int v = ((int)blockIdx.x & 7) * (kChipWGs / 8) + ((int)blockIdx.x >> 3);
-    const int grp = (int)blockIdx.x & 7, rank = (int)blockIdx.x >> 3;
-    const int row0 = v * d.per + tr;
-    const int glo = grp * (kChipWGs / 8) * d.per;
-    const int ghi = (glo + (kChipWGs / 8) * d.per < d.n) ? glo + (kChipWGs / 8) * d.per : d.n;
+    const ChipGeom G = chip_geom(d.per, d.n, tr);
     const int zp_remote = (d.n + kChipZpPad) * 16, v8_remote = (d.n + kChipZpPad) * 8;
     const __amdgpu_buffer_rsrc_t zp_rs = chip_rsrc(d.zp, 2u * (unsigned)(d.n + kChipZpPad) * 16u);
     const __amdgpu_buffer_rsrc_t r_rs = chip_rsrc(d.rpub, 2u * (unsigned)(d.n + kChipZpPad) * 16u);     // (16-byte granules; the 8-byte forms use half)
@@ -69,7 +63,7 @@ __global__ __launch_bounds__(kChipThreads) void k_pcg_chip_llt(const ChipLltDesc
     double bb_loc = 0.0;
 #pragma unroll
     for (int k = 0; k < RPT; ++k) {
-        const int loc = k * kChipThreads + tr, i = row0 + k * kChipThreads;
+        const int loc = k * kChipThreads + tr, i = G.row0 + k * kChipThreads;
         const bool valid = loc < d.per && i < d.n;
         const int ic = valid ? i : 0;
         const int a0 = d.rp[ic], a1 = d.rp[ic + 1];
@@ -95,11 +89,7 @@ __global__ __launch_bounds__(kChipThreads) void k_pcg_chip_llt(const ChipLltDesc
                 const int e = on ? e0 + j : 0;
                 const int c = on ? ci[e] : i;
                 const double a = on ? val[e] : 0.0;
-                const unsigned del = (unsigned)(c - i + 32768) & 0xffffu;
-                if (s & 1) dl[s >> 1] |= del << 16;
-                else dl[s >> 1] = del;
-                if (s < NREG) vr[s < NREG ? s : 0] = a;
-                else chip_lv[(s - NREG) * kChipThreads + t] = a;
+                put_slot<NREG>(s, i, c, a, dl, vr, chip_lv + t);
             }
         };
         take(0, WA, d.ci, d.val, a0, a1 - a0);
@@ -113,9 +103,7 @@ __global__ __launch_bounds__(kChipThreads) void k_pcg_chip_llt(const ChipLltDesc
     auto row_counts = [&](int k) -> bool { return counts && (lens[k] & 0x80000000u) != 0; };   // ... and this lane speaks for it
     bool local = false;
 
-    Exchange X;
-    X.part_rs = chip_rsrc(d.part, (unsigned)kChipSlotBytes);
-    X.v = v; X.grp = grp; X.rank = rank; X.sh = sh; X.s_res = s_res; X.s_flag = &s_flag; X.err = d.err;
+    Exchange X = make_exchange(d.part, G.v, G.grp, G.rank, sh, s_res, &s_flag, d.err);
     double dummy = 0.0, dummy2 = 0.0;
     auto data_barrier = [&]() -> bool { return exchange2(X, 0.0, 0.0, true, dummy, dummy2); };
     // y_k = (row of the matrix whose slots start at `first`) . vec, the vector's entries fetched by `fetch(column, is_own_group)`;
@@ -125,14 +113,14 @@ __global__ __launch_bounds__(kChipThreads) void k_pcg_chip_llt(const ChipLltDesc
         int tl = t;
         asm volatile("" : "+v"(tl));                      // (keeps the LDS reads and the addresses inside the update loop: see dpcg_chip.hip)
         const double *lvt = chip_lv + tl;
-        int glo_l = glo, span_l = local ? ghi - glo : 0;
+        int glo_l = G.glo, span_l = local ? G.ghi - G.glo : 0;
         asm volatile("" : "+s"(glo_l), "+s"(span_l));
 #pragma unroll
         for (int e = 0; e < (NS + 1) / 2; ++e) asm volatile("" : "+v"(dl[e]));
 #pragma unroll
         for (int k = 0; k < RPT; ++k) {
             asm volatile("" : "+v"(lens[k]));
-            const int rowk = row0 + k * kChipThreads;
+            const int rowk = G.row0 + k * kChipThreads;
             const int len = (int)((lens[k] >> lshift) & 31u);
             double g[16];
 #pragma unroll
@@ -159,22 +147,21 @@ __global__ __launch_bounds__(kChipThreads) void k_pcg_chip_llt(const ChipLltDesc
     };
     auto fetch8 = [&](const __amdgpu_buffer_rsrc_t &rs) {
         return [&, rs](int c, bool own) -> double {
-            const u32x2 w = __builtin_amdgcn_raw_buffer_load_b64(rs, c * 8 + (own ? grp * 128 : v8_remote), 0, kSc1);
+            const u32x2 w = __builtin_amdgcn_raw_buffer_load_b64(rs, c * 8 + (own ? G.grp * 128 : v8_remote), 0, kSc1);
             return __hiloint2double((int)w.y, (int)w.x);
         };
     };
     auto publish8 = [&](const __amdgpu_buffer_rsrc_t &rs, int k, double val) {
-        const int o = (row0 + k * kChipThreads) * 8;
+        const int o = (G.row0 + k * kChipThreads) * 8;
         u32x2 w;
         w.x = (unsigned)__double2loint(val);
         w.y = (unsigned)__double2hiint(val);
-        if (local) __builtin_amdgcn_raw_buffer_store_b64(w, rs, o + grp * 128, 0, 0);
+        if (local) __builtin_amdgcn_raw_buffer_store_b64(w, rs, o + G.grp * 128, 0, 0);
         if ((far_rows >> k) & 1u) __builtin_amdgcn_raw_buffer_store_b64(w, rs, o + v8_remote, 0, kSc1);
     };
     auto publish_zp = [&](int k, double zk, double pk) {
-        const int o = (row0 + k * kChipThreads) * 16;
-        if (local) __builtin_amdgcn_raw_buffer_store_b128(pack_f64x2(zk, pk), zp_rs, o + grp * 128, 0, 0);
-        if ((far_rows >> k) & 1u) __builtin_amdgcn_raw_buffer_store_b128(pack_f64x2(zk, pk), zp_rs, o + zp_remote, 0, kSc1);
+        const int o = (G.row0 + k * kChipThreads) * 16;
+        store_granule(pack_f64x2(zk, pk), zp_rs, o, G.grp, zp_remote, local, ((far_rows >> k) & 1u) != 0);
     };
     // SELF-VALIDATING granules for r and t = L^T r: {value, value ^ key}, the key a function of the solve and of the publication's
     // generation.  Each half is an aligned 8-byte word (written and read whole); a reader accepts a granule only when its halves
@@ -183,22 +170,16 @@ __global__ __launch_bounds__(kChipThreads) void k_pcg_chip_llt(const ChipLltDesc
     // refused and read again.  The gather of a product is thereby its own synchronisation: no drain, no flag, no barrier between the
     // three products of an update.  Rewriting is safe: two chip-wide exchanges lie between a vector's gathers and its next publication.
     // (nonce == 0 -- development knob DPCG_CHIP_LLT_SYNC=0 -- keeps plain 8-byte vectors and a chip-wide barrier per product.)
-    auto make_key = [&](unsigned gen) -> unsigned long long {
-        return (((unsigned long long)d.nonce << 32) | (unsigned long long)gen) * 0x9E3779B97F4A7C15ull | 1ull;
-    };
     auto publish_tagged = [&](const __amdgpu_buffer_rsrc_t &rs, int k, double val, unsigned long long key) {
-        const int o = (row0 + k * kChipThreads) * 16;
-        const unsigned long long bits = (unsigned long long)__double_as_longlong(val), tag = bits ^ key;
-        u32x4 w;
-        w.x = (unsigned)bits; w.y = (unsigned)(bits >> 32); w.z = (unsigned)tag; w.w = (unsigned)(tag >> 32);
-        if (local) __builtin_amdgcn_raw_buffer_store_b128(w, rs, o + grp * 128, 0, 0);
-        if ((far_rows >> k) & 1u) __builtin_amdgcn_raw_buffer_store_b128(w, rs, o + zp_remote, 0, kSc1);
+        const int o = (G.row0 + k * kChipThreads) * 16;
+        const u32x4 w = tagged_granule(val, key);
+        store_granule(w, rs, o, G.grp, zp_remote, local, ((far_rows >> k) & 1u) != 0);
     };
     auto products_tagged = [&](int first, int W, int lshift, double (&y)[RPT], const __amdgpu_buffer_rsrc_t &rs, unsigned long long key) -> bool {
         int tl = t;
         asm volatile("" : "+v"(tl));
         const double *lvt = chip_lv + tl;
-        int glo_l = glo, span_l = local ? ghi - glo : 0;
+        int glo_l = G.glo, span_l = local ? G.ghi - G.glo : 0;
         asm volatile("" : "+s"(glo_l), "+s"(span_l));
 #pragma unroll
         for (int e = 0; e < (NS + 1) / 2; ++e) asm volatile("" : "+v"(dl[e]));
@@ -207,7 +188,7 @@ __global__ __launch_bounds__(kChipThreads) void k_pcg_chip_llt(const ChipLltDesc
 #pragma unroll
         for (int k = 0; k < RPT; ++k) {
             asm volatile("" : "+v"(lens[k]));
-            const int rowk = row0 + k * kChipThreads;
+            const int rowk = G.row0 + k * kChipThreads;
             const int len = (int)((lens[k] >> lshift) & 31u);
             u32x4 g[16];
             int off[16];
@@ -217,7 +198,7 @@ __global__ __launch_bounds__(kChipThreads) void k_pcg_chip_llt(const ChipLltDesc
                     const int s = k * WR + first + j;
                     const int del = (int)((dl[s >> 1] >> (16 * (s & 1))) & 0xffffu);
                     const int c = rowk + del - 32768;
-                    off[j] = c * 16 + ((unsigned)(c - glo_l) < (unsigned)span_l ? grp * 128 : zp_remote);
+                    off[j] = c * 16 + ((unsigned)(c - glo_l) < (unsigned)span_l ? G.grp * 128 : zp_remote);
                     g[j] = __builtin_amdgcn_raw_buffer_load_b128(rs, off[j], 0, kSc1);
                 }
             }
@@ -285,7 +266,7 @@ __global__ __launch_bounds__(kChipThreads) void k_pcg_chip_llt(const ChipLltDesc
     // q = A p_k, the gathered entries recomputed from the granules {z_k, p_{k-1}} (cg.py:75,83)
     auto spmv_a = [&](double beta) {
         row_products(0, WA, 0, q, [&](int c, bool own) -> double {
-            const u32x4 gq = __builtin_amdgcn_raw_buffer_load_b128(zp_rs, c * 16 + (own ? grp * 128 : zp_remote), 0, kSc1);
+            const u32x4 gq = __builtin_amdgcn_raw_buffer_load_b128(zp_rs, c * 16 + (own ? G.grp * 128 : zp_remote), 0, kSc1);
             return lo_f64(gq) + beta * hi_f64(gq);
         });
     };
@@ -294,13 +275,13 @@ __global__ __launch_bounds__(kChipThreads) void k_pcg_chip_llt(const ChipLltDesc
     unsigned pub_gen = 0;
     auto apply_m = [&]() -> bool {
         if (d.nonce) {                                            // self-validating granules: the gathers synchronise
-            const unsigned long long key_r = make_key(++pub_gen);
+            const unsigned long long key_r = granule_key(d.nonce, ++pub_gen);
 #pragma unroll
             for (int k = 0; k < RPT; ++k)
                 if (row_on(k) && counts) publish_tagged(r_rs, k, r[k], key_r);
             double tv[RPT];
             if (!products_tagged(WA, WLS, 5, tv, r_rs, key_r)) return false;
-            const unsigned long long key_t = make_key(++pub_gen);
+            const unsigned long long key_t = granule_key(d.nonce, ++pub_gen);
 #pragma unroll
             for (int k = 0; k < RPT; ++k)
                 if (row_on(k) && counts) publish_tagged(t_rs, k, tv[k], key_t);
@@ -322,18 +303,7 @@ __global__ __launch_bounds__(kChipThreads) void k_pcg_chip_llt(const ChipLltDesc
     };
 
     bool alive = true;
-    if (d.xcc) {
-        local = groups_on_one_xcd(X, d.xcc, alive);
-        X.local = local;
-        if (local) {
-            far_rows = 0;
-#pragma unroll
-            for (int k = 0; k < RPT; ++k) {
-                const int i = row0 + k * kChipThreads;
-                if (i < glo + d.band || i >= ghi - d.band) far_rows |= 1u << k;
-            }
-        }
-    }
+    if (d.xcc) local = place_groups<RPT>(X, d.xcc, G.row0, G.glo, G.ghi, d.band, far_rows, alive);
     // ---- cg.py:58-67 -------------------------------------------------------------------------------------------------
     if (alive && d.x0) {                                          // r = b - A x0 (cg.py:60): x0 published as "z", beta = 0
 #pragma unroll
@@ -365,7 +335,7 @@ __global__ __launch_bounds__(kChipThreads) void k_pcg_chip_llt(const ChipLltDesc
     int k_done = 0, status = DPCG_MAX_ITER;
     bool stop = false;
     if (alive) {
-        if (v == 0 && t == 0 && d.hist_cap > 0) d.hist[0] = res;
+        if (G.v == 0 && t == 0 && d.hist_cap > 0) d.hist[0] = res;
         const bool conv = (res < d.rtol_sq) || (tt < d.atol_sq);
         if (conv) { stop = true; status = DPCG_OK; }
         else if (!(res == res)) { stop = true; status = DPCG_BREAKDOWN; }
@@ -402,21 +372,16 @@ __global__ __launch_bounds__(kChipThreads) void k_pcg_chip_llt(const ChipLltDesc
         rz = rz_new;
         res = rr / bb;                                            // cg.py:86
         ++k_done;
-        if (v == 0 && t == 0 && k_done < d.hist_cap) d.hist[k_done] = res;
+        if (G.v == 0 && t == 0 && k_done < d.hist_cap) d.hist[k_done] = res;
         const bool conv = (res < d.rtol_sq) || (rr < d.atol_sq);  // cg.py:71
         if (conv) { stop = true; status = DPCG_OK; }
         else if (!(res == res)) { stop = true; status = DPCG_BREAKDOWN; }
     }
 #pragma unroll
     for (int k = 0; k < RPT; ++k)
-        if (alive && row_counts(k)) d.x[row0 + k * kChipThreads] = x[k];     // (nothing after a wait that ran out: see dpcg_chip.hip)
-    if (v == 0 && t == 0) {
-        Scalars *sc = d.out;
-        sc->k = k_done;
-        sc->res = res;
-        sc->bb = bb;
-        sc->status = alive ? status : DPCG_ERR_STATE;
-        sc->done = 1;
+        if (alive && row_counts(k)) d.x[G.row0 + k * kChipThreads] = x[k];     // (nothing after a wait that ran out: see dpcg_chip.hip)
+    if (G.v == 0 && t == 0) {
+        store_scalars(d.out, k_done, res, bb, alive, status);
     }
 }
 
@@ -425,20 +390,7 @@ int chip_llt_launch(const ChipLltDesc &d, hipStream_t s, bool check_only) {
     constexpr int NS = RPT * (WA + 2 * (SPLIT ? WL / 2 : WL));
     constexpr int NLDS = NS < kChipLdsSlots ? NS : kChipLdsSlots;
     const int lds = NLDS * kChipThreads * (int)sizeof(double);
-    static int resident = -1;
-    if (resident < 0) {
-        if (hipFuncSetAttribute((const void *)k_pcg_chip_llt<RPT, WA, WL, SPLIT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
-            return DPCG_ERR_HIP;
-        int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_pcg_chip_llt<RPT, WA, WL, SPLIT>, kChipThreads, (size_t)lds) !=
-            hipSuccess)
-            return DPCG_ERR_HIP;
-        resident = per_cu;
-    }
-    if (resident < 1) return DPCG_ERR_STATE;
-    if (check_only) return DPCG_OK;
-    hipLaunchKernelGGL((k_pcg_chip_llt<RPT, WA, WL, SPLIT>), dim3(kChipWGs), dim3(kChipThreads), (size_t)lds, s, d);
-    return DPCG_OK;
+    return chip_launch_resident<k_pcg_chip_llt<RPT, WA, WL, SPLIT>>(lds, d, s, check_only);
 }
 
 }  // namespace

@@ -30,7 +30,10 @@
 //     that polls a slot polls two -- both requests are in flight together, so a hop costs one round trip as before.  32-byte slots
 //     validated as two halves would need the same two loads a lane and a second layout of the slot array besides.  The sums of both
 //     sets go through the wave tree that chip::exchange2 uses, lane for lane: every workgroup adds the same values in the same
-//     order (the oracle's form "chip").  With M = I gamma and rho are the same sum; it is carried twice rather than compiled twice.
+//     order (the oracle's form "chip").  exchange4 / poll_slots2 below are a copy of chip::exchange2 / poll_slots kept in step BY HAND:
+//     one template over the number of sets changed the register allocation of three instantiations of this kernel and of nine elsewhere
+//     ("Shared device code"), so a change to either pair must be made to both.  With M = I gamma and rho are the same
+//     sum; it is carried twice rather than compiled twice.
 //   * geometry, placement, visibility, co-residency: dpcg_chip.hip's (256 x 512 threads, rows v * per + t + 512 k, values in LDS and
 //     registers, 16-bit column offsets, XCD reporting, the plain copy inside a group and the written-through copy for the rows within
 //     the band of a group's edge, bounded waits, DPCG_ERR_STATE -> the caller's multi-launch path with the standard recurrence).
@@ -56,20 +59,12 @@ __device__ __forceinline__ bool poll_slots2(const Exchange &X, const __amdgpu_bu
         sa = __builtin_amdgcn_raw_buffer_load_b128(X.part_rs, off, 0, kSc1);
         sb = __builtin_amdgcn_raw_buffer_load_b128(part2_rs, off, 0, kSc1);
     }
-    unsigned spins = 0;
-    unsigned long long t0 = 0;
+    BoundedWait wait;
     while (__ballot(mine && (is_pending(sa) || is_pending(sb))) != 0) {
         __builtin_amdgcn_s_sleep(1);
         if (mine && is_pending(sa)) sa = __builtin_amdgcn_raw_buffer_load_b128(X.part_rs, off, 0, kSc1);
         if (mine && is_pending(sb)) sb = __builtin_amdgcn_raw_buffer_load_b128(part2_rs, off, 0, kSc1);
-        if ((++spins & 255u) == 0) {
-            const unsigned long long now = wall_clock64();
-            if (t0 == 0) t0 = now;
-            else if (now - t0 > kChipSpinTicks || __hip_atomic_load(X.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-                atomicExch(X.err, 1);
-                return false;
-            }
-        }
+        if (wait.give_up(X.err)) return false;
     }
     return true;
 }
@@ -213,23 +208,13 @@ __global__ __launch_bounds__(kChipThreads) void k_pcg_chip_sr(const ChipSrDesc d
         }
 #pragma unroll
         for (int j = 0; j < WMAX; ++j) {
-            const int sl = k * WMAX + j;
             const bool on = j < len_k[k];
-            const int c = on ? cj[j] : i;
-            const double a = on ? aj[j] : 0.0;
-            const unsigned del = (unsigned)(c - i + 32768) & 0xffffu;
-            if (sl & 1) dl[sl >> 1] |= del << 16;
-            else dl[sl >> 1] = del;
-            if (sl < NREG) vr[sl < NREG ? sl : 0] = a;
-            else chip_lv[(sl - NREG) * kChipThreads + t] = a;
+            put_slot<NREG>(k * WMAX + j, i, on ? cj[j] : i, on ? aj[j] : 0.0, dl, vr, chip_lv + t);
         }
         __builtin_amdgcn_sched_barrier(0);
     }
     bool local = false;                     // every group on one XCD (established below, once per solve)
     auto row_on = [&](int k) -> bool { return row_valid_bits(lens, k); };
-    auto make_key = [&](unsigned gen) -> unsigned long long {
-        return (((unsigned long long)ds.nonce << 32) | (unsigned long long)gen) * 0x9E3779B97F4A7C15ull | 1ull;
-    };
 
     // s = A z for the own rows out of the granules of generation `gen`; a row whose granules are not all of that generation yet is
     // gathered again.  The next row's gathers are issued while this row's are checked and consumed; row sums in CSR order.
@@ -247,7 +232,7 @@ __global__ __launch_bounds__(kChipThreads) void k_pcg_chip_sr(const ChipSrDesc d
 #pragma unroll
         for (int e = 0; e < (NS + 1) / 2; ++e) asm volatile("" : "+v"(dl[e]));
         asm volatile("" : "+v"(lens));
-        const unsigned long long key = make_key(gen);
+        const unsigned long long key = granule_key(ds.nonce, gen);
         const unsigned klo = (unsigned)key, khi = (unsigned)(key >> 32);
         auto address = [&](int k, int j) -> int {
             const int sl = k * WMAX + j;
@@ -267,8 +252,7 @@ __global__ __launch_bounds__(kChipThreads) void k_pcg_chip_sr(const ChipSrDesc d
             if (k + 1 < RPT) request(k + 1, g[(k + 1) & 1]);
             __builtin_amdgcn_sched_barrier(0);                     // (two rows' granules in flight is what the registers hold)
             const int len = (int)((lens >> (4 * k)) & 7u);
-            unsigned spins = 0;
-            unsigned long long t0 = 0;
+            BoundedWait wait;
             for (;;) {
                 bool bad = false;
 #pragma unroll
@@ -276,14 +260,9 @@ __global__ __launch_bounds__(kChipThreads) void k_pcg_chip_sr(const ChipSrDesc d
                 if (__ballot(bad) == 0) break;
                 __builtin_amdgcn_s_sleep(1);
                 if (bad) request(k, g[k & 1]);                     // (the whole row again: one divergent region)
-                if ((++spins & 255u) == 0) {
-                    const unsigned long long now = wall_clock64();
-                    if (t0 == 0) t0 = now;
-                    else if (now - t0 > kChipSpinTicks || __hip_atomic_load(d.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-                        atomicExch(d.err, 1);
-                        ok = false;
-                        break;
-                    }
+                if (wait.give_up(d.err)) {
+                    ok = false;
+                    break;
                 }
             }
             double acc = 0.0;
@@ -299,39 +278,23 @@ __global__ __launch_bounds__(kChipThreads) void k_pcg_chip_sr(const ChipSrDesc d
         return __syncthreads_and(ok ? 1 : 0) != 0;
     };
 
-    Exchange X;
-    X.part_rs = chip_rsrc(d.part, (unsigned)kChipSlotBytes);
-    X.v = v; X.grp = grp; X.rank = rank; X.sh = sh; X.s_res = s_res; X.s_flag = &s_flag; X.err = d.err;
+    Exchange X = make_exchange(d.part, v, grp, rank, sh, s_res, &s_flag, d.err);
     unsigned far_rows = 0xffu;              // bit k: row k of this thread is gathered by another group (all of them until `local` holds)
     int row0_l = row0;                      // an opaque copy per update: hoisted store addresses are registers the loop does not have
     auto publish = [&](int k, double zk, unsigned long long key) {
         const int o = (row0_l + k * kChipThreads) * 16;
-        const unsigned long long bits = (unsigned long long)__double_as_longlong(zk), tag = bits ^ key;
-        u32x4 w;
-        w.x = (unsigned)bits; w.y = (unsigned)(bits >> 32); w.z = (unsigned)tag; w.w = (unsigned)(tag >> 32);
-        if (local) __builtin_amdgcn_raw_buffer_store_b128(w, zp_rs, o + grp * 128, 0, 0);
-        if ((far_rows >> k) & 1u) __builtin_amdgcn_raw_buffer_store_b128(w, zp_rs, o + remote_base, 0, kSc1);
+        const u32x4 w = tagged_granule(zk, key);
+        store_granule(w, zp_rs, o, grp, remote_base, local, ((far_rows >> k) & 1u) != 0);
     };
 
     bool alive = true;
     // ---- where the groups sit: every workgroup reports its XCD, everybody reads the 256 answers ---------------------------
-    if (d.xcc) {
-        local = groups_on_one_xcd(X, d.xcc, alive);
-        X.local = local;
-        if (local) {
-            far_rows = 0;
-#pragma unroll
-            for (int k = 0; k < RPT; ++k) {
-                const int i = row0 + k * kChipThreads;
-                if (i < glo + d.band || i >= ghi - d.band) far_rows |= 1u << k;
-            }
-        }
-    }
+    if (d.xcc) local = place_groups<RPT>(X, d.xcc, row0, glo, ghi, d.band, far_rows, alive);
     const double zero4[4] = {0.0, 0.0, 0.0, 0.0};
     double sum4[4] = {0.0, 0.0, 0.0, 0.0};
     // ---- r0 = b - A x0 ---------------------------------------------------------------------------------------------------
     if (alive && d.x0) {
-        const unsigned long long key_x0 = make_key(kGenX0);
+        const unsigned long long key_x0 = granule_key(ds.nonce, kGenX0);
 #pragma unroll
         for (int k = 0; k < RPT; ++k)
             if (row_on(k)) publish(k, XMEM ? ds.xwork[row0 + k * kChipThreads] : x[XMEM ? 0 : k], key_x0);
@@ -341,7 +304,7 @@ __global__ __launch_bounds__(kChipThreads) void k_pcg_chip_sr(const ChipSrDesc d
         if (alive) alive = exchange4(X, part2_rs, sh4, s_res4, zero4, sum4);   // everybody has read x0 out of the granules before z_0 overwrites them
     }
     {
-        const unsigned long long key0 = make_key(0u);
+        const unsigned long long key0 = granule_key(ds.nonce, 0u);
 #pragma unroll
         for (int k = 0; k < RPT; ++k)
             if (alive && row_on(k)) publish(k, JAC ? dv[JAC ? k : 0] * r[k] : r[k], key0);
@@ -378,7 +341,7 @@ __global__ __launch_bounds__(kChipThreads) void k_pcg_chip_sr(const ChipSrDesc d
         gamma_prev = gamma;
         alpha_prev = alpha;
         ++k_done;
-        const unsigned long long key = make_key((unsigned)k_done);
+        const unsigned long long key = granule_key(ds.nonce, (unsigned)k_done);
         asm volatile("" : "+v"(row0_l), "+v"(far_rows));
 #pragma unroll
         for (int k = 0; k < RPT; ++k) {
@@ -406,12 +369,7 @@ __global__ __launch_bounds__(kChipThreads) void k_pcg_chip_sr(const ChipSrDesc d
             else d.x[i] = x[XMEM ? 0 : k];
         }
     if (v == 0 && t == 0) {
-        Scalars *sc = d.out;
-        sc->k = k_done;
-        sc->res = res;
-        sc->bb = bb;
-        sc->status = alive ? status : DPCG_ERR_STATE;
-        sc->done = 1;
+        store_scalars(d.out, k_done, res, bb, alive, status);
     }
 }
 
@@ -420,19 +378,7 @@ int chip_sr_launch(const ChipSrDesc &ds, hipStream_t s, bool check_only) {
     constexpr int NS = RPT * WMAX;
     constexpr int NLDS = NS < kChipLdsSlots ? NS : kChipLdsSlots;
     const int lds = NLDS * kChipThreads * (int)sizeof(double);
-    static int resident = -1;              // workgroups the occupancy query admits per CU (once per instantiation)
-    if (resident < 0) {
-        if (hipFuncSetAttribute((const void *)k_pcg_chip_sr<RPT, WMAX, JAC, XMEM>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
-            return DPCG_ERR_HIP;
-        int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_pcg_chip_sr<RPT, WMAX, JAC, XMEM>, kChipThreads, (size_t)lds) != hipSuccess)
-            return DPCG_ERR_HIP;
-        resident = per_cu;
-    }
-    if (resident < 1) return DPCG_ERR_STATE;       // the kernel does not fit a CU: refused up front
-    if (check_only) return DPCG_OK;
-    hipLaunchKernelGGL((k_pcg_chip_sr<RPT, WMAX, JAC, XMEM>), dim3(kChipWGs), dim3(kChipThreads), (size_t)lds, s, ds);
-    return DPCG_OK;
+    return chip_launch_resident<k_pcg_chip_sr<RPT, WMAX, JAC, XMEM>>(lds, ds, s, check_only);
 }
 
 }  // namespace

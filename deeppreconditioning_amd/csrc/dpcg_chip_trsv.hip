@@ -235,15 +235,8 @@ __global__ __launch_bounds__(kChipThreads) void k_pcg_chip_trsv(const ChipTrsvDe
         }
 #pragma unroll
         for (int j = 0; j < WMAX; ++j) {
-            const int s = k * WMAX + j;
             const bool on = j < len_k[k];
-            const int c = on ? cj[j] : i;
-            const double a = on ? aj[j] : 0.0;
-            const unsigned del = (unsigned)(c - i + 32768) & 0xffffu;
-            if (s & 1) dl[s >> 1] |= del << 16;
-            else dl[s >> 1] = del;
-            if (s < NREG) vr[s < NREG ? s : 0] = a;
-            else chip_lv[(s - NREG) * kChipThreads + t] = a;
+            put_slot<NREG>(k * WMAX + j, i, on ? cj[j] : i, on ? aj[j] : 0.0, dl, vr, chip_lv + t);
         }
         __builtin_amdgcn_sched_barrier(0);
     }
@@ -313,9 +306,6 @@ __global__ __launch_bounds__(kChipThreads) void k_pcg_chip_trsv(const ChipTrsvDe
     // ---- one triangular solve: the wave walks its blocks of factor `fi` (0: L y = rhs, 1: L^T z = rhs) --------------------------------
     const int wave_id = __builtin_amdgcn_readfirstlane(v * (kChipThreads / 64) + (t >> 6));
     unsigned pub_gen = 0;
-    auto make_key = [&](unsigned gen) -> unsigned long long {
-        return (((unsigned long long)d.nonce << 32) | (unsigned long long)gen) * 0x9E3779B97F4A7C15ull | 1ull;
-    };
     auto tri_solve = [&](int fi, const __amdgpu_buffer_rsrc_t &out_rs, const double (&rhs)[RPT], double (&out)[RPT], unsigned long long key) __attribute__((always_inline)) -> bool {
         const int4 *__restrict__ blk = fi ? d.blk_u : d.blk_l;
         const __amdgpu_buffer_rsrc_t ev_rs = chip_rsrc(fi ? d.val_u : d.val_l, (unsigned)(fi ? d.nent_u : d.nent_l) * 8u);
@@ -433,9 +423,7 @@ __global__ __launch_bounds__(kChipThreads) void k_pcg_chip_trsv(const ChipTrsvDe
             const double res = acc / (act ? D.dg : 1.0);
             if (act) {
                 const int o = (row0 + k * kChipThreads) * 16;
-                const unsigned long long bits = (unsigned long long)__double_as_longlong(res), tag = bits ^ key;
-                u32x4 w;
-                w.x = (unsigned)bits; w.y = (unsigned)(bits >> 32); w.z = (unsigned)tag; w.w = (unsigned)(tag >> 32);
+                const u32x4 w = tagged_granule(res, key);
                 if (local) __builtin_amdgcn_raw_buffer_store_b128(w, out_rs, o + grp * 128, 0, 0);
                 if ((far_rows >> k) & 1u) __builtin_amdgcn_raw_buffer_store_b128(w, out_rs, o + remote_base, 0, kSc1);
             }
@@ -468,9 +456,7 @@ __global__ __launch_bounds__(kChipThreads) void k_pcg_chip_trsv(const ChipTrsvDe
                 const double res = rhs[kk] / (on0 ? dg[kk] : 1.0);
                 if (on0) {
                     const int o = (row0 + kk * kChipThreads) * 16;
-                    const unsigned long long bits = (unsigned long long)__double_as_longlong(res), tag = bits ^ key;
-                    u32x4 w;
-                    w.x = (unsigned)bits; w.y = (unsigned)(bits >> 32); w.z = (unsigned)tag; w.w = (unsigned)(tag >> 32);
+                    const u32x4 w = tagged_granule(res, key);
                     if (local) __builtin_amdgcn_raw_buffer_store_b128(w, out_rs, o + grp * 128, 0, 0);
                     if ((far_rows >> kk) & 1u) __builtin_amdgcn_raw_buffer_store_b128(w, out_rs, o + remote_base, 0, kSc1);
                 }
@@ -496,9 +482,9 @@ __global__ __launch_bounds__(kChipThreads) void k_pcg_chip_trsv(const ChipTrsvDe
     };
     // z = L^-T (L^-1 r) for the own rows (cg.py:61,81); y lives in q's registers (q is dead between cg.py:80 and the next cg.py:75)
     auto apply_m = [&]() -> bool {
-        const unsigned long long key_y = make_key(++pub_gen);
+        const unsigned long long key_y = granule_key(d.nonce, ++pub_gen);
         bool ok = tri_solve(0, y_rs, r, q, key_y);
-        const unsigned long long key_z = make_key(++pub_gen);
+        const unsigned long long key_z = granule_key(d.nonce, ++pub_gen);
         if (ok) ok = tri_solve(1, w_rs, q, z, key_z);
         const unsigned long long ts0 = tick();
         const bool all_ok = __syncthreads_and(ok ? 1 : 0) != 0;
@@ -689,12 +675,7 @@ __global__ __launch_bounds__(kChipThreads) void k_pcg_chip_trsv_res(const ChipTr
     double *const f_val = res_lds;
     unsigned *const f_off = reinterpret_cast<unsigned *>(res_lds + NS * kChipThreads);
     const int t = threadIdx.x, lane = t & 63;
-    const int v = ((int)blockIdx.x & 7) * (kChipWGs / 8) + ((int)blockIdx.x >> 3);
-    const int row0 = v * d.per + t;
-    const int grp = (int)blockIdx.x & 7, rank = (int)blockIdx.x >> 3;
-    const int glo = grp * (kChipWGs / 8) * d.per;
-    const int ghi = (glo + (kChipWGs / 8) * d.per < d.n) ? glo + (kChipWGs / 8) * d.per : d.n;
-    const int remote_base = (d.n + kChipZpPad) * 16;
+    const ChipGeom G = chip_geom(d.per, d.n, t);
     const unsigned gran_bytes = 2u * (unsigned)(d.n + kChipZpPad) * 16u;
     const __amdgpu_buffer_rsrc_t zp_rs = chip_rsrc(d.zp, gran_bytes);
     const __amdgpu_buffer_rsrc_t y_rs = chip_rsrc(d.ypub, gran_bytes);
@@ -712,7 +693,7 @@ __global__ __launch_bounds__(kChipThreads) void k_pcg_chip_trsv_res(const ChipTr
     double bb_loc = 0.0;
 #pragma unroll
     for (int k = 0; k < RPT; ++k) {
-        const int loc = k * kChipThreads + t, i = row0 + k * kChipThreads;
+        const int loc = k * kChipThreads + t, i = G.row0 + k * kChipThreads;
         const bool valid = loc < d.per && i < d.n;
         const int ic = valid ? i : 0;
         const int rs = d.rp[ic], re = d.rp[ic + 1];
@@ -722,7 +703,7 @@ __global__ __launch_bounds__(kChipThreads) void k_pcg_chip_trsv_res(const ChipTr
         r[k] = valid ? d.b[ic] : 0.0;
         p[k] = q[k] = z[k] = 0.0;
         if (valid) bb_loc += r[k] * r[k];
-        meta[k] = t < d.tstride ? d.fmeta[(v * RPT + k) * d.tstride + t] : 0;
+        meta[k] = t < d.tstride ? d.fmeta[(G.v * RPT + k) * d.tstride + t] : 0;
 #pragma unroll
         for (int j = 0; j < WMAX; ++j) {
             const int s = k * WMAX + j;
@@ -730,26 +711,22 @@ __global__ __launch_bounds__(kChipThreads) void k_pcg_chip_trsv_res(const ChipTr
             const int e = on ? rs + j : 0;
             const int c = on ? d.ci[e] : i;
             va[s] = on ? d.val[e] : 0.0;
-            const unsigned del = (unsigned)(c - i + 32768) & 0xffffu;
-            if (s & 1) dl[s >> 1] |= del << 16;
-            else dl[s >> 1] = del;
+            put_col_offset(dl, s, (unsigned)(c - i + 32768) & 0xffffu);
         }
     }
     {
         unsigned fo[NOFF];
 #pragma unroll
         for (int k = 0; k < RPT; ++k) {
-            const int i = row0 + k * kChipThreads;
+            const int i = G.row0 + k * kChipThreads;
 #pragma unroll
             for (int j = 0; j < WMAX; ++j) {
                 const int s = k * WMAX + j;
-                const size_t e = ((size_t)v * NS + s) * d.tstride + t;
+                const size_t e = ((size_t)G.v * NS + s) * d.tstride + t;
                 const bool has = t < d.tstride;                   // (small systems: the plan holds the threads that can own a row)
                 f_val[s * kChipThreads + t] = has ? d.fval[has ? e : 0] : (j == WMAX - 1 ? 1.0 : 0.0);
                 const int c = has ? d.fcol[has ? e : 0] : -1;
-                const unsigned del = c >= 0 ? (unsigned)(c - i + 32768) & 0xffffu : 0u;
-                if (s & 1) fo[s >> 1] |= del << 16;
-                else fo[s >> 1] = del;
+                put_col_offset(fo, s, c >= 0 ? (unsigned)(c - i + 32768) & 0xffffu : 0u);
             }
         }
 #pragma unroll
@@ -761,21 +738,21 @@ __global__ __launch_bounds__(kChipThreads) void k_pcg_chip_trsv_res(const ChipTr
     // q = A p_k for the own rows, the gathered entries of p_k recomputed from the granules {z_k, p_{k-1}} (dpcg_chip.hip)
     auto spmv = [&](double beta) {
         u32x4 g[2][WMAX];
-        int glo_l = glo, span_l = local ? ghi - glo : 0;
-        const int local_shift = grp * 128;
+        int glo_l = G.glo, span_l = local ? G.ghi - G.glo : 0;
+        const int local_shift = G.grp * 128;
         asm volatile("" : "+s"(glo_l), "+s"(span_l));
 #pragma unroll
         for (int e = 0; e < NOFF; ++e) asm volatile("" : "+v"(dl[e]));
         asm volatile("" : "+v"(lens));
         auto request = [&](int k, u32x4 (&gk)[WMAX]) {
-            const int rowk = row0 + k * kChipThreads;
+            const int rowk = G.row0 + k * kChipThreads;
 #pragma unroll
             for (int j = 0; j < WMAX; ++j) {
                 const int s = k * WMAX + j;
                 const int del = (int)((dl[s >> 1] >> (16 * (s & 1))) & 0xffffu);
                 const int c = rowk + del - 32768;
                 const bool own = (unsigned)(c - glo_l) < (unsigned)span_l;
-                gk[j] = __builtin_amdgcn_raw_buffer_load_b128(zp_rs, c * 16 + (own ? local_shift : remote_base), 0, kSc1);
+                gk[j] = __builtin_amdgcn_raw_buffer_load_b128(zp_rs, c * 16 + (own ? local_shift : G.remote_base), 0, kSc1);
             }
         };
         request(0, g[0]);
@@ -800,26 +777,21 @@ __global__ __launch_bounds__(kChipThreads) void k_pcg_chip_trsv_res(const ChipTr
     auto tr_add = [&](int phase, unsigned long long dt) {
         if (TRACE && lane == 0) s_tr[(t >> 6) * 8 + phase] += dt;
     };
-    Exchange X;
-    X.part_rs = chip_rsrc(d.part, (unsigned)kChipSlotBytes);
-    X.v = v; X.grp = grp; X.rank = rank; X.sh = sh; X.s_res = s_res; X.s_flag = &s_flag; X.err = d.err;
+    Exchange X = make_exchange(d.part, G.v, G.grp, G.rank, sh, s_res, &s_flag, d.err);
     auto chip_sum2 = [&](double a, double b2, bool publish, double &ra, double &rb) -> bool { return exchange2(X, a, b2, publish, ra, rb); };
     unsigned far_rows = 0xffu;
-    int row0_l = row0;
+    int row0_l = G.row0;
     auto publish_zp = [&](int k, double zk, double pk) {
         const int o = (row0_l + k * kChipThreads) * 16;
-        if (local) __builtin_amdgcn_raw_buffer_store_b128(pack_f64x2(zk, pk), zp_rs, o + grp * 128, 0, 0);
-        if ((far_rows >> k) & 1u) __builtin_amdgcn_raw_buffer_store_b128(pack_f64x2(zk, pk), zp_rs, o + remote_base, 0, kSc1);
+        if (local) __builtin_amdgcn_raw_buffer_store_b128(pack_f64x2(zk, pk), zp_rs, o + G.grp * 128, 0, 0);
+        if ((far_rows >> k) & 1u) __builtin_amdgcn_raw_buffer_store_b128(pack_f64x2(zk, pk), zp_rs, o + G.remote_base, 0, kSc1);
     };
     unsigned pub_gen = 0;
-    auto make_key = [&](unsigned gen) -> unsigned long long {
-        return (((unsigned long long)d.nonce << 32) | (unsigned long long)gen) * 0x9E3779B97F4A7C15ull | 1ull;
-    };
     constexpr int kNoCol = 0x7ffffff0;
     // one triangular solve (fi = 0: L y = rhs, 1: L^T z = rhs) on the resident factor
     auto tri_solve = [&](int fi, int nlev, const __amdgpu_buffer_rsrc_t &out_rs, const double (&rhs)[RPT], double (&out)[RPT], unsigned long long key) __attribute__((always_inline)) -> bool {
         const unsigned klo = (unsigned)key, khi = (unsigned)(key >> 32);
-        int glo_l = glo, span_l = local ? ghi - glo : 0;
+        int glo_l = G.glo, span_l = local ? G.ghi - G.glo : 0;
         asm volatile("" : "+s"(glo_l), "+s"(span_l));
         int tl = t;
         asm volatile("" : "+v"(tl));                              // (keeps the LDS addresses of the loop below out of hoisted registers)
@@ -827,12 +799,10 @@ __global__ __launch_bounds__(kChipThreads) void k_pcg_chip_trsv_res(const ChipTr
         const unsigned *fo = f_off + tl;
         const int lsh = 8 + 6 * fi;
         auto publish = [&](int k, double res) {
-            const int o = (row0 + k * kChipThreads) * 16;
-            const unsigned long long bits = (unsigned long long)__double_as_longlong(res), tag = bits ^ key;
-            u32x4 w;
-            w.x = (unsigned)bits; w.y = (unsigned)(bits >> 32); w.z = (unsigned)tag; w.w = (unsigned)(tag >> 32);
-            if (local) __builtin_amdgcn_raw_buffer_store_b128(w, out_rs, o + grp * 128, 0, 0);
-            if ((far_rows >> k) & 1u) __builtin_amdgcn_raw_buffer_store_b128(w, out_rs, o + remote_base, 0, kSc1);
+            const int o = (G.row0 + k * kChipThreads) * 16;
+            const u32x4 w = tagged_granule(res, key);
+            if (local) __builtin_amdgcn_raw_buffer_store_b128(w, out_rs, o + G.grp * 128, 0, 0);
+            if ((far_rows >> k) & 1u) __builtin_amdgcn_raw_buffer_store_b128(w, out_rs, o + G.remote_base, 0, kSc1);
         };
         const unsigned long long tk0 = tick();
         // level 0: no dependencies -- slot by slot
@@ -857,9 +827,9 @@ __global__ __launch_bounds__(kChipThreads) void k_pcg_chip_trsv_res(const ChipTr
             const int slc = on ? B.e0 + j : 0;
             const unsigned w = fo[(slc >> 1) * kChipThreads];
             const int del = (int)((w >> (16 * (slc & 1))) & 0xffffu);
-            const int c = row0 + B.k * kChipThreads + del - 32768;
+            const int c = G.row0 + B.k * kChipThreads + del - 32768;
             const bool own = (unsigned)(c - glo_l) < (unsigned)span_l;
-            return on ? c * 16 + (own ? grp * 128 : remote_base) : kNoCol;
+            return on ? c * 16 + (own ? G.grp * 128 : G.remote_base) : kNoCol;
         };
         auto next_block = [&](Blk &B) __attribute__((always_inline)) -> bool {          // false: the levels are used up (the same for the whole wave)
             while (__ballot(mk != 0) == 0) {
@@ -972,9 +942,9 @@ __global__ __launch_bounds__(kChipThreads) void k_pcg_chip_trsv_res(const ChipTr
         return ok != 0;
     };
     auto apply_m = [&]() -> bool {
-        const unsigned long long key_y = make_key(++pub_gen);
+        const unsigned long long key_y = granule_key(d.nonce, ++pub_gen);
         bool ok = tri_solve(0, d.nlev_l, y_rs, r, q, key_y);
-        const unsigned long long key_z = make_key(++pub_gen);
+        const unsigned long long key_z = granule_key(d.nonce, ++pub_gen);
         if (ok) ok = tri_solve(1, d.nlev_u, w_rs, q, z, key_z);
         const unsigned long long ts0 = tick();
         const bool all_ok = __syncthreads_and(ok ? 1 : 0) != 0;
@@ -985,18 +955,7 @@ __global__ __launch_bounds__(kChipThreads) void k_pcg_chip_trsv_res(const ChipTr
     __syncthreads();                                              // (the factor's slice is in the LDS)
     bool alive = true;
     double dummy = 0.0, dummy2 = 0.0;
-    if (d.xcc) {
-        local = groups_on_one_xcd(X, d.xcc, alive);
-        X.local = local;
-        if (local) {
-            far_rows = 0;
-#pragma unroll
-            for (int k = 0; k < RPT; ++k) {
-                const int i = row0 + k * kChipThreads;
-                if (i < glo + d.band || i >= ghi - d.band) far_rows |= 1u << k;
-            }
-        }
-    }
+    if (d.xcc) local = place_groups<RPT>(X, d.xcc, G.row0, G.glo, G.ghi, d.band, far_rows, alive);
     // ---- cg.py:58-67 -------------------------------------------------------------------------------------------------
     if (alive && d.x0) {
 #pragma unroll
@@ -1028,7 +987,7 @@ __global__ __launch_bounds__(kChipThreads) void k_pcg_chip_trsv_res(const ChipTr
     int k_done = 0, status = DPCG_MAX_ITER;
     bool stop = false;
     if (alive) {
-        if (v == 0 && t == 0 && d.hist_cap > 0) d.hist[0] = res;
+        if (G.v == 0 && t == 0 && d.hist_cap > 0) d.hist[0] = res;
         const bool conv = (res < d.rtol_sq) || (tt < d.atol_sq);
         if (conv) { stop = true; status = DPCG_OK; }
         else if (!(res == res)) { stop = true; status = DPCG_BREAKDOWN; }
@@ -1066,25 +1025,20 @@ __global__ __launch_bounds__(kChipThreads) void k_pcg_chip_trsv_res(const ChipTr
         rz = rz_new;
         res = rr / bb;                                            // cg.py:86
         ++k_done;
-        if (v == 0 && t == 0 && k_done < d.hist_cap) d.hist[k_done] = res;
+        if (G.v == 0 && t == 0 && k_done < d.hist_cap) d.hist[k_done] = res;
         const bool conv = (res < d.rtol_sq) || (rr < d.atol_sq);  // cg.py:71
         if (conv) { stop = true; status = DPCG_OK; }
         else if (!(res == res)) { stop = true; status = DPCG_BREAKDOWN; }
     }
 #pragma unroll
     for (int k = 0; k < RPT; ++k)
-        if (alive && row_on(k)) d.x[row0 + k * kChipThreads] = x[k];
+        if (alive && row_on(k)) d.x[G.row0 + k * kChipThreads] = x[k];
     if (TRACE && d.dbg) {
         __syncthreads();
-        if (t < 64) d.dbg[v * 64 + t] = s_tr[t];
+        if (t < 64) d.dbg[G.v * 64 + t] = s_tr[t];
     }
-    if (v == 0 && t == 0) {
-        Scalars *sc = d.out;
-        sc->k = k_done;
-        sc->res = res;
-        sc->bb = bb;
-        sc->status = alive ? status : DPCG_ERR_STATE;
-        sc->done = 1;
+    if (G.v == 0 && t == 0) {
+        store_scalars(d.out, k_done, res, bb, alive, status);
     }
 }
 
@@ -1092,19 +1046,7 @@ template <int RPT, int WMAX, bool TRACE = false>
 int chip_trsv_res_launch(const ChipTrsvDesc &d, hipStream_t s, bool check_only) {
     constexpr int NS = RPT * WMAX;
     const int lds = NS * kChipThreads * (int)sizeof(double) + ((NS + 1) / 2) * kChipThreads * (int)sizeof(unsigned);
-    static int resident = -1;
-    if (resident < 0) {
-        if (hipFuncSetAttribute((const void *)k_pcg_chip_trsv_res<RPT, WMAX, TRACE>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
-            return DPCG_ERR_HIP;
-        int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_pcg_chip_trsv_res<RPT, WMAX, TRACE>, kChipThreads, (size_t)lds) != hipSuccess)
-            return DPCG_ERR_HIP;
-        resident = per_cu;
-    }
-    if (resident < 1) return DPCG_ERR_STATE;
-    if (check_only) return DPCG_OK;
-    hipLaunchKernelGGL((k_pcg_chip_trsv_res<RPT, WMAX, TRACE>), dim3(kChipWGs), dim3(kChipThreads), (size_t)lds, s, d);
-    return DPCG_OK;
+    return chip_launch_resident<k_pcg_chip_trsv_res<RPT, WMAX, TRACE>>(lds, d, s, check_only);
 }
 
 template <int RPT, int WMAX, int WL, bool TRACE = false>
@@ -1112,19 +1054,7 @@ int chip_trsv_launch(const ChipTrsvDesc &d, hipStream_t s, bool check_only) {
     constexpr int NS = RPT * WMAX;
     constexpr int NLDS = NS < kChipLdsSlots ? NS : kChipLdsSlots;
     const int lds = NLDS * kChipThreads * (int)sizeof(double);
-    static int resident = -1;
-    if (resident < 0) {
-        if (hipFuncSetAttribute((const void *)k_pcg_chip_trsv<RPT, WMAX, WL, TRACE>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
-            return DPCG_ERR_HIP;
-        int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_pcg_chip_trsv<RPT, WMAX, WL, TRACE>, kChipThreads, (size_t)lds) != hipSuccess)
-            return DPCG_ERR_HIP;
-        resident = per_cu;
-    }
-    if (resident < 1) return DPCG_ERR_STATE;
-    if (check_only) return DPCG_OK;
-    hipLaunchKernelGGL((k_pcg_chip_trsv<RPT, WMAX, WL, TRACE>), dim3(kChipWGs), dim3(kChipThreads), (size_t)lds, s, d);
-    return DPCG_OK;
+    return chip_launch_resident<k_pcg_chip_trsv<RPT, WMAX, WL, TRACE>>(lds, d, s, check_only);
 }
 
 }  // namespace
