@@ -97,6 +97,8 @@ SIGNATURES = {
     "dpcg_guess_info": (_int, [_p, _p]),
     "dpcg_guess_get_basis": (_int, [_p, _p, _p]),
     "dpcg_guess_destroy": (_int, [_p]),
+    "dpcg_set_nullspace": (_int, [_p, _int, _p, _int, _dbl, _p]),
+    "dpcg_get_nullspace": (_int, [_p, C.POINTER(_int), _p]),
     "dpcg_solve": (_int, [_p, _p, _p, _p, _dbl, _dbl, _int, _int, _p, C.POINTER(_int), C.POINTER(_dbl),
                           C.POINTER(_dbl), _p, _p, _p]),
     "dpcg_solve_batch": (_int, [_int, _p, _p, _p, _p, _dbl, _dbl, _int, _int, _int, _p, _p, _p, _p]),

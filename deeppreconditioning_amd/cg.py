@@ -42,7 +42,8 @@ def _system_and_device(A, b):
 
 
 def preconditioned_conjugate_gradient(A, b, M, x0=None, x_true=None, rtol=1e-8, max_iter=1024, *,
-                                      mixed_precision=False, compact_values=False, details=False, recurrence="standard"):
+                                      mixed_precision=False, compact_values=False, details=False, recurrence="standard",
+                                      nullspace=None):
     """PCG, cg.py:50-90.  Returns `(duration_seconds, iterations, info)`.
 
     `rtol` is compared with <r,r>/<b,b> (squared ratio, cg.py:71); the first test uses z0
@@ -53,7 +54,9 @@ def preconditioned_conjugate_gradient(A, b, M, x0=None, x_true=None, rtol=1e-8, 
     bit-identical results, 8 instead of 12 bytes per non-zero; `details=True` returns the full
     `SolveResult` (status 0 converged / 1 max_iter / 2 breakdown, residual history, x); `recurrence="single_reduction"` asks for
     Chronopoulos and Gear's single-synchronisation form of the loop (`CsrSystem.solve`: M = None or Jacobi on chip-sized systems,
-    other bits than the reference's recurrence, which stays the default).
+    other bits than the reference's recurrence, which stays the default); `nullspace="constant"` or an (n, k) basis, k <= 4,
+    attaches the null space of a singular (all-Neumann) system -- `CsrSystem.set_nullspace` -- which the loop then projects out
+    (the minimum-norm solution; no reference counterpart).  The default None changes nothing.
 
     The plain return value follows the reference to the letter: `info` is always 0 (cg.py:90), and a NaN
     breakdown (b = 0, NaN input, singular M), on which the reference keeps looping because `nan < rtol` is
@@ -62,7 +65,9 @@ def preconditioned_conjugate_gradient(A, b, M, x0=None, x_true=None, rtol=1e-8, 
     del x_true  # unused by the reference's return value
     system = _system_and_device(A, b)
     system.set_preconditioner(M)
-    flags = (L.SPMV_F32 if mixed_precision else 0) | (L.VAL32_IF_LOSSLESS if compact_values else 0)
+    if nullspace is not None:
+        system.set_nullspace(nullspace)
+    flags =(L.SPMV_F32 if mixed_precision else 0) | (L.VAL32_IF_LOSSLESS if compact_values else 0)
     result = system.solve(b, x0, rtol_sq=float(rtol), max_iter=int(max_iter), flags=flags, recurrence=recurrence)
     if details:
         return result
@@ -70,12 +75,15 @@ def preconditioned_conjugate_gradient(A, b, M, x0=None, x_true=None, rtol=1e-8, 
     return result.seconds, iterations, 0
 
 
-def conjugate_gradient(A, b, x0=None, x_true=None, rtol=1e-8, max_iter=1024, *, recurrence="standard"):
+def conjugate_gradient(A, b, x0=None, x_true=None, rtol=1e-8, max_iter=1024, *, recurrence="standard", nullspace=None):
     """Unpreconditioned CG, cg.py:20-47.  Returns `(errors, x_hat)` with
     `errors[k] = (A-norm error of x_k or 0, <r_k,r_k>/<b,b>)` as 0-d tensors.  `recurrence="single_reduction"` (keyword-only, not
-    together with `x_true`): see `preconditioned_conjugate_gradient`."""
+    together with `x_true`) and `nullspace` (keyword-only, not together with `x_true` either): see
+    `preconditioned_conjugate_gradient`."""
     system = _system_and_device(A, b)
     system.set_preconditioner(None)
+    if nullspace is not None:
+        system.set_nullspace(nullspace)
     result = system.solve(b, x0, rtol_sq=float(rtol), max_iter=int(max_iter), flags=L.INIT_CHECK_R, x_true=x_true,
                           recurrence=recurrence)
     res = torch.from_numpy(result.res_history.copy()).to(system.device)

@@ -1464,6 +1464,9 @@ extern "C" int dpcg_set_precond_amg_precision(dpcg_handle_t h, double theta, int
     if (precision == DPCG_AMG_FP32 && smoother == DPCG_AMG_GAUSS_SEIDEL)
         return invalid("dpcg_set_precond_amg_precision: the fp32 cycle takes DPCG_AMG_JACOBI and DPCG_AMG_CHEBYSHEV only (Gauss-Seidel's "
                        "cost is its colour passes, not its bytes)");
+    if (h->ns)
+        return invalid("dpcg_set_precond_amg: the handle has a null space attached (a singular system): the hierarchy's exact coarse solve "
+                       "would invert a singular matrix");
     hipStream_t s = (hipStream_t)stream;
     SetupScope scope(s, true);
     AmgState *old = h->amg_parked;

@@ -186,6 +186,12 @@ int solve_chip_one(dpcg_system *h, SolveCall c);          // M = I / Jacobi
 int solve_chip_sr_one(dpcg_system *h, SolveCall c);       // ... with the single-reduction recurrence
 int solve_chip_llt_one(dpcg_system *h, SolveCall c);      // M = L L^T multiplied
 int solve_chip_trsv_one(dpcg_system *h, SolveCall c);     // M = (L L^T)^-1 by two triangular solves
+// dpcg_nullspace.hip: singular systems with an attached null space (dpcg_set_nullspace).  Why a solve with these arguments is refused
+// (nullptr: it is not); the solve itself, whatever the system's size; the check of A Z = 0 again after dpcg_update_values; the release
+const char *nullspace_refusal(const dpcg_system *h, int flags, const double *x_true);
+int solve_nullspace_one(dpcg_system *h, SolveCall c);
+int nullspace_values_changed(dpcg_system *h, hipStream_t s);
+void free_nullspace(dpcg_system *h);
 // dpcg_amg.hip: the smoothed-aggregation hierarchy -- free, launches of one V-cycle, sum over levels of nnz(A_l) + 2 nnz(P_l), the apply
 // (part_rz: the last kernel leaves the partials of <r, z>), and how many partials an in-loop apply leaves (0: none)
 void free_amg(AmgState *&S);

@@ -215,6 +215,7 @@ void launch_sfs_block_max(const int32_t *blk, int nblk, const int32_t *lo_rowptr
 
 struct AmgState;   // dpcg_amg.hip: a smoothed-aggregation hierarchy
 struct FsaiCache;  // dpcg_fsai.hip: what the symbolic phase of an FSAI factor leaves on the handle
+struct NullSpace;  // dpcg_nullspace.hip: the null space attached to a singular (semi-definite) system and its solve state
 
 // (dpcg_chip_trsv.hip; the comment is with ChipTrsvDesc below)
 struct ChipTrsvLists {
@@ -323,6 +324,8 @@ struct dpcg_system {
     // guesses made for this handle (dpcg_destroy takes their buffers and their system away; the objects are the caller's)
     uint64_t values_epoch = 0;
     std::vector<dpcg_guess *> guesses;
+    // dpcg_set_nullspace (dpcg_nullspace.hip): null = a definite system, every solve takes the paths it always took
+    dpcg::NullSpace *ns = nullptr;
 };
 
 namespace dpcg {

@@ -727,6 +727,12 @@ extern "C" int dpcg_solve(dpcg_handle_t h, const double *b, const double *x0, do
                           double *final_res, double *seconds, double *res_history, const double *x_true,
                           double *err_history) {
     DPCG_TRY(check_solve_args(h, b, max_iter, flags, x_true, err_history));
+    if (h->ns) {                             // a singular system with its null space attached: its own driver, whatever the size (dpcg_nullspace.hip)
+        if (const char *why = nullspace_refusal(h, flags, x_true)) return invalid(why);
+        h->last_recurrence = 0;
+        h->chip_shared_known = false;
+        return solve_nullspace_one(h, {b, x0, x, rtol_sq, atol_sq, max_iter, flags, (hipStream_t)stream, iters, final_res, seconds, res_history});
+    }
     const bool one_launch_open = co_residency().open();      // (false during the cool-down after repeated co-residency timeouts)
     if (flags & DPCG_SINGLE_REDUCTION) {
         if (const char *why = chip_sr_refusal(h, flags, x_true)) return invalid(why);     // (nothing of the handle has been touched)
@@ -794,6 +800,8 @@ extern "C" int dpcg_solve_batch(int count, dpcg_handle_t *handles, const double 
     if (n_streams > 8) n_streams = 8;
     if (n_streams > count) n_streams = count;
     for (int i = 0; i < count; ++i) DPCG_TRY(check_solve_args(handles[i], b[i], max_iter, flags, nullptr, nullptr));
+    for (int i = 0; i < count; ++i)
+        if (handles[i]->ns) return invalid("dpcg_solve_batch: a handle with a null space is solved by dpcg_solve, one at a time");
     if (flags & DPCG_SINGLE_REDUCTION) {
         for (int i = 0; i < count; ++i)
             if (const char *why = chip_sr_refusal(handles[i], flags, nullptr)) return invalid(why);     // (nothing of any handle has been touched)

@@ -660,9 +660,13 @@ class CsrSystem:
             if self._keep and (v.dtype != torch.float64 or v.data_ptr() % 16):
                 v = v.to(torch.float64).clone()
             with torch.cuda.device(self.device):
-                L.check(L.lib().dpcg_update_values(self._h, _dev_ptr(v), L.F64 if v.dtype == torch.float64 else L.F32,
-                                                   L.DEVICE, _stream()))
-            if self._keep:                      # a system created from device arrays borrows them: borrow the new ones likewise --
+                try:
+                    L.check(L.lib().dpcg_update_values(self._h, _dev_ptr(v), L.F64 if v.dtype == torch.float64 else L.F32,
+                                                       L.DEVICE, _stream()))
+                except L.DpcgError:
+                    self._kept_on_error = v     # (a failed null-space check comes after the handle has borrowed the new buffer)
+                    raise
+            if self._keep:                     # a system created from device arrays borrows them: borrow the new ones likewise --
                 self._keep = (self._keep[0], self._keep[1], v)      # only once the call has succeeded (the handle still points at the old buffer otherwise)
         else:
             a = values.detach().cpu().numpy() if isinstance(values, torch.Tensor) else np.asarray(values)
@@ -683,6 +687,41 @@ class CsrSystem:
         perm = np.empty(self.n, dtype=np.int32)
         L.check(L.lib().dpcg_get_permutation(self._h, C.byref(flag), _np_ptr(perm), None))
         return perm if flag.value else None
+
+    def set_nullspace(self, Z, check_tol: float = 1e-8) -> None:
+        """Attach the null space of a singular (symmetric positive semi-definite) system -- a closed, all-Neumann domain -- so
+        that `solve` projects it out inside PCG and returns the minimum-norm solution (dpcg_set_nullspace, include/dpcg.h).
+
+        `Z`: "constant" (the constant vector, never stored), an array or tensor of shape (n,) or (n, k), k <= 4, with any linearly
+        independent columns in the caller's numbering (orthonormalised by the library), or None to clear.  `check_tol` > 0 checks
+        max|A z| <= check_tol ||A||_inf ||z||_inf for every column, now and after every `update_values`; <= 0: no check.
+        Raises DpcgError (ERR_INVALID) for k > 4, a rank-deficient Z, non-finite entries and a failed check."""
+        with torch.cuda.device(self.device):
+            if Z is None:
+                L.check(L.lib().dpcg_set_nullspace(self._h, 0, None, L.HOST, 0.0, _stream()))
+                return
+            if isinstance(Z, str):
+                if Z != "constant":
+                    raise ValueError("the only named null space is 'constant'")
+                L.check(L.lib().dpcg_set_nullspace(self._h, 1, None, L.HOST, float(check_tol), _stream()))
+                return
+            a = Z.detach().cpu().numpy() if isinstance(Z, torch.Tensor) else np.asarray(Z)
+            a = a.reshape(self.n, 1) if a.ndim == 1 and a.size == self.n else a
+            if a.ndim != 2 or a.shape[0] != self.n or a.shape[1] < 1:
+                raise ValueError(f"expected a null-space basis of shape ({self.n}, k)")
+            cols = np.asfortranarray(a, dtype=np.float64)       # column-major n x k
+            L.check(L.lib().dpcg_set_nullspace(self._h, int(cols.shape[1]), cols.ctypes.data_as(C.c_void_p), L.HOST,
+                                               float(check_tol), _stream()))
+
+    def nullspace(self):
+        """The attached null space as an (n, k) numpy array with orthonormal columns in the caller's numbering, or None."""
+        k = C.c_int(0)
+        L.check(L.lib().dpcg_get_nullspace(self._h, C.byref(k), None))
+        if k.value == 0:
+            return None
+        out = np.empty((self.n, k.value), dtype=np.float64, order="F")
+        L.check(L.lib().dpcg_get_nullspace(self._h, C.byref(k), out.ctypes.data_as(C.c_void_p)))
+        return out
 
     # -- constructors ----------------------------------------------------------------------
     @classmethod

@@ -46,6 +46,41 @@ def rhs(n: int, seed: int = 0, device=None) -> torch.Tensor:
     return torch.from_numpy(np.random.default_rng(seed).uniform(-1.0, 1.0, n)).to(device)
 
 
+def neumann_csr(dims, coefficient_seed=None):
+    """Host-side pure-Neumann pressure matrix of a closed box: the 5-point (len(dims) == 2) or 7-point (3) graph Laplacian of a
+    dims[0] x dims[1] [x dims[2]] grid, first index fastest -- a_ij = -w_ij for neighbours, a_ii = the sum of the row's weights, so
+    every row sums to zero: symmetric positive SEMI-definite, its null space the constants (`CsrSystem.set_nullspace("constant")`).
+    `coefficient_seed`: None gives unit weights; an int draws one weight 10^U(-1, 1) per edge from `default_rng(seed)`, axis by
+    axis in row order (a variable-coefficient, e.g. two-phase, system).  Returns a scipy CSR matrix with sorted int32 indices."""
+    import scipy.sparse as sp
+    dims = tuple(int(d) for d in dims)
+    if len(dims) not in (2, 3) or min(dims) < 1:
+        raise ValueError("dims must be 2 or 3 positive grid sizes")
+    rows = int(np.prod(dims))
+    idx = np.arange(rows, dtype=np.int64)
+    rng = None if coefficient_seed is None else np.random.default_rng(coefficient_seed)
+    r_list, c_list, v_list = [], [], []
+    diag = np.zeros(rows)
+    off = 1
+    for d in dims:
+        lo = idx[(idx // off) % d < d - 1]            # the lower end of every edge along this axis
+        w = np.ones(lo.size) if rng is None else 10.0 ** rng.uniform(-1.0, 1.0, lo.size)
+        r_list += [lo, lo + off]
+        c_list += [lo + off, lo]
+        v_list += [-w, -w]
+        np.add.at(diag, lo, w)
+        np.add.at(diag, lo + off, w)
+        off *= d
+    r_list.append(idx)
+    c_list.append(idx)
+    v_list.append(diag)
+    A = sp.csr_matrix((np.concatenate(v_list), (np.concatenate(r_list), np.concatenate(c_list))), shape=(rows, rows))
+    A.sort_indices()
+    A.indices = A.indices.astype(np.int32)
+    A.indptr = A.indptr.astype(np.int32)
+    return A
+
+
 def unstructured_like_csr(dim: int, n: int, seed: int = 0):
     """Host-side stand-in for an OpenFOAM pressure matrix: D (P A P^T) D of the
     Poisson matrix with a seeded random symmetric permutation P and D = diag(U(0.5, 2)).  Returns a scipy CSR

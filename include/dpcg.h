@@ -487,6 +487,41 @@ int dpcg_solve(dpcg_handle_t h, const double *b, const double *x0, double *x, do
                int max_iter, int flags, dpcg_stream_t stream, int *iters, double *final_res, double *seconds,
                double *res_history, const double *x_true, double *err_history);
 
+/* ---- singular systems: a null space attached to the handle, projected inside PCG -------------------------------------
+ * A closed domain (all-Neumann boundaries, or several closed regions in one mesh) gives a symmetric positive SEMI-definite
+ * matrix whose kernel is the constants (one constant per region).  Not in the reference, whose systems are all definite.
+ * With Z (n x k, orthonormal columns, 1 <= k <= 4) attached and P = I - Z Z^T, dpcg_solve runs
+ *     b' = P b;  r = b' - A x0 (x0 given: r = P r once);  bb = <b',b'>;  zt = M r;  s = Z^T zt;  t = Z^T r;
+ *     rho = <r,zt> - t^T s;  p = zt - Z s;   first test: <p,p> = <zt,zt> - s^T s, or <r,r> with DPCG_INIT_CHECK_R
+ *     each update:  q = A p;  alpha = rho / <p,q>;  x += alpha p;  r -= alpha q
+ *                   zt = M r                      (NOT projected in memory)
+ *                   s = Z^T zt;  t = Z^T r        (k numbers each)
+ *                   rho' = <r,zt> - t^T s         (= <r, P zt>)
+ *                   p = (zt - Z s) + (rho'/rho) p (the projection lives only in this update)
+ *     end:          x = x - Z (Z^T x)             (the minimum-norm solution; also after max_iter updates and after a breakdown)
+ * The history, the stopping test, the first test, the cap and the NaN breakdown mean what they mean above, with b' for b.
+ * An update is the SpMV with its partials of <p,q>, one pass over q, r (dinv) that leaves per-workgroup partials of <r,zt>, <r,r>,
+ * Z^T zt and Z^T r (2 + 2k sums, each summed in one fixed order: no float atomics), and one pass over r (dinv), p, x -- for M = I
+ * and Jacobi the launches and reduction rounds of a definite solve.  Any other M: the r update, the handle's apply, one dot kernel.
+ *
+ * dpcg_set_nullspace: k = 0 clears.  Z == NULL with k == 1: the constant vector 1/sqrt(n), never read from memory (the vector
+ * passes then move the bytes of a definite solve; a general Z adds 8k bytes per row to each).  Otherwise Z is column-major n x k
+ * (memspace as for dpcg_create) in the CALLER's numbering, any linearly independent columns: the library orthonormalises them on
+ * the host (fp64 modified Gram-Schmidt, twice) and permutes them to the handle's numbering when the handle is reordered
+ * (dpcg_reorder on a handle that has a null space is DPCG_ERR_STATE: reorder first).  check_tol > 0: every column must satisfy
+ * max_i |(A z_j)_i| <= check_tol ||A||_inf ||z_j||_inf; check_tol <= 0: no check.  DPCG_ERR_INVALID (text in dpcg_last_error) for
+ * k < 0 or k > 4, Z == NULL with k > 1, a non-finite entry, a rank-deficient Z (a column's norm after orthogonalisation below
+ * 1e-12 of its norm before) and a failed check; the handle then keeps what it had.  dpcg_update_values keeps the null space and
+ * repeats the check when one was asked for (its failure is that call's DPCG_ERR_INVALID; the null space is then dropped).
+ * dpcg_get_nullspace: *k (0: none) and, Z_host != NULL, the orthonormal basis column-major n x k in the caller's numbering.
+ *
+ * A handle with a null space takes this driver whatever its size (no one-launch form).  Refused with DPCG_ERR_INVALID and a reason:
+ * DPCG_SINGLE_REDUCTION, DPCG_SPMV_F32, DPCG_TEAM; x_true; dpcg_solve_batch with such a handle; DPCG_PRECOND_AMG (its exact coarse
+ * solve inverts a singular matrix); DPCG_PRECOND_CALLBACK (the driver enqueues updates ahead of the test and a callback cannot be
+ * skipped once it has passed).  A handle without a null space takes exactly the paths it took. */
+int dpcg_set_nullspace(dpcg_handle_t h, int k, const double *Z, int memspace, double check_tol, dpcg_stream_t stream);
+int dpcg_get_nullspace(dpcg_handle_t h, int *k, double *Z_host);
+
 /* `count` independent systems (train.py:90-108 / test.py:121-149 loop over samples): handles[i],
  * b[i], x0[i], x[i] as above; outputs are arrays of length count.  Systems are interleaved on
  * `n_streams` internal streams (1..8).  Returns the worst status. */
