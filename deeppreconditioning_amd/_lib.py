@@ -90,6 +90,8 @@ SIGNATURES = {
     "dpcg_spectrum": (_int, [_p, _int, _dbl, C.c_uint64, _p, C.POINTER(_int), C.POINTER(_dbl), C.POINTER(_dbl),
                              C.POINTER(_dbl), C.POINTER(_dbl), _p, _p]),
     "dpcg_tridiag_ritz": (_int, [_int, _p, _p, _p, _p]),
+    "dpcg_tridiag_eigvecs": (_int, [_int, _p, _p, _int, _p, _p]),
+    "dpcg_spectrum_vectors": (_int, [_p, _int, _int, _dbl, C.c_uint64, _p, C.POINTER(_int), _p, _p, _p]),
     "dpcg_guess_create": (_int, [_p, _int, _dbl, C.POINTER(_p)]),
     "dpcg_guess_project": (_int, [_p, _p, _p, _p]),
     "dpcg_guess_update": (_int, [_p, _p, _p]),
@@ -99,6 +101,8 @@ SIGNATURES = {
     "dpcg_guess_destroy": (_int, [_p]),
     "dpcg_set_nullspace": (_int, [_p, _int, _p, _int, _dbl, _p]),
     "dpcg_get_nullspace": (_int, [_p, C.POINTER(_int), _p]),
+    "dpcg_set_deflation": (_int, [_p, _int, _p, _int, _p]),
+    "dpcg_get_deflation": (_int, [_p, C.POINTER(_int), _p, _p]),
     "dpcg_solve": (_int, [_p, _p, _p, _p, _dbl, _dbl, _int, _int, _p, C.POINTER(_int), C.POINTER(_dbl),
                           C.POINTER(_dbl), _p, _p, _p]),
     "dpcg_solve_batch": (_int, [_int, _p, _p, _p, _p, _dbl, _dbl, _int, _int, _int, _p, _p, _p, _p]),

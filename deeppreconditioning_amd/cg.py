@@ -43,7 +43,7 @@ def _system_and_device(A, b):
 
 def preconditioned_conjugate_gradient(A, b, M, x0=None, x_true=None, rtol=1e-8, max_iter=1024, *,
                                       mixed_precision=False, compact_values=False, details=False, recurrence="standard",
-                                      nullspace=None):
+                                      nullspace=None, deflation=None):
     """PCG, cg.py:50-90.  Returns `(duration_seconds, iterations, info)`.
 
     `rtol` is compared with <r,r>/<b,b> (squared ratio, cg.py:71); the first test uses z0
@@ -56,7 +56,8 @@ def preconditioned_conjugate_gradient(A, b, M, x0=None, x_true=None, rtol=1e-8, 
     Chronopoulos and Gear's single-synchronisation form of the loop (`CsrSystem.solve`: M = None or Jacobi on chip-sized systems,
     other bits than the reference's recurrence, which stays the default); `nullspace="constant"` or an (n, k) basis, k <= 4,
     attaches the null space of a singular (all-Neumann) system -- `CsrSystem.set_nullspace` -- which the loop then projects out
-    (the minimum-norm solution; no reference counterpart).  The default None changes nothing.
+    (the minimum-norm solution; no reference counterpart).  The default None changes nothing.  `deflation`: an (n, k) array,
+    k <= 8, or "ritz" -- `CsrSystem.set_deflation`, attached after M: deflated PCG (no reference counterpart; None changes nothing).
 
     The plain return value follows the reference to the letter: `info` is always 0 (cg.py:90), and a NaN
     breakdown (b = 0, NaN input, singular M), on which the reference keeps looping because `nan < rtol` is
@@ -67,6 +68,8 @@ def preconditioned_conjugate_gradient(A, b, M, x0=None, x_true=None, rtol=1e-8, 
     system.set_preconditioner(M)
     if nullspace is not None:
         system.set_nullspace(nullspace)
+    if deflation is not None:
+        system.set_deflation(deflation)
     flags =(L.SPMV_F32 if mixed_precision else 0) | (L.VAL32_IF_LOSSLESS if compact_values else 0)
     result = system.solve(b, x0, rtol_sq=float(rtol), max_iter=int(max_iter), flags=flags, recurrence=recurrence)
     if details:
@@ -75,15 +78,18 @@ def preconditioned_conjugate_gradient(A, b, M, x0=None, x_true=None, rtol=1e-8, 
     return result.seconds, iterations, 0
 
 
-def conjugate_gradient(A, b, x0=None, x_true=None, rtol=1e-8, max_iter=1024, *, recurrence="standard", nullspace=None):
+def conjugate_gradient(A, b, x0=None, x_true=None, rtol=1e-8, max_iter=1024, *, recurrence="standard", nullspace=None,
+                       deflation=None):
     """Unpreconditioned CG, cg.py:20-47.  Returns `(errors, x_hat)` with
     `errors[k] = (A-norm error of x_k or 0, <r_k,r_k>/<b,b>)` as 0-d tensors.  `recurrence="single_reduction"` (keyword-only, not
-    together with `x_true`) and `nullspace` (keyword-only, not together with `x_true` either): see
+    together with `x_true`), `nullspace` and `deflation` (keyword-only, not together with `x_true` either): see
     `preconditioned_conjugate_gradient`."""
     system = _system_and_device(A, b)
     system.set_preconditioner(None)
     if nullspace is not None:
         system.set_nullspace(nullspace)
+    if deflation is not None:
+        system.set_deflation(deflation)
     result = system.solve(b, x0, rtol_sq=float(rtol), max_iter=int(max_iter), flags=L.INIT_CHECK_R, x_true=x_true,
                           recurrence=recurrence)
     res = torch.from_numpy(result.res_history.copy()).to(system.device)

@@ -399,6 +399,7 @@ extern "C" int dpcg_destroy(dpcg_handle_t h) {
     SetupScope scope(nullptr, true);                      // (waits for the device: the arrays may be in use on any stream)
     orphan_guesses(h);
     free_nullspace(h);
+    free_deflation(h);
     free_precond(h);
     free_csr(h->A);
     free_csr(h->A_user);
@@ -434,6 +435,10 @@ extern "C" int dpcg_reorder(dpcg_handle_t h, int mode, dpcg_stream_t stream, int
     if (mode != DPCG_REORDER_AUTO && mode != DPCG_REORDER_ALWAYS && mode != DPCG_REORDER_REGIONS) return invalid("dpcg_reorder: bad mode");
     if (h->ns) {                         // (its basis is stored in the numbering the handle has)
         set_error("dpcg_reorder: the handle has a null space attached: reorder first, then dpcg_set_nullspace");
+        return DPCG_ERR_STATE;
+    }
+    if (h->df) {                         // (and so are its deflation vectors)
+        set_error("dpcg_reorder: the handle has a deflation attached: reorder first, then dpcg_set_deflation");
         return DPCG_ERR_STATE;
     }
     hipStream_t s = (hipStream_t)stream;
@@ -580,6 +585,7 @@ extern "C" int dpcg_update_values(dpcg_handle_t h, const void *val, int val_dtyp
     h->values_epoch += 1;                        // (a projected guess re-orthonormalises its basis before its next use)
     DPCG_CHECK_LAUNCH();
     DPCG_TRY(nullspace_values_changed(h, s));    // an attached null space stays; its check, if one was asked for, runs on the new values
+    DPCG_TRY(deflation_values_changed(h, s));    // an attached deflation keeps its span: A W and the A-orthonormalisation are redone
     return DPCG_OK;
 }
 

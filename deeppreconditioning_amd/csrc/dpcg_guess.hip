@@ -313,13 +313,6 @@ void launch_pair(const dpcg_guess *g, int l, const double *coef, bool dot, hipSt
     hipLaunchKernelGGL((k_gs_pair<kGsRows>), dim3(grid), dim3(kBlock), 0, s, g->ld, l, g->X, g->W, coef, g->d, g->w, part);
 }
 
-void launch_rmul(const dpcg_guess *g, int l, const double *rinv, hipStream_t s) {
-    const dim3 grid((unsigned)(g->ld / (kBlock * 2)), 2);
-    if (l <= 8) hipLaunchKernelGGL((k_gs_rmul<8>), grid, dim3(kBlock), 0, s, g->ld, l, g->X, g->W, rinv);
-    else if (l <= 16) hipLaunchKernelGGL((k_gs_rmul<16>), grid, dim3(kBlock), 0, s, g->ld, l, g->X, g->W, rinv);
-    else hipLaunchKernelGGL((k_gs_rmul<32>), grid, dim3(kBlock), 0, s, g->ld, l, g->X, g->W, rinv);
-}
-
 void release_buffers(dpcg_guess *g) {
     dev_free(g->X);
     dev_free(g->W);
@@ -342,51 +335,23 @@ int reorthonormalise(dpcg_guess *g, hipStream_t s) {
     dpcg_system *h = g->h;
     int l = g->size;
     for (int j = 0; j < l; ++j) DPCG_TRY(dpcg_spmv(h, g->X + (int64_t)j * g->ld, g->W + (int64_t)j * g->ld, s));
-    std::vector<double> G, R;
+    std::vector<double> G;
     const double tol2 = g->tol_dep * g->tol_dep;
     for (int round = 0; round < 2 && l > 0; ++round) {
         // column j of the Gram matrix: G[i][j] = <x~_i, W_j>, kept at G[j * l + i]
         for (int j = 0; j < l; ++j)
-            launch_dots(g, l, g->X, g->W + (int64_t)j * g->ld, GS_PADDED, false, g->coef + kCoefGram + j * l, s);
+            gs_gram_column(g->ld, l, g->X, g->W + (int64_t)j * g->ld, g->part, g->coef + kCoefGram + j * l, s);
         DPCG_CHECK_LAUNCH();
         G.assign((size_t)l * l, 0.0);
         DPCG_HIP(hipMemcpyAsync(G.data(), g->coef + kCoefGram, (size_t)l * l * sizeof(double), hipMemcpyDeviceToHost, s));
         DPCG_HIP(hipStreamSynchronize(s));
-        // G = R^T R from the upper triangle, row by row; sums over k ascending
-        R.assign((size_t)l * l, 0.0);
-        int keep = l;
-        for (int j = 0; j < l; ++j) {
-            const double gjj = G[(size_t)j * l + j];
-            double p = gjj;
-            for (int k = 0; k < j; ++k) p = p - R[(size_t)k * l + j] * R[(size_t)k * l + j];
-            if (!std::isfinite(p) || !(p > tol2 * gjj)) {
-                keep = j;
-                break;
-            }
-            const double rjj = std::sqrt(p);
-            R[(size_t)j * l + j] = rjj;
-            for (int m = j + 1; m < l; ++m) {
-                double t = G[(size_t)m * l + j];
-                for (int k = 0; k < j; ++k) t = t - R[(size_t)k * l + j] * R[(size_t)k * l + m];
-                R[(size_t)j * l + m] = t / rjj;
-            }
-        }
-        g->dropped += l - keep;
-        // T = R^-1 of the leading keep x keep block, column by column (row-major, keep x keep)
         std::vector<double> &T = g->rinv_host;
-        T.assign((size_t)keep * keep, 0.0);
-        for (int j = 0; j < keep; ++j) {
-            T[(size_t)j * keep + j] = 1.0 / R[(size_t)j * l + j];
-            for (int i = j - 1; i >= 0; --i) {
-                double t = 0.0;
-                for (int k = i + 1; k <= j; ++k) t = t + R[(size_t)i * l + k] * T[(size_t)k * keep + j];
-                T[(size_t)i * keep + j] = -t / R[(size_t)i * l + i];
-            }
-        }
+        const int keep = gs_cholesky_rinv(G, l, tol2, T);
+        g->dropped += l - keep;
         l = keep;
         if (l == 0) break;
         DPCG_HIP(hipMemcpyAsync(g->coef + kCoefRinv, T.data(), (size_t)l * l * sizeof(double), hipMemcpyHostToDevice, s));
-        launch_rmul(g, l, g->coef + kCoefRinv, s);
+        gs_rmul_pair(g->ld, l, g->X, g->W, g->coef + kCoefRinv, s);
         DPCG_CHECK_LAUNCH();
         DPCG_HIP(hipStreamSynchronize(s));      // (T is overwritten by the next round)
     }
@@ -415,6 +380,53 @@ void orphan_guesses(dpcg_system *h) {
 }
 
 }  // namespace dpcg
+
+// ---- the pieces of CholQR2 that dpcg_deflation.hip shares (dpcg_host.h) ----------------------------------------------------------
+void gs_gram_column(int64_t ld, int l, const double *X, const double *v, double *part, double *out, hipStream_t s) {
+    const int grid = (int)(ld / (kBlock * kGsRows));
+    hipLaunchKernelGGL((k_gs_dots<kGsRows>), dim3(grid), dim3(kBlock), 0, s, ld, ld, l, X, v, (int)GS_PADDED, 0, part);
+    if (l > 0) hipLaunchKernelGGL(k_gs_fin, dim3(l), dim3(kBlock), 0, s, part, ld / (64 * kGsRows), out);
+}
+
+int gs_cholesky_rinv(const std::vector<double> &G, int l, double tol2, std::vector<double> &T) {
+    // G = R^T R from the upper triangle, row by row; sums over k ascending
+    std::vector<double> R((size_t)l * l, 0.0);
+    int keep = l;
+    for (int j = 0; j < l; ++j) {
+        const double gjj = G[(size_t)j * l + j];
+        double p = gjj;
+        for (int k = 0; k < j; ++k) p = p - R[(size_t)k * l + j] * R[(size_t)k * l + j];
+        if (!std::isfinite(p) || !(p > tol2 * gjj)) {
+            keep = j;
+            break;
+        }
+        const double rjj = std::sqrt(p);
+        R[(size_t)j * l + j] = rjj;
+        for (int m = j + 1; m < l; ++m) {
+            double t = G[(size_t)m * l + j];
+            for (int k = 0; k < j; ++k) t = t - R[(size_t)k * l + j] * R[(size_t)k * l + m];
+            R[(size_t)j * l + m] = t / rjj;
+        }
+    }
+    // T = R^-1 of the leading keep x keep block, column by column (row-major, keep x keep)
+    T.assign((size_t)keep * keep, 0.0);
+    for (int j = 0; j < keep; ++j) {
+        T[(size_t)j * keep + j] = 1.0 / R[(size_t)j * l + j];
+        for (int i = j - 1; i >= 0; --i) {
+            double t = 0.0;
+            for (int k = i + 1; k <= j; ++k) t = t + R[(size_t)i * l + k] * T[(size_t)k * keep + j];
+            T[(size_t)i * keep + j] = -t / R[(size_t)i * l + i];
+        }
+    }
+    return keep;
+}
+
+void gs_rmul_pair(int64_t ld, int l, double *X, double *W, const double *rinv, hipStream_t s) {
+    const dim3 grid((unsigned)(ld / (kBlock * 2)), 2);
+    if (l <= 8) hipLaunchKernelGGL((k_gs_rmul<8>), grid, dim3(kBlock), 0, s, ld, l, X, W, rinv);
+    else if (l <= 16) hipLaunchKernelGGL((k_gs_rmul<16>), grid, dim3(kBlock), 0, s, ld, l, X, W, rinv);
+    else hipLaunchKernelGGL((k_gs_rmul<32>), grid, dim3(kBlock), 0, s, ld, l, X, W, rinv);
+}
 
 extern "C" int dpcg_guess_create(dpcg_handle_t h, int depth, double tol_dep, dpcg_guess_t *out) {
     if (!out) return invalid("dpcg_guess_create: out is NULL");

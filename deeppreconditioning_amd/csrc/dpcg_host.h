@@ -192,6 +192,18 @@ const char *nullspace_refusal(const dpcg_system *h, int flags, const double *x_t
 int solve_nullspace_one(dpcg_system *h, SolveCall c);
 int nullspace_values_changed(dpcg_system *h, hipStream_t s);
 void free_nullspace(dpcg_system *h);
+// dpcg_deflation.hip: deflated PCG (dpcg_set_deflation), the same four -- after dpcg_update_values A W and the A-orthonormalisation are redone
+const char *deflation_refusal(const dpcg_system *h, int flags, const double *x_true);
+int solve_deflated_one(dpcg_system *h, SolveCall c);
+int deflation_values_changed(dpcg_system *h, hipStream_t s);
+void free_deflation(dpcg_system *h);
+// dpcg_guess.hip, shared with dpcg_deflation.hip: the device and host pieces of CholQR2 on a tall-skinny pair X, W = A X (column-major, ld a
+// multiple of 1024 rows apart, padding rows zero).  gs_gram_column: out[i] = <X[:, i], v>, i < l (part: l x ld / 128 doubles of scratch);
+// gs_cholesky_rinv: G = R^T R (G[j * l + i] = G_ij), T = R^-1 of the leading keep x keep block (row-major), keep = the first j whose pivot is
+// <= tol2 G_jj (l: none); gs_rmul_pair: X <- X T, W <- W T in place (T on the device).
+void gs_gram_column(int64_t ld, int l, const double *X, const double *v, double *part, double *out, hipStream_t s);
+int gs_cholesky_rinv(const std::vector<double> &G, int l, double tol2, std::vector<double> &T);
+void gs_rmul_pair(int64_t ld, int l, double *X, double *W, const double *rinv, hipStream_t s);
 // dpcg_amg.hip: the smoothed-aggregation hierarchy -- free, launches of one V-cycle, sum over levels of nnz(A_l) + 2 nnz(P_l), the apply
 // (part_rz: the last kernel leaves the partials of <r, z>), and how many partials an in-loop apply leaves (0: none)
 void free_amg(AmgState *&S);

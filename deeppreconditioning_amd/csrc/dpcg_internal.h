@@ -216,6 +216,7 @@ void launch_sfs_block_max(const int32_t *blk, int nblk, const int32_t *lo_rowptr
 struct AmgState;   // dpcg_amg.hip: a smoothed-aggregation hierarchy
 struct FsaiCache;  // dpcg_fsai.hip: what the symbolic phase of an FSAI factor leaves on the handle
 struct NullSpace;  // dpcg_nullspace.hip: the null space attached to a singular (semi-definite) system and its solve state
+struct Deflation;  // dpcg_deflation.hip: the A-orthonormal deflation vectors W, A W and the partial buffer of a deflated solve
 
 // (dpcg_chip_trsv.hip; the comment is with ChipTrsvDesc below)
 struct ChipTrsvLists {
@@ -326,6 +327,8 @@ struct dpcg_system {
     std::vector<dpcg_guess *> guesses;
     // dpcg_set_nullspace (dpcg_nullspace.hip): null = a definite system, every solve takes the paths it always took
     dpcg::NullSpace *ns = nullptr;
+    // dpcg_set_deflation (dpcg_deflation.hip): null = no deflation, every solve takes the paths it always took
+    dpcg::Deflation *df = nullptr;
 };
 
 namespace dpcg {

@@ -232,9 +232,47 @@ __global__ __launch_bounds__(kBlock) void k_lz_store(const double *__restrict__ 
     }
 }
 
+// Ritz vectors y_i = Z s_i, i < nvec <= kLzVecMax: the tall-skinny product (n x m)(m x nvec) in one pass over the basis columns.  A lane
+// owns 2 consecutive rows and keeps their kLzVecMax accumulators in registers; S (m x kLzVecMax, row-major, the unused columns zero) is
+// staged through LDS kLzVecChunk rows at a time (every lane reads the same word: a broadcast); each sum runs over the basis columns in
+// ascending order.  out: column-major n x nvec in the CALLER's numbering (perm: handle row -> caller row, or null).  Grid: ld / 512.
+constexpr int kLzVecMax = 8, kLzVecChunk = 512;
+__global__ __launch_bounds__(kBlock) void k_lz_ritz_vectors(int64_t ld, int64_t n, int m, const double *__restrict__ Z,
+                                                            const double *__restrict__ S, int nvec, const int32_t *__restrict__ perm,
+                                                            double *__restrict__ out) {
+    __shared__ double sS[kLzVecChunk * kLzVecMax];
+    const int64_t row = ((int64_t)blockIdx.x * kBlock + threadIdx.x) * 2;
+    double a0[kLzVecMax], a1[kLzVecMax];
+#pragma unroll
+    for (int j = 0; j < kLzVecMax; ++j) a0[j] = a1[j] = 0.0;
+    for (int c0 = 0; c0 < m; c0 += kLzVecChunk) {
+        const int cn = m - c0 < kLzVecChunk ? m - c0 : kLzVecChunk;
+        __syncthreads();                                   // (the previous chunk may still be read)
+        for (int t = threadIdx.x; t < cn * kLzVecMax; t += kBlock) sS[t] = S[(int64_t)c0 * kLzVecMax + t];
+        __syncthreads();
+#pragma unroll 4
+        for (int c = 0; c < cn; ++c) {
+            const double2 zv = *reinterpret_cast<const double2 *>(Z + (int64_t)(c0 + c) * ld + row);
+#pragma unroll
+            for (int j = 0; j < kLzVecMax; ++j) {
+                const double sj = sS[c * kLzVecMax + j];
+                a0[j] = a0[j] + zv.x * sj;
+                a1[j] = a1[j] + zv.y * sj;
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < kLzVecMax; ++j) {
+        if (j < nvec) {
+            if (row < n) out[(int64_t)j * n + (perm ? perm[row] : row)] = a0[j];
+            if (row + 1 < n) out[(int64_t)j * n + (perm ? perm[row + 1] : row + 1)] = a1[j];
+        }
+    }
+}
+
 struct LzBuffers {
     double *R = nullptr, *Z = nullptr, *w = nullptr, *u = nullptr, *part = nullptr, *part_s = nullptr, *part_d = nullptr;
-    double *alpha = nullptr, *beta = nullptr, *c = nullptr;
+    double *alpha = nullptr, *beta = nullptr, *c = nullptr, *S = nullptr;
     LzState *st = nullptr;
     ~LzBuffers() {
         dev_free(R);
@@ -247,6 +285,7 @@ struct LzBuffers {
         dev_free(alpha);
         dev_free(beta);
         dev_free(c);
+        dev_free(S);
         dev_free(st);
     }
 };
@@ -314,17 +353,80 @@ extern "C" int dpcg_tridiag_ritz(int k, const double *alpha, const double *beta,
     return DPCG_OK;
 }
 
-extern "C" int dpcg_spectrum(dpcg_handle_t h, int max_steps, double rtol, uint64_t seed, dpcg_stream_t stream, int *steps,
-                             double *theta_min, double *theta_max, double *err_min, double *err_max, double *alpha,
-                             double *beta) {
-    if (!h || max_steps < 1 || !(rtol >= 0.0)) return invalid("dpcg_spectrum: bad argument (max_steps >= 1, rtol >= 0)");
+// The nvec lowest eigenpairs of the same tridiagonal as unit vectors: the QL iteration above with the rotations accumulated on the
+// whole eigenvector matrix (O(k^2) per sweep; the eigenvalues take the same path and come out with the same bits).  S: column-major
+// k x nvec, S[i * k + r] = component r of theta[i]'s eigenvector (sign arbitrary).
+extern "C" int dpcg_tridiag_eigvecs(int k, const double *alpha, const double *beta, int nvec, double *theta, double *S) {
+    if (k < 1 || !alpha || (k > 1 && !beta) || nvec < 1 || nvec > k || !theta || !S) return invalid("dpcg_tridiag_eigvecs: bad argument (1 <= nvec <= k)");
+    std::vector<double> d(alpha, alpha + k), e(k, 0.0), V((size_t)k * k, 0.0);   // V[i * k + r]: component r of column i
+    for (int i = 0; i + 1 < k; ++i) e[i] = beta[i];
+    for (int i = 0; i < k; ++i) V[(size_t)i * k + i] = 1.0;
+    const double eps = std::numeric_limits<double>::epsilon();
+    for (int l = 0; l < k; ++l) {
+        for (int iter = 0;; ++iter) {
+            int m = l;
+            for (; m + 1 < k; ++m)
+                if (std::fabs(e[m]) <= eps * (std::fabs(d[m]) + std::fabs(d[m + 1]))) break;
+            if (m == l) break;
+            if (iter == 60) return invalid("dpcg_tridiag_eigvecs: QL iteration did not converge");
+            double g = (d[l + 1] - d[l]) / (2.0 * e[l]);
+            double r = std::hypot(g, 1.0);
+            g = d[m] - d[l] + e[l] / (g + std::copysign(r, g));
+            double s = 1.0, c = 1.0, p = 0.0;
+            int i = m - 1;
+            bool underflow = false;
+            for (; i >= l; --i) {
+                const double f = s * e[i], b = c * e[i];
+                r = std::hypot(f, g);
+                e[i + 1] = r;
+                if (r == 0.0) {
+                    d[i + 1] -= p;
+                    e[m] = 0.0;
+                    underflow = true;
+                    break;
+                }
+                s = f / r;
+                c = g / r;
+                g = d[i + 1] - p;
+                r = (d[i] - g) * s + 2.0 * c * b;
+                p = s * r;
+                d[i + 1] = g + p;
+                g = c * r - b;
+                double *vi = V.data() + (size_t)i * k, *vi1 = vi + k;       // the rotation on columns i, i + 1, every row
+                for (int row = 0; row < k; ++row) {
+                    const double t = vi1[row];
+                    vi1[row] = s * vi[row] + c * t;
+                    vi[row] = c * vi[row] - s * t;
+                }
+            }
+            if (underflow) continue;
+            d[l] -= p;
+            e[l] = g;
+            e[m] = 0.0;
+        }
+    }
+    std::vector<int> order(k);
+    for (int i = 0; i < k; ++i) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return d[a] < d[b]; });
+    for (int i = 0; i < nvec; ++i) {
+        theta[i] = d[order[i]];
+        std::copy(V.begin() + (size_t)order[i] * k, V.begin() + (size_t)(order[i] + 1) * k, S + (size_t)i * k);
+    }
+    return DPCG_OK;
+}
+
+// The Lanczos run behind dpcg_spectrum (nvec = 0: stops on the two extreme Ritz pairs) and dpcg_spectrum_vectors (nvec > 0: stops on
+// the nvec lowest ones and leaves their Ritz vectors in W_dev before the basis is released).  `who` heads the error texts.
+static int lanczos_run(dpcg_system *h, const char *who, int max_steps, double rtol, uint64_t seed, hipStream_t s, int nvec, int *steps,
+                       double *theta_min, double *theta_max, double *err_min, double *err_max, double *alpha, double *beta,
+                       double *theta_low, double *err_low, double *W_dev) {
+    const std::string name(who);
     if (h->precond == DPCG_PRECOND_LU_MULTIPLY || h->precond == DPCG_PRECOND_LU_SOLVE) {
         // the process runs in the M inner product, which a non-symmetric M does not define: no step is taken
         if (steps) *steps = 0;
-        set_error("dpcg_spectrum: M = L U is not symmetric");
+        set_error(name + ": M = L U is not symmetric");
         return DPCG_BREAKDOWN;
     }
-    hipStream_t s = (hipStream_t)stream;
     const int64_t n = h->A.n;
     const int m = (int)std::min<int64_t>(max_steps, n);  // the Krylov space has at most n dimensions
     const int64_t ld = (n + kLzSpan - 1) / kLzSpan * kLzSpan;
@@ -338,8 +440,8 @@ extern "C" int dpcg_spectrum(dpcg_handle_t h, int max_steps, double rtol, uint64
         DPCG_HIP(hipMemGetInfo(&free_b, &total_b));
         if (need > (double)free_b + (double)cached_memory_bytes()) {
             char buf[256];
-            snprintf(buf, sizeof(buf), "dpcg_spectrum: the Lanczos basis needs %.2f GiB (2 x (max_steps + 1) x n x 8 bytes, "
-                     "max_steps = %d, n = %lld), %.2f GiB are free", need / 1073741824.0, m, (long long)n, free_b / 1073741824.0);
+            snprintf(buf, sizeof(buf), "%s: the Lanczos basis needs %.2f GiB (2 x (max_steps + 1) x n x 8 bytes, "
+                     "max_steps = %d, n = %lld), %.2f GiB are free", who, need / 1073741824.0, m, (long long)n, free_b / 1073741824.0);
             set_error(buf);
             return DPCG_ERR_NOMEM;
         }
@@ -351,7 +453,7 @@ extern "C" int dpcg_spectrum(dpcg_handle_t h, int max_steps, double rtol, uint64
     {
         int st = DPCG_OK;
         if ((st = dev_alloc(&B.R, basis)) < 0 || (st = dev_alloc(&B.Z, basis)) < 0) {
-            set_error("dpcg_spectrum: the Lanczos basis (2 x (max_steps + 1) x n doubles) does not fit in device memory");
+            set_error(name + ": the Lanczos basis (2 x (max_steps + 1) x n doubles) does not fit in device memory");
             return st;
         }
     }
@@ -412,14 +514,14 @@ extern "C" int dpcg_spectrum(dpcg_handle_t h, int max_steps, double rtol, uint64
         DPCG_HIP(hipStreamSynchronize(s));
         if (sh.status == LZ_NOT_SPD || sh.status == LZ_NONFINITE) {
             char buf[256];
-            snprintf(buf, sizeof(buf), "dpcg_spectrum: %s after %d steps: M is not symmetric positive definite, or A / M hold "
-                     "non-finite values", sh.status == LZ_NOT_SPD ? "<w, M w> <= 0" : "a non-finite <w, M w>", sh.stop);
+            snprintf(buf, sizeof(buf), "%s: %s after %d steps: M is not symmetric positive definite, or A / M hold "
+                     "non-finite values", who, sh.status == LZ_NOT_SPD ? "<w, M w> <= 0" : "a non-finite <w, M w>", sh.stop);
             set_error(buf);
             return DPCG_BREAKDOWN;
         }
         k = sh.status == LZ_INVARIANT ? sh.stop : done;
         if (k < 1) {
-            set_error("dpcg_spectrum: the start vector lies in an invariant space of dimension 0");
+            set_error(name + ": the start vector lies in an invariant space of dimension 0");
             return DPCG_BREAKDOWN;
         }
         DPCG_TRY(dpcg_tridiag_ritz(k, ah.data(), bh.data() + 1, theta.data(), bottom.data()));
@@ -428,10 +530,34 @@ extern "C" int dpcg_spectrum(dpcg_handle_t h, int max_steps, double rtol, uint64
         tmax = theta[k - 1];
         emin = bnext * std::fabs(bottom[0]);
         emax = bnext * std::fabs(bottom[k - 1]);
-        converged = sh.status == LZ_INVARIANT || k == n || (emin <= rtol * std::fabs(tmin) && emax <= rtol * std::fabs(tmax));
+        bool small = emin <= rtol * std::fabs(tmin) && emax <= rtol * std::fabs(tmax);
+        if (nvec > 0) {                                  // the nvec lowest pairs instead of the two extreme ones
+            small = k >= nvec;
+            for (int i = 0; small && i < nvec; ++i) small = bnext * std::fabs(bottom[i]) <= rtol * std::fabs(theta[i]);
+        }
+        converged = sh.status == LZ_INVARIANT || k == n || small;
         if (converged || sh.status) break;
     }
     if (steps) *steps = k;
+    if (nvec > 0) {
+        if (k < nvec) {
+            char buf[200];
+            snprintf(buf, sizeof(buf), "%s: the Krylov space of the start vector has %d dimensions, fewer than the %d vectors asked for", who, k, nvec);
+            set_error(buf);
+            return DPCG_ERR_INVALID;
+        }
+        std::vector<double> S((size_t)k * nvec), Sp((size_t)k * kLzVecMax, 0.0);
+        DPCG_TRY(dpcg_tridiag_eigvecs(k, ah.data(), bh.data() + 1, nvec, theta_low, S.data()));
+        for (int i = 0; i < nvec; ++i) {
+            err_low[i] = bh[k] * std::fabs(S[(size_t)i * k + k - 1]);
+            for (int r = 0; r < k; ++r) Sp[(size_t)r * kLzVecMax + i] = S[(size_t)i * k + r];
+        }
+        DPCG_TRY(dev_alloc(&B.S, (int64_t)k * kLzVecMax));
+        DPCG_HIP(hipMemcpyAsync(B.S, Sp.data(), Sp.size() * sizeof(double), hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_lz_ritz_vectors, dim3((unsigned)(ld / (kBlock * 2))), dim3(kBlock), 0, s, ld, n, k, B.Z, B.S, nvec, h->perm, W_dev);
+        DPCG_CHECK_LAUNCH();
+        DPCG_HIP(hipStreamSynchronize(s));               // (Sp and the basis go out of scope)
+    }
     if (theta_min) *theta_min = tmin;
     if (theta_max) *theta_max = tmax;
     if (err_min) *err_min = emin;
@@ -439,4 +565,21 @@ extern "C" int dpcg_spectrum(dpcg_handle_t h, int max_steps, double rtol, uint64
     if (alpha) std::copy(ah.begin(), ah.begin() + k, alpha);
     if (beta) std::copy(bh.begin() + 1, bh.begin() + 1 + k, beta);
     return converged ? DPCG_OK : DPCG_MAX_ITER;
+}
+
+extern "C" int dpcg_spectrum(dpcg_handle_t h, int max_steps, double rtol, uint64_t seed, dpcg_stream_t stream, int *steps,
+                             double *theta_min, double *theta_max, double *err_min, double *err_max, double *alpha,
+                             double *beta) {
+    if (!h || max_steps < 1 || !(rtol >= 0.0)) return invalid("dpcg_spectrum: bad argument (max_steps >= 1, rtol >= 0)");
+    return lanczos_run(h, "dpcg_spectrum", max_steps, rtol, seed, (hipStream_t)stream, 0, steps, theta_min, theta_max, err_min, err_max, alpha,
+                       beta, nullptr, nullptr, nullptr);
+}
+
+extern "C" int dpcg_spectrum_vectors(dpcg_handle_t h, int k, int max_steps, double rtol, uint64_t seed, dpcg_stream_t stream, int *steps,
+                                     double *theta, double *err, double *W_dev) {
+    if (!h || max_steps < 1 || !(rtol >= 0.0) || !theta || !err || !W_dev)
+        return invalid("dpcg_spectrum_vectors: bad argument (max_steps >= 1, rtol >= 0, theta, err and W_dev not NULL)");
+    if (k < 1 || k > kLzVecMax || k > h->A.n) return invalid("dpcg_spectrum_vectors: k must lie in 1 .. 8 and not exceed n");
+    return lanczos_run(h, "dpcg_spectrum_vectors", max_steps, rtol, seed, (hipStream_t)stream, k, steps, nullptr, nullptr, nullptr, nullptr,
+                       nullptr, nullptr, theta, err, W_dev);
 }

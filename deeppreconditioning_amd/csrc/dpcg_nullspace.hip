@@ -25,6 +25,7 @@
 
 #include "dpcg_device.h"
 #include "dpcg_host.h"
+#include "dpcg_slots.h"
 
 namespace dpcg {
 
@@ -45,39 +46,6 @@ struct NullSpace {
 };
 
 namespace {
-
-template <int N>
-__device__ __forceinline__ void block_sum_n(double (&v)[N], double *sh) {   // sh: 4 N doubles
-#pragma unroll
-    for (int j = 0; j < N; ++j) v[j] = wave_sum(v[j]);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 63) {
-#pragma unroll
-        for (int j = 0; j < N; ++j) sh[4 * j + (threadIdx.x >> 6)] = v[j];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < N; ++j) v[j] = ((sh[4 * j] + sh[4 * j + 1]) + sh[4 * j + 2]) + sh[4 * j + 3];
-}
-
-// slots first .. first + N - 1 of the partial buffer, G partials each, summed as reduce_partials sums them
-template <int N>
-__device__ __forceinline__ void reduce_slots(const double *__restrict__ part, int first, int G, double (&v)[N], double *sh) {
-#pragma unroll
-    for (int j = 0; j < N; ++j) {
-        const double *__restrict__ pj = part + (int64_t)(first + j) * kMaxGrid;
-        double s = 0.0;
-        for (int i = threadIdx.x; i < G; i += kBlock) s += pj[i];
-        v[j] = s;
-    }
-    block_sum_n<N>(v, sh);
-}
-
-template <int N>
-__device__ __forceinline__ void store_slots(double *__restrict__ part, int first, const double (&v)[N]) {
-#pragma unroll
-    for (int j = 0; j < N; ++j) part[(int64_t)(first + j) * kMaxGrid + blockIdx.x] = v[j];
-}
 
 // rows 2 i, 2 i + 1 of the K columns
 template <int K, bool CONST>
@@ -626,6 +594,7 @@ int nullspace_values_changed(dpcg_system *h, hipStream_t s) {
 extern "C" int dpcg_set_nullspace(dpcg_handle_t h, int k, const double *Z, int memspace, double check_tol, dpcg_stream_t stream) {
     if (!h) return invalid("dpcg_set_nullspace: NULL handle");
     if (k < 0 || k > kNsMaxK) return invalid("dpcg_set_nullspace: k must lie in 0 .. 4 (0 clears)");
+    if (k > 0 && h->df) return invalid("dpcg_set_nullspace: the handle has a deflation attached (dpcg_set_deflation): one or the other");
     hipStream_t s = (hipStream_t)stream;
     SetupScope scope(s, true);            // (the old basis may be in use on another stream)
     if (k == 0) {

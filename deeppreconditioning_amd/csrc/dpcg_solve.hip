@@ -733,6 +733,12 @@ extern "C" int dpcg_solve(dpcg_handle_t h, const double *b, const double *x0, do
         h->chip_shared_known = false;
         return solve_nullspace_one(h, {b, x0, x, rtol_sq, atol_sq, max_iter, flags, (hipStream_t)stream, iters, final_res, seconds, res_history});
     }
+    if (h->df) {                             // deflation vectors attached: the deflated driver, whatever the size (dpcg_deflation.hip)
+        if (const char *why = deflation_refusal(h, flags, x_true)) return invalid(why);
+        h->last_recurrence = 0;
+        h->chip_shared_known = false;
+        return solve_deflated_one(h, {b, x0, x, rtol_sq, atol_sq, max_iter, flags, (hipStream_t)stream, iters, final_res, seconds, res_history});
+    }
     const bool one_launch_open = co_residency().open();      // (false during the cool-down after repeated co-residency timeouts)
     if (flags & DPCG_SINGLE_REDUCTION) {
         if (const char *why = chip_sr_refusal(h, flags, x_true)) return invalid(why);     // (nothing of the handle has been touched)
@@ -802,6 +808,8 @@ extern "C" int dpcg_solve_batch(int count, dpcg_handle_t *handles, const double 
     for (int i = 0; i < count; ++i) DPCG_TRY(check_solve_args(handles[i], b[i], max_iter, flags, nullptr, nullptr));
     for (int i = 0; i < count; ++i)
         if (handles[i]->ns) return invalid("dpcg_solve_batch: a handle with a null space is solved by dpcg_solve, one at a time");
+    for (int i = 0; i < count; ++i)
+        if (handles[i]->df) return invalid("dpcg_solve_batch: a handle with a deflation is solved by dpcg_solve, one at a time");
     if (flags & DPCG_SINGLE_REDUCTION) {
         for (int i = 0; i < count; ++i)
             if (const char *why = chip_sr_refusal(handles[i], flags, nullptr)) return invalid(why);     // (nothing of any handle has been touched)

@@ -723,6 +723,60 @@ class CsrSystem:
         L.check(L.lib().dpcg_get_nullspace(self._h, C.byref(k), out.ctypes.data_as(C.c_void_p)))
         return out
 
+    def set_deflation(self, W, *, k: int = 8, max_steps: int = 200, rtol: float = 1e-3, seed: int = 0) -> None:
+        """Attach deflation vectors, so that `solve` runs deflated PCG (dpcg_set_deflation, include/dpcg.h): the search directions
+        are kept A-orthogonal to span(W), which takes the eigenvalues of M A that W captures out of the update count.
+
+        `W`: an array or tensor of shape (n,) or (n, k), k <= 8, with any linearly independent columns in the caller's numbering (the
+        library A-orthonormalises them; a dependent column is refused) -- `poisson.subdomain_indicators` gives Nicolaides'
+        piecewise-constant choice without an eigen-solve; None clears; "ritz" harvests the `k` lowest Ritz vectors of M A from the
+        Lanczos process of `spectrum_bounds` (dpcg_spectrum_vectors: at most `max_steps` steps, until their bounds are below
+        `rtol` times the Ritz value; start vector from `seed`), evaluated against the preconditioner set at this moment.  A later
+        `set_preconditioner` keeps the vectors although they were harvested for the old M: they stay valid deflation vectors, only
+        no longer the low eigenvectors of the new M A.  `update_values` keeps the span and re-orthonormalises it for the new matrix.
+        Raises DpcgError (ERR_INVALID) for k > 8, a dependent column, non-finite entries and a handle that has a null space."""
+        self._deflation_ritz = None
+        with torch.cuda.device(self.device):
+            if W is None:
+                L.check(L.lib().dpcg_set_deflation(self._h, 0, None, L.HOST, _stream()))
+                return
+            if isinstance(W, str):
+                if W != "ritz":
+                    raise ValueError("the only named deflation is 'ritz'")
+                k = int(k)
+                if not 1 <= k <= min(8, self.n):
+                    raise ValueError("k must lie in 1 .. 8 and not exceed n")
+                Wd = torch.empty(self.n * k, dtype=torch.float64, device=self.device)      # column-major n x k
+                theta, err, steps = np.zeros(k), np.zeros(k), C.c_int(0)
+                status = L.check(L.lib().dpcg_spectrum_vectors(self._h, k, int(max_steps), float(rtol), int(seed) & (2**64 - 1), _stream(),
+                                                               C.byref(steps), _np_ptr(theta), _np_ptr(err), _dev_ptr(Wd)))
+                if status == L.BREAKDOWN:
+                    raise L.DpcgError(status, L.lib().dpcg_last_error().decode(errors="replace"))
+                L.check(L.lib().dpcg_set_deflation(self._h, k, _dev_ptr(Wd), L.DEVICE, _stream()))
+                self._deflation_ritz = {"theta": theta, "err": err, "steps": steps.value, "converged": status == L.OK}
+                return
+            a = W.detach().cpu().numpy() if isinstance(W, torch.Tensor) else np.asarray(W)
+            a = a.reshape(self.n, 1) if a.ndim == 1 and a.size == self.n else a
+            if a.ndim != 2 or a.shape[0] != self.n or a.shape[1] < 1:
+                raise ValueError(f"expected deflation vectors of shape ({self.n}, k)")
+            cols = np.asfortranarray(a, dtype=np.float64)       # column-major n x k
+            L.check(L.lib().dpcg_set_deflation(self._h, int(cols.shape[1]), cols.ctypes.data_as(C.c_void_p), L.HOST, _stream()))
+
+    def deflation(self):
+        """The attached deflation as a dict -- k, W and AW = A W as the device holds them ((n, k) numpy arrays, W^T A W = I, the
+        caller's numbering) and, after set_deflation("ritz"), theta, err, steps and converged of the harvest -- or None."""
+        k = C.c_int(0)
+        L.check(L.lib().dpcg_get_deflation(self._h, C.byref(k), None, None))
+        if k.value == 0:
+            return None
+        W = np.empty((self.n, k.value), dtype=np.float64, order="F")
+        AW = np.empty((self.n, k.value), dtype=np.float64, order="F")
+        with torch.cuda.device(self.device):
+            L.check(L.lib().dpcg_get_deflation(self._h, C.byref(k), _np_ptr(W), _np_ptr(AW)))
+        out = {"k": k.value, "W": W, "AW": AW}
+        out.update(getattr(self, "_deflation_ritz", None) or {})
+        return out
+
     # -- constructors ----------------------------------------------------------------------
     @classmethod
     def from_host(cls, rowptr: np.ndarray, col: np.ndarray, val: np.ndarray, n: int, device=None, reorder="auto") -> "CsrSystem":
@@ -1066,6 +1120,22 @@ def tridiag_ritz(alpha, beta):
     bottom = np.empty(k)
     L.check(L.lib().dpcg_tridiag_ritz(k, _np_ptr(a), _np_ptr(b) if k > 1 else None, _np_ptr(theta), _np_ptr(bottom)))
     return theta, bottom
+
+
+def tridiag_eigvecs(alpha, beta, k):
+    """(theta, S): the k lowest eigenvalues of tridiag(beta, alpha, beta), ascending, and their unit eigenvectors as the columns of
+    S, shape (len(alpha), k), signs arbitrary (host only, dpcg_tridiag_eigvecs: implicit QL with accumulated rotations)."""
+    a = np.ascontiguousarray(alpha, dtype=np.float64)
+    b = np.ascontiguousarray(beta, dtype=np.float64)
+    m = a.size
+    if b.size < m - 1:
+        raise ValueError("beta needs len(alpha) - 1 entries")
+    if not 1 <= int(k) <= m:
+        raise ValueError("k must lie in 1 .. len(alpha)")
+    theta = np.empty(int(k))
+    S = np.empty((m, int(k)), order="F")
+    L.check(L.lib().dpcg_tridiag_eigvecs(m, _np_ptr(a), _np_ptr(b) if m > 1 else None, int(k), _np_ptr(theta), _np_ptr(S)))
+    return theta, S
 
 
 def dot(a: torch.Tensor, b: torch.Tensor) -> float:

@@ -81,6 +81,30 @@ def neumann_csr(dims, coefficient_seed=None):
     return A
 
 
+def subdomain_indicators(shape, blocks):
+    """The piecewise-constant deflation vectors of a box partition (Nicolaides' subdomain deflation; `CsrSystem.set_deflation`): the
+    grid `shape` (first index fastest, as `neumann_csr` and `poisson_csr` number it) is cut into blocks[0] x blocks[1] [x ...] boxes,
+    axis a into blocks[a] runs of near-equal length, and column j of the (prod(shape), prod(blocks)) result is 1 on box j and 0
+    elsewhere -- every row sums to 1.  ValueError when a box would be empty (more blocks than grid points along an axis)."""
+    shape = tuple(int(d) for d in shape)
+    blocks = tuple(int(d) for d in blocks)
+    if len(shape) != len(blocks) or not shape or min(shape) < 1 or min(blocks) < 1:
+        raise ValueError("shape and blocks need the same number of positive entries")
+    if any(nb > d for d, nb in zip(shape, blocks)):
+        raise ValueError("a block would be empty: more blocks than grid points along an axis")
+    rows = int(np.prod(shape))
+    idx = np.arange(rows, dtype=np.int64)
+    box = np.zeros(rows, dtype=np.int64)
+    off, boff = 1, 1
+    for d, nb in zip(shape, blocks):
+        box += ((idx // off) % d) * nb // d * boff         # point c of the axis lies in run floor(c nb / d)
+        off *= d
+        boff *= nb
+    W = np.zeros((rows, int(np.prod(blocks))), order="F")
+    W[idx, box] = 1.0
+    return W
+
+
 def unstructured_like_csr(dim: int, n: int, seed: int = 0):
     """Host-side stand-in for an OpenFOAM pressure matrix: D (P A P^T) D of the
     Poisson matrix with a seeded random symmetric permutation P and D = diag(U(0.5, 2)).  Returns a scipy CSR

@@ -434,6 +434,19 @@ int dpcg_spectrum(dpcg_handle_t h, int max_steps, double rtol, uint64_t seed, dp
  * beta[0..k-1) (beta may be NULL when k = 1), and bottom[i] = the last component of theta[i]'s unit eigenvector (sign
  * arbitrary).  Implicit QL with Wilkinson shifts. */
 int dpcg_tridiag_ritz(int k, const double *alpha, const double *beta, double *theta, double *bottom);
+/* Host only: the nvec lowest eigenpairs of the same tridiagonal (1 <= nvec <= k), theta[0..nvec) ascending and S column-major k x nvec,
+ * S[i * k + r] = component r of theta[i]'s unit eigenvector (sign arbitrary).  The same QL iteration with the rotations accumulated on
+ * the whole eigenvector matrix: O(k^2) per sweep, the eigenvalues bit-equal to dpcg_tridiag_ritz's. */
+int dpcg_tridiag_eigvecs(int k, const double *alpha, const double *beta, int nvec, double *theta, double *S);
+/* The k lowest Ritz vectors of M A (1 <= k <= 8), harvested from the same Lanczos process as dpcg_spectrum -- the same start vector,
+ * the same step kernels, the basis Z = M R resident in HBM -- for use as deflation vectors (dpcg_set_deflation, below).  Stops when the
+ * k lowest Ritz pairs have err_i <= rtol theta_i, when beta reaches 0 or after n steps (DPCG_OK), or after max_steps (DPCG_MAX_ITER: the
+ * vectors are returned all the same).  theta[k], err[k] (host): the Ritz values, ascending, and their bounds beta_{m+1} |s_m|.  W_dev:
+ * device fp64, column-major n x k in the CALLER's numbering: y_i = Z s_i, s_i the unit eigenvector of T_m (dpcg_tridiag_eigvecs), one
+ * pass over the basis columns, every sum in column order.  The y_i are M-orthonormal approximations of eigenvectors of M A, not yet
+ * A-orthonormal.  DPCG_ERR_INVALID when the Krylov space of the start vector has fewer than k dimensions; otherwise as dpcg_spectrum. */
+int dpcg_spectrum_vectors(dpcg_handle_t h, int k, int max_steps, double rtol, uint64_t seed, dpcg_stream_t stream, int *steps,
+                          double *theta, double *err, double *W_dev);
 
 /* ---- projected initial guess for a SEQUENCE of systems on one handle ------------------------------------------------
  * The reference starts every solve from zeros (cg.py:58).  In a time-stepping run ("same mesh, next time step") consecutive
@@ -521,6 +534,40 @@ int dpcg_solve(dpcg_handle_t h, const double *b, const double *x0, double *x, do
  * skipped once it has passed).  A handle without a null space takes exactly the paths it took. */
 int dpcg_set_nullspace(dpcg_handle_t h, int k, const double *Z, int memspace, double check_tol, dpcg_stream_t stream);
 int dpcg_get_nullspace(dpcg_handle_t h, int *k, double *Z_host);
+
+/* ---- deflated PCG: a few vectors attached to the handle and projected out of the search directions --------------------
+ * A handful of smallest eigenvalues of M A sets the update count on Poisson-type systems, and no preconditioner here removes them.
+ * Deflation does (Saad, Yeung, Erhel, Guyomarc'h, SISC 21, 2000; with piecewise-constant vectors: Nicolaides' subdomain deflation).
+ * Not in the reference.  With W (n x k, 1 <= k <= 8, W^T A W = I -- the library makes it so) and AW = A W attached, dpcg_solve runs
+ *     start:   r = b - A x0 (x0 NULL: r = b);  c = W^T r;  x = x0 + W c;  r = r - AW c        (no second SpMV)
+ *              bb = <b,b> of the caller's b;  z = M r;  mu = AW^T z;  p = z - W mu;  rho = <r,z>
+ *              first test: <z,z>/bb, or <r,r>/bb with DPCG_INIT_CHECK_R, on the r AFTER the start correction
+ *     update:  q = A p;  alpha = rho / <p,q>;  x += alpha p;  r -= alpha q;  z = M r
+ *              mu = AW^T z  (k sums);  rho' = <r,z>;  p = (z - W mu) + (rho'/rho) p
+ * The history, the stopping test, the cap, the NaN breakdown and the status words mean what they mean for dpcg_solve above.
+ * An update is the SpMV with its partials of <p,q>, one pass over q, r (dinv), AW that leaves per-workgroup partials of <r,r>, <r,z> and
+ * AW^T z (2 + k sums, each summed in one fixed order: no float atomics), and one pass over r (dinv), p, x, W -- for M = I and Jacobi the
+ * launches and reduction rounds of a plain solve, 8 k more bytes per row in each of the two passes.  Any other M: the r update, the
+ * handle's apply, one dot kernel.
+ *
+ * dpcg_set_deflation: k = 0 clears.  W is column-major n x k (memspace as for dpcg_create) in the CALLER's numbering, any columns that
+ * are linearly independent: the library checks that every entry is finite, permutes W to the handle's numbering, forms AW by k calls of
+ * the handle's SpMV and A-orthonormalises by CholQR2 as the projected guess does after new values (G = W^T AW on the device with
+ * fixed-order sums, Cholesky on the host, W <- W R^-1 and AW <- AW R^-1 in place, twice).  Unlike the guess, a dependent column -- a
+ * pivot <= tol^2 G_jj, tol = 1e-7 -- is refused, not dropped: DPCG_ERR_INVALID, the text names the column.  k < 0, k > 8 and a
+ * non-finite entry are DPCG_ERR_INVALID too; after any refusal the handle keeps what it had.  Columns are stored ld rows apart (ld = n
+ * rounded up to a multiple of 1024: every column 16-byte aligned), the padding zero.  dpcg_update_values keeps the span: it recomputes AW
+ * and the A-orthonormalisation before it returns (a failure is that call's DPCG_ERR_INVALID; the deflation is then dropped).
+ * dpcg_reorder on a handle that carries a deflation is DPCG_ERR_STATE: reorder first.  dpcg_set_preconditioner keeps the vectors.
+ * dpcg_get_deflation: *k (0: none) and, where not NULL, the A-orthonormal W and AW as the device holds them, column-major n x k in the
+ * caller's numbering (host); waits for the device.
+ *
+ * A handle with a deflation takes this driver whatever its size (no one-launch form deflates).  Refused with DPCG_ERR_INVALID and a
+ * reason: DPCG_SINGLE_REDUCTION, DPCG_SPMV_F32, DPCG_TEAM; x_true; dpcg_solve_batch with such a handle; DPCG_PRECOND_CALLBACK; a handle
+ * that also has a null space (refused at whichever attach comes second).  DPCG_PRECOND_AMG is accepted.  A handle without a deflation
+ * takes exactly the paths it took. */
+int dpcg_set_deflation(dpcg_handle_t h, int k, const double *W, int memspace, dpcg_stream_t stream);
+int dpcg_get_deflation(dpcg_handle_t h, int *k, double *W_host, double *AW_host);
 
 /* `count` independent systems (train.py:90-108 / test.py:121-149 loop over samples): handles[i],
  * b[i], x0[i], x[i] as above; outputs are arrays of length count.  Systems are interleaved on
