@@ -6,6 +6,7 @@
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include <functional>
 #include <map>
 #include <mutex>
 #include <string>
@@ -186,6 +187,27 @@ int solve_chip_one(dpcg_system *h, SolveCall c);          // M = I / Jacobi
 int solve_chip_sr_one(dpcg_system *h, SolveCall c);       // ... with the single-reduction recurrence
 int solve_chip_llt_one(dpcg_system *h, SolveCall c);      // M = L L^T multiplied
 int solve_chip_trsv_one(dpcg_system *h, SolveCall c);     // M = (L L^T)^-1 by two triangular solves
+// ---- the pieces of a launch-path solve (dpcg_solve.hip), shared by the plain driver and the two projected ones --------------------------
+// how the vector kernels see M: 0 = I, 1 = Jacobi (z = dinv r on the fly), 2 = anything else (an apply between K2 and K3)
+inline int precond_class(const dpcg_system *h) { return h->precond == DPCG_PRECOND_NONE ? 0 : (h->precond == DPCG_PRECOND_JACOBI ? 1 : 2); }
+// the handle's permutation on the host (empty: the handle is not reordered)
+int read_perm(const dpcg_system *h, std::vector<int32_t> &perm, hipStream_t s);
+// Staging of a call: the work vectors, the progress word zeroed, b gathered into the handle's numbering, x = x0 or 0, and
+// r = b - A x or r = b.  rhs (may be empty) is called with the gathered b and returns the right-hand side to use in its place.
+// *b_used: that right-hand side.
+int stage_call(dpcg_system *h, const double *b, const double *x0, int max_iter, bool need_f32, bool need_err, hipStream_t s,
+               const double **b_used, const std::function<const double *(const double *)> &rhs = nullptr);
+// Waits until the progress word leaves v -- a bounded spin, then a look at the stream so that a fault cannot hang the host.  Returns
+// DPCG_OK (moved, or still running: the caller looks again) or the error; behind: updates are enqueued beyond the one v reports, so a
+// drained stream must have moved the word.  tag: "", " (null space)", " (deflation)".
+int wait_progress(volatile unsigned long long *prog, unsigned long long v, hipStream_t s, bool behind, const char *tag);
+// Plain launches kept enqueued ahead of the progress word until the solve reports its end or max_iter: 16 updates before the time
+// per update is known (from the fourth on), then enough to cover ~150 us of host latency, 3 .. 32.
+int run_launch_ahead(dpcg_system *h, int max_iter, hipStream_t s, std::chrono::steady_clock::time_point t0, const char *tag,
+                     const std::function<int()> &enqueue_update);
+// The delivery tail, after the finaliser has been enqueued: the scalars, the end of the timer (c.seconds counts from t0), errors of the
+// sync-free triangular solves, iters / final_res / res_history, x in the caller's numbering.  Returns the solve's status.
+int deliver_solve(dpcg_system *h, const SolveCall &c, std::chrono::steady_clock::time_point t0);
 // dpcg_nullspace.hip: singular systems with an attached null space (dpcg_set_nullspace).  Why a solve with these arguments is refused
 // (nullptr: it is not); the solve itself, whatever the system's size; the check of A Z = 0 again after dpcg_update_values; the release
 const char *nullspace_refusal(const dpcg_system *h, int flags, const double *x_true);

@@ -47,7 +47,7 @@ static int enqueue_iteration(dpcg_system *h, int flags, const double *x_true, hi
         // KA: test of the current iterate, p = z + beta p, deferred x += alpha p, q = A p, partials of <p,q>
         launch_spmv_fused(h->A, h->planA, fuse_args(h), h->q, h->part_pq, h->scal, s);          // cg.py:71,83,79,75
         // KB: alpha; r -= alpha q; (z = M r fused); partials <r,z>, <r,r>; k += 1                cg.py:78,80-82,86
-        const int pre = h->precond == DPCG_PRECOND_NONE ? 0 : (h->precond == DPCG_PRECOND_JACOBI ? 1 : 2);
+        const int pre = precond_class(h);
         if (ride)
             launch_update_r_ride(n, h->scal, h->part_pq, h->planA.grid, h->q, h->r, h->lvlL.ride_diag, h->lvlL.lm_pos, h->lvlL.lm_out,
                                  h->lvlL.level_ptr[1], h->part_rr, h->vec_grid, s, true);
@@ -71,7 +71,7 @@ static int enqueue_iteration(dpcg_system *h, int flags, const double *x_true, hi
     else if (v32) launch_spmv_val32(h->A, h->planA, p_cur, h->q, h->part_pq, &ctl, s);
     else launch_spmv(h->A, h->planA, p_cur, h->q, h->part_pq, &ctl, s);
     // K2: alpha; r -= alpha Ap; (z = M r fused); partials <r,z>, <r,r>              cg.py:78,80-82,86
-    const int pre = h->precond == DPCG_PRECOND_NONE ? 0 : (h->precond == DPCG_PRECOND_JACOBI ? 1 : 2);
+    const int pre = precond_class(h);
     // Jacobi: z = dinv .* r is never stored -- K2 only needs it for <r,z>, and K3 recomputes the same product from r and
     // dinv (same rounding, same bits).  That moves 8 B per row from a write in K2 to a read in K3; writes are the dearer
     // direction (measured: 34.9 -> 33.1 us per update at 1M DoF).
@@ -183,6 +183,100 @@ int check_spin_errors(dpcg_system *h, hipStream_t s) {
     return DPCG_OK;
 }
 
+int read_perm(const dpcg_system *h, std::vector<int32_t> &perm, hipStream_t s) {
+    perm.clear();
+    if (!h->perm) return DPCG_OK;
+    perm.resize((size_t)h->A.n);
+    DPCG_HIP(hipMemcpyAsync(perm.data(), h->perm, perm.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    DPCG_HIP(hipStreamSynchronize(s));
+    return DPCG_OK;
+}
+
+int stage_call(dpcg_system *h, const double *b, const double *x0, int max_iter, bool need_f32, bool need_err, hipStream_t s,
+               const double **b_used, const std::function<const double *(const double *)> &rhs) {
+    const int64_t n = h->A.n;
+    DPCG_TRY(ensure_work(h, max_iter, need_f32, need_err));
+    *extras()[h].prog_host = 0;
+    if (h->perm) {                         // b and x0 arrive in the caller's numbering
+        if (!h->pb) DPCG_TRY(dev_alloc(&h->pb, n));
+        launch_gather_f64(n, h->perm, b, h->pb, s);
+        b = h->pb;
+    }
+    if (rhs) b = rhs(b);
+    if (x0) {
+        if (h->perm) launch_gather_f64(n, h->perm, x0, h->x, s);
+        else DPCG_HIP(hipMemcpyAsync(h->x, x0, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s));
+        launch_spmv(h->A, h->planA, h->x, h->q, nullptr, nullptr, s);
+        launch_residual(n, b, h->q, h->r, h->vec_grid, s);                           // cg.py:60
+    } else {
+        DPCG_HIP(hipMemsetAsync(h->x, 0, (size_t)n * sizeof(double), s));            // cg.py:58
+        DPCG_HIP(hipMemcpyAsync(h->r, b, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s));
+    }
+    *b_used = b;
+    return DPCG_OK;
+}
+
+int wait_progress(volatile unsigned long long *prog, unsigned long long v, hipStream_t s, bool behind, const char *tag) {
+    for (int spin = 0; spin < 4000; ++spin) {
+        if (*prog != v) return DPCG_OK;
+        __builtin_ia32_pause();
+    }
+    const hipError_t q = hipStreamQuery(s);
+    if (q == hipErrorNotReady) return DPCG_OK;
+    DPCG_HIP(q);
+    // stream drained: every enqueued update has run, the word is final for them
+    if (*prog == v && behind) {
+        set_error(std::string("PCG driver") + tag + ": enqueued updates finished without reporting progress");
+        return DPCG_ERR_STATE;
+    }
+    return DPCG_OK;
+}
+
+int run_launch_ahead(dpcg_system *h, int max_iter, hipStream_t s, std::chrono::steady_clock::time_point t0, const char *tag,
+                     const std::function<int()> &enqueue_update) {
+    volatile unsigned long long *prog = extras()[h].prog_host;
+    int enq = 0;
+    double t_iter = 0.0;
+    for (;;) {
+        const unsigned long long v = *prog;
+        const int k = (int)(v >> 1);
+        if ((v & 1ull) || k >= max_iter) return DPCG_OK;
+        if (k >= 4) t_iter = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() / k;
+        // updates kept enqueued beyond the last one reported: enough to cover ~150 us of host latency
+        int ahead = 16;
+        if (t_iter > 0.0) ahead = std::min(32, std::max(3, (int)(150e-6 / t_iter) + 2));
+        while (enq < max_iter && enq - k < ahead) {
+            DPCG_TRY(enqueue_update());
+            enq += 1;
+        }
+        DPCG_CHECK_LAUNCH();
+        DPCG_TRY(wait_progress(prog, v, s, enq > k, tag));
+    }
+}
+
+int deliver_solve(dpcg_system *h, const SolveCall &c, std::chrono::steady_clock::time_point t0) {
+    const int64_t n = h->A.n;
+    hipStream_t s = c.s;
+    DPCG_HIP(hipMemcpyAsync(h->scal_host, h->scal, sizeof(Scalars), hipMemcpyDeviceToHost, s));
+    DPCG_HIP(hipStreamSynchronize(s));
+    const auto t1 = std::chrono::steady_clock::now();                            // cg.py:88 (the loop only)
+    DPCG_TRY(check_spin_errors(h, s));
+    const Scalars sc = *h->scal_host;
+    if (c.seconds) *c.seconds = std::chrono::duration<double>(t1 - t0).count();
+    if (c.iters) *c.iters = sc.k;                                                // cg.py:90
+    if (c.final_res) *c.final_res = sc.res;
+    if (c.res_history) DPCG_HIP(hipMemcpyAsync(c.res_history, h->hist, (size_t)(sc.k + 1) * sizeof(double), hipMemcpyDeviceToHost, s));
+    // x is handed over in stream order: the copy is enqueued on the caller's stream, a second host sync is only
+    // needed for the host-side history buffer
+    if (c.x) {
+        if (h->perm) launch_scatter_f64(n, h->perm, h->x, c.x, s);       // back to the caller's numbering
+        else DPCG_HIP(hipMemcpyAsync(c.x, h->x, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s));
+    }
+    if (c.res_history) DPCG_HIP(hipStreamSynchronize(s));
+    DPCG_CHECK_LAUNCH();
+    return sc.status;
+}
+
 namespace {
 // Host side of one solve.  The GPU never waits for the host: iterations are enqueued ahead of the
 // progress word that K3 posts to pinned memory, as a replayed hipGraph of `chunk` updates (launch-bound
@@ -245,8 +339,12 @@ struct Solve {
     int start(const double *b, const double *x0, double rtol_sq, double atol_sq) {
         const int64_t n = h->A.n;
         const bool f32 = (flags & DPCG_SPMV_F32) != 0;
-        HandleExtras &ex = extras()[h];
-        DPCG_TRY(ensure_work(h, max_iter, f32, x_true != nullptr));
+        DPCG_TRY(stage_call(h, b, x0, max_iter, f32, x_true != nullptr, s, &b));
+        if (h->perm && x_true) {           // x_true arrives in the caller's numbering too
+            if (!h->pxt) DPCG_TRY(dev_alloc(&h->pxt, n));
+            launch_gather_f64(n, h->perm, x_true, h->pxt, s);
+            x_true = h->pxt;
+        }
         if ((flags & DPCG_VAL32_IF_LOSSLESS) && h->A.val32_lossless == 0) {   // decide once per matrix
             int *d_lossy = nullptr, lossy = 0;
             DPCG_TRY(dev_alloc(&d_lossy, 1));
@@ -280,32 +378,12 @@ struct Solve {
             DPCG_TRY(ensure_graph(h, flags, chunk));
             if (!h->graph_exec) use_graph = false;       // a voided capture (see ensure_graph)
         }
-        *ex.prog_host = 0;
-        if (h->perm) {                     // b, x0, x_true arrive in the caller's numbering
-            if (!h->pb) DPCG_TRY(dev_alloc(&h->pb, n));
-            launch_gather_f64(n, h->perm, b, h->pb, s);
-            b = h->pb;
-            if (x_true) {
-                if (!h->pxt) DPCG_TRY(dev_alloc(&h->pxt, n));
-                launch_gather_f64(n, h->perm, x_true, h->pxt, s);
-                x_true = h->pxt;
-            }
-        }
-        if (x0) {
-            if (h->perm) launch_gather_f64(n, h->perm, x0, h->x, s);
-            else DPCG_HIP(hipMemcpyAsync(h->x, x0, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s));
-            launch_spmv(h->A, h->planA, h->x, h->q, nullptr, nullptr, s);
-            launch_residual(n, b, h->q, h->r, h->vec_grid, s);                       // cg.py:60
-        } else {
-            DPCG_HIP(hipMemsetAsync(h->x, 0, (size_t)n * sizeof(double), s));        // cg.py:58
-            DPCG_HIP(hipMemcpyAsync(h->r, b, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s));
-        }
         double *z = h->precond == DPCG_PRECOND_NONE ? h->r : h->z;
         if (h->precond != DPCG_PRECOND_NONE) DPCG_TRY(apply_precond(h, h->r, h->z, s));   // cg.py:61
         launch_init_state(n, h->scal, b, h->r, z, h->p, f32 ? h->p32 : nullptr, h->part_bb, h->part_rz, h->part_rr,
                           (flags & DPCG_INIT_CHECK_R) ? 1 : 0, h->vec_grid, s);
         launch_finalize_init(h->scal, h->part_bb, h->part_rz, h->part_rr, h->vec_grid, rtol_sq, atol_sq, h->hist,
-                             h->hist_cap, ex.prog_dev, s, kMaxSpmvGrid);
+                             h->hist_cap, extras()[h].prog_dev, s, kMaxSpmvGrid);
         if (fused) {
             DPCG_HIP(hipMemsetAsync(h->p2, 0, (size_t)n * sizeof(double), s));       // "p_{-1}": multiplied by beta_0 = 0
             launch_fused_init(h->scal, s);
@@ -336,21 +414,7 @@ struct Solve {
             const int target = run_ahead();
             while (enq < max_iter && enq - k < target) DPCG_TRY(enqueue_some());
             if (!blocking) return 0;
-            // wait for the progress word to move; watch the stream so that a fault cannot hang the host
-            bool moved = false;
-            for (int spin = 0; spin < 4000 && !moved; ++spin) {
-                moved = *prog() != v;
-                if (!moved) __builtin_ia32_pause();
-            }
-            if (moved) continue;
-            const hipError_t q = hipStreamQuery(s);
-            if (q == hipErrorNotReady) continue;
-            DPCG_HIP(q);
-            // stream drained: every enqueued update has run, the word is final for them
-            if (*prog() == v && enq > k) {
-                set_error("PCG driver: enqueued updates finished without reporting progress");
-                return DPCG_ERR_STATE;
-            }
+            DPCG_TRY(wait_progress(prog(), v, s, enq > k, ""));
         }
     }
 
@@ -363,33 +427,12 @@ struct Solve {
             launch_final_deferred(n, h->scal, h->x, h->p, h->p2, h->vec_grid, s);
         else
             launch_final_check(h->scal, s);
-        DPCG_HIP(hipMemcpyAsync(h->scal_host, h->scal, sizeof(Scalars), hipMemcpyDeviceToHost, s));
-        DPCG_HIP(hipStreamSynchronize(s));
-        const auto t1 = std::chrono::steady_clock::now();                            // cg.py:88 (the loop only)
-        DPCG_TRY(check_spin_errors(h, s));
-        const Scalars sc = *h->scal_host;
-        if (seconds) *seconds = std::chrono::duration<double>(t1 - t0).count();
-        if (iters) *iters = sc.k;                                                    // cg.py:90
-        if (final_res) *final_res = sc.res;
-        bool pending = false;
-        if (res_history) {
-            DPCG_HIP(hipMemcpyAsync(res_history, h->hist, (size_t)(sc.k + 1) * sizeof(double), hipMemcpyDeviceToHost, s));
-            pending = true;
+        const int st = deliver_solve(h, {nullptr, nullptr, x, 0.0, 0.0, max_iter, flags, s, iters, final_res, seconds, res_history}, t0);
+        if (st >= 0 && err_history && x_true) {      // (the count of entries is known only now)
+            DPCG_HIP(hipMemcpyAsync(err_history, h->err_hist, (size_t)(h->scal_host->k + 1) * sizeof(double), hipMemcpyDeviceToHost, s));
+            DPCG_HIP(hipStreamSynchronize(s));
         }
-        if (err_history && x_true) {
-            DPCG_HIP(hipMemcpyAsync(err_history, h->err_hist, (size_t)(sc.k + 1) * sizeof(double),
-                                    hipMemcpyDeviceToHost, s));
-            pending = true;
-        }
-        // x is handed over in stream order: the copy is enqueued on the caller's stream, a second host sync is only
-        // needed for the host-side history buffers
-        if (x) {
-            if (h->perm) launch_scatter_f64(n, h->perm, h->x, x, s);       // back to the caller's numbering
-            else DPCG_HIP(hipMemcpyAsync(x, h->x, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s));
-        }
-        if (pending) DPCG_HIP(hipStreamSynchronize(s));
-        DPCG_CHECK_LAUNCH();
-        return sc.status;
+        return st;
     }
 };
 }  // namespace
