@@ -7,8 +7,8 @@ The solver kernels live in `csrc/` (HIP, gfx950) behind the C ABI of `include/dp
 
 from . import _lib  # noqa: F401
 from .operators import (FSAI, IC0, ICT, ILUT, ICholT, AmgHierarchy, CsrPreconditioner, CsrSystem, Identity, Jacobi, LLtMultiply, LLtSolve,  # noqa: F401
-                        OperatorPreconditioner, Preconditioner, ProjectedGuess, SmoothedAggregation, SolveResult, SpectrumBounds, as_preconditioner,
+                        OperatorPreconditioner, Preconditioner, ProjectedGuess, RefinedSolveResult, SmoothedAggregation, SolveResult, SpectrumBounds, as_preconditioner,
                         csr_arrays, dot)
 
 __all__ = ["CsrSystem", "Preconditioner", "Identity", "Jacobi", "CsrPreconditioner", "LLtMultiply", "LLtSolve", "IC0", "ICT", "ICholT", "ILUT", "FSAI", "OperatorPreconditioner",
-           "SmoothedAggregation", "AmgHierarchy", "ProjectedGuess", "SolveResult", "SpectrumBounds", "as_preconditioner", "csr_arrays", "dot"]
+           "SmoothedAggregation", "AmgHierarchy", "ProjectedGuess", "SolveResult", "RefinedSolveResult", "SpectrumBounds", "as_preconditioner", "csr_arrays", "dot"]

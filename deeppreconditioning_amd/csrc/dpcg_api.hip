@@ -328,6 +328,7 @@ static void park_precond(dpcg_system *h) {
 
 void free_precond(dpcg_system *h, bool keep_parked) {
     if (!keep_parked) free_parked(h);
+    free_refine(h);
     drop_graph(h);
     free_ell(h->ell_m);
     free_ell(h->ell_t);

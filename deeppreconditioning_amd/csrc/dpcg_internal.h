@@ -217,6 +217,7 @@ struct AmgState;   // dpcg_amg.hip: a smoothed-aggregation hierarchy
 struct FsaiCache;  // dpcg_fsai.hip: what the symbolic phase of an FSAI factor leaves on the handle
 struct NullSpace;  // dpcg_nullspace.hip: the null space attached to a singular (semi-definite) system and its solve state
 struct Deflation;  // dpcg_deflation.hip: the A-orthonormal deflation vectors W, A W and the partial buffer of a deflated solve
+struct Refine;     // dpcg_refine.hip: the fp32 copies and fp32 work vectors of dpcg_solve_refined
 
 // (dpcg_chip_trsv.hip; the comment is with ChipTrsvDesc below)
 struct ChipTrsvLists {
@@ -329,6 +330,9 @@ struct dpcg_system {
     dpcg::NullSpace *ns = nullptr;
     // dpcg_set_deflation (dpcg_deflation.hip): null = no deflation, every solve takes the paths it always took
     dpcg::Deflation *df = nullptr;
+    // dpcg_solve_refined (dpcg_refine.hip): made by its first call, dropped with the preconditioner (new values, a reordering); no other
+    // entry point reads it
+    dpcg::Refine *rf = nullptr;
 };
 
 namespace dpcg {

@@ -583,6 +583,19 @@ class SolveResult:
 
 
 @dataclass
+class RefinedSolveResult:
+    """What `CsrSystem.solve_refined` returns (dpcg_solve_refined in include/dpcg.h)."""
+    x: torch.Tensor
+    iterations: int            # inner (fp32) updates, summed over the outer steps
+    outer_steps: int           # outer residual evaluations minus one = inner solves run
+    status: int                # 0 converged, 1 max_iter (cap, max_outer or stagnation), 2 breakdown
+    final_res: float           # the last TRUE <r,r>/<b,b>, recomputed in fp64 = outer_history[-1]
+    seconds: float             # wall time of the outer loop, device-synchronised
+    res_history: np.ndarray    # iterations + 1 entries: [0] the first true value, then one rescaled recurrence value per update
+    outer_history: np.ndarray  # outer_steps + 1 true values
+
+
+@dataclass
 class SpectrumBounds:
     """Extreme eigenvalues of M A from `CsrSystem.spectrum_bounds` (a Lanczos process on the device, dpcg_spectrum).
 
@@ -997,6 +1010,26 @@ class CsrSystem:
         L.check(L.lib().dpcg_get_last_recurrence(self._h, C.byref(ran)))
         return SolveResult(x, k, status, res.value, sec.value, hist[: k + 1] if hist is not None else np.empty(0),
                            err[: k + 1] if err is not None else None, L.RECURRENCES[ran.value])
+
+    def solve_refined(self, b, x0=None, *, rtol_sq: float = 1e-8, atol_sq: float = 0.0, max_iter: int = 1024,
+                      inner_rtol_sq: float = 1e-6, max_outer: int = 16, want_history: bool = True) -> RefinedSolveResult:
+        """Mixed-precision PCG (dpcg_solve_refined in include/dpcg.h): inner PCG updates whose matrix values and vectors are stored
+        in fp32, inside an fp64 loop that recomputes the true residual and corrects x.  Opt-in; M = I or Jacobi only, no null space
+        and no deflation -- anything else raises DpcgError (ERR_INVALID) with the reason.  `final_res` is a true residual."""
+        bv = self._vec(b)
+        x0v = None if x0 is None else self._vec(x0)
+        x = torch.empty_like(bv)
+        hist = np.full(max(int(max_iter), 0) + 1, np.nan) if want_history else None
+        outer_hist = np.full(max(int(max_outer), 0) + 1, np.nan)
+        iters, outer, res, sec = C.c_int(), C.c_int(), C.c_double(), C.c_double()
+        with torch.cuda.device(self.device):
+            status = L.check(L.lib().dpcg_solve_refined(
+                self._h, _dev_ptr(bv), _dev_ptr(x0v), _dev_ptr(x), rtol_sq, atol_sq, int(max_iter), float(inner_rtol_sq),
+                int(max_outer), 0, _stream(), C.byref(iters), C.byref(outer), C.byref(res), C.byref(sec), _np_ptr(hist),
+                _np_ptr(outer_hist)))
+        k = iters.value
+        return RefinedSolveResult(x, k, outer.value, status, res.value, sec.value,
+                                  hist[: k + 1] if hist is not None else np.empty(0), outer_hist[: outer.value + 1])
 
     def amg_hierarchy(self) -> AmgHierarchy:
         """The smoothed-aggregation hierarchy of the attached `SmoothedAggregation` preconditioner (DpcgError otherwise)."""

@@ -569,6 +569,53 @@ int dpcg_get_nullspace(dpcg_handle_t h, int *k, double *Z_host);
 int dpcg_set_deflation(dpcg_handle_t h, int k, const double *W, int memspace, dpcg_stream_t stream);
 int dpcg_get_deflation(dpcg_handle_t h, int *k, double *W_host, double *AW_host);
 
+/* ---- mixed-precision PCG: fp32 inner iterations inside an fp64 refinement loop ------------------------------------------
+ * PCG whose vectors and matrix values are all STORED in fp32, wrapped in an fp64 loop that recomputes the true residual and
+ * corrects x (iterative refinement).  Not in the reference.  Storage is fp32 and arithmetic is fp64 (the convention of the fp32 AMG
+ * cycle): every product and sum is formed in fp64, a value is rounded to fp32 exactly where it is stored to an fp32 vector.
+ *     A32 = fl32(A values), dinv32 = fl32(1/a_ii) (Jacobi)      made by the first call, kept until the values, the preconditioner or
+ *                                                                the numbering change
+ *     bb = <b,b> (fp64);  x = x0 or 0 (fp64);  total = 0
+ *     outer s = 0, 1, ...:
+ *         r = b - A x                                  fp64, the handle's fp64 SpMV (x0 == NULL, s = 0: r = b)
+ *         rr = <r,r>;  outer_history[s] = rr / bb
+ *         stop OK        if rr/bb < rtol_sq or rr < atol_sq
+ *         stop MAX_ITER  if total == max_iter or s == max_outer
+ *         stop BREAKDOWN if rr is not finite
+ *         stop MAX_ITER  ("stagnated" in dpcg_last_error) if s >= 1 and rr >= 0.25 * rr_prev
+ *         sigma = sqrt(rr);  r32 = fl32(r / sigma)     (scaled: the inner problem never drifts into fp32 denormals)
+ *         target = max(inner_rtol_sq, 0.25 * rtol_sq * bb / rr)     (the last outer step does not over-solve)
+ *         inner PCG on A32 d = r32 from d = 0 with M = I or diag(dinv32): the recurrence of dpcg_solve with DPCG_INIT_CHECK_R
+ *             z = fl32(dinv32 r);  p = z;  rho = <r,z>;  first test on <r,r>
+ *             update:  q = fl32(A32 p);  alpha = rho / <p,q>;  d = fl32(d + alpha p);  r = fl32(r - alpha q);  z = fl32(dinv32 r);
+ *                      rho' = <r,z>;  p = fl32(z + (rho'/rho) p);  test <r,r> / <r32,r32> < target
+ *             at most max_iter - total updates;  d, r, z, p, q are fp32 vectors (z is never stored: both readers form the same
+ *             rounded product);  alpha, beta and all dots are fp64, the dots over the STORED (rounded) vectors
+ *         total += inner updates;  x += sigma * d      fp64
+ * iters = total, the inner updates summed over all outer steps.  outer = the number of outer residual evaluations minus one (= the
+ * number of inner solves).  final_res = the last rr / bb: a TRUE residual, not a recurrence value, and equal to the last entry
+ * written to outer_history.  outer_history: host fp64[max_outer + 1] or NULL, entries 0 .. outer.  res_history: host
+ * fp64[max_iter + 1] or NULL, iters + 1 entries: entry 0 is outer_history[0], and entry t >= 1 is the inner recurrence's <r,r>
+ * after update t rescaled to the outer problem, <r,r> * rr / bb with the rr of the outer step the update belongs to -- the
+ * histories of successive outer steps concatenated, one entry per update (an inner solve's own first entry, which restates the
+ * outer value it starts from, is not repeated).  seconds = host wall time around the whole outer loop, device-synchronised.
+ * <b,b> == 0 behaves as in dpcg_solve: rr / bb is 0/0, not a number, so the first test is OK only through atol_sq > 0 and
+ * DPCG_BREAKDOWN otherwise, with x = x0 or 0.
+ * An inner update is three launches as in the plain solve: a CSR row SpMV over fp32 values and fp32 p with its partials of <p,q>,
+ * one pass over q, r (dinv32) that leaves per-workgroup partials of <r,r> and <r,z>, one pass over r (dinv32), p, d -- 4 bytes a
+ * vector entry where the fp64 launches move 8, 8 bytes a non-zero where they move 12.  Each sum is formed in one fixed order: no
+ * float atomics.  An outer step adds the fp64 SpMV, one pass that forms r and its partials, one that scales it to fp32 and starts
+ * the inner solve, and one that adds sigma d to x; the host reads rr once per outer step.
+ * flags: 0 or DPCG_NO_GRAPH (accepted; this driver replays no graph).  Refused with DPCG_ERR_INVALID and a reason in
+ * dpcg_last_error, the handle unchanged: a preconditioner other than none or Jacobi; a handle with a null space or a deflation; any
+ * other flag; inner_rtol_sq <= 0, max_outer < 1, max_iter < 0; a matrix value or reciprocal diagonal that is not finite after
+ * rounding to fp32 (the text names the first such entry, in the handle's numbering).  A reordered handle works as for dpcg_solve:
+ * b, x0 and x are gathered and scattered, the inner solve runs in the handle's numbering.  dpcg_solve and every other entry point
+ * keep their paths and bits.  Returns DPCG_OK / DPCG_MAX_ITER / DPCG_BREAKDOWN or a negative error. */
+int dpcg_solve_refined(dpcg_handle_t h, const double *b, const double *x0, double *x, double rtol_sq, double atol_sq,
+                       int max_iter, double inner_rtol_sq, int max_outer, int flags, dpcg_stream_t stream,
+                       int *iters, int *outer, double *final_res, double *seconds, double *res_history, double *outer_history);
+
 /* `count` independent systems (train.py:90-108 / test.py:121-149 loop over samples): handles[i],
  * b[i], x0[i], x[i] as above; outputs are arrays of length count.  Systems are interleaved on
  * `n_streams` internal streams (1..8).  Returns the worst status. */
