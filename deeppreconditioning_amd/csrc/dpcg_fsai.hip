@@ -75,13 +75,19 @@ __global__ __launch_bounds__(kBlock) void k_identity(int64_t n, int32_t *__restr
     }
 }
 
-// first row of A without a stored diagonal -> *first (atomicMin)
-__global__ __launch_bounds__(kBlock) void k_missing_diag(int64_t n, const int32_t *__restrict__ rp, const int32_t *__restrict__ ci, int *first) {
+// first row of A without a stored diagonal -> *first (atomicMin); first row whose columns do not strictly ascend -> *unsorted
+// (find_entry searches A's rows by bisection: on any other row it would miss stored entries and the gather map read them as 0)
+__global__ __launch_bounds__(kBlock) void k_check_rows(int64_t n, const int32_t *__restrict__ rp, const int32_t *__restrict__ ci, int *first,
+                                                       int *unsorted) {
     const int64_t stride = (int64_t)gridDim.x * kBlock;
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
-        bool have = false;
-        for (int k = rp[i]; k < rp[i + 1]; ++k) have |= ci[k] == i;
+        bool have = false, asc = true;
+        for (int k = rp[i]; k < rp[i + 1]; ++k) {
+            have |= ci[k] == i;
+            asc &= k + 1 >= rp[i + 1] || ci[k] < ci[k + 1];
+        }
         if (!have) atomicMin(first, (int)i);
+        if (!asc) atomicMin(unsorted, (int)i);
     }
 }
 
@@ -531,19 +537,25 @@ int symbolic_rest(FsaiCache &c, const CsrDev &A, hipStream_t s) {
 int symbolic(FsaiCache &c, const CsrDev &A, hipStream_t s) {
     const int64_t n = A.n;
     c.n = n;
-    if (c.level > 0) {
+    {
         Buf<int> first;
-        DPCG_TRY(first.alloc(1));
-        const int none = kNoColumn;
-        DPCG_HIP(hipMemcpyAsync(first.p, &none, sizeof(int), hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_missing_diag, dim3(grid_of(n)), dim3(kBlock), 0, s, n, A.rowptr, A.col, first.p);
-        int h_first = kNoColumn;
-        DPCG_HIP(hipMemcpyAsync(&h_first, first.p, sizeof(int), hipMemcpyDeviceToHost, s));
+        DPCG_TRY(first.alloc(2));
+        const int none[2] = {kNoColumn, kNoColumn};
+        DPCG_HIP(hipMemcpyAsync(first.p, none, sizeof(none), hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_check_rows, dim3(grid_of(n)), dim3(kBlock), 0, s, n, A.rowptr, A.col, first.p, first.p + 1);
+        int h_first[2] = {kNoColumn, kNoColumn};
+        DPCG_HIP(hipMemcpyAsync(h_first, first.p, sizeof(h_first), hipMemcpyDeviceToHost, s));
         DPCG_HIP(hipStreamSynchronize(s));
-        if (h_first != kNoColumn) {
-            set_error("fsai: structurally missing diagonal at column " + std::to_string(h_first));
+        if (h_first[1] != kNoColumn) {
+            set_error("fsai: the matrix must have strictly ascending columns in every row (row " + std::to_string(h_first[1]) + " has not)");
             return DPCG_ERR_INVALID;
         }
+        if (c.level > 0 && h_first[0] != kNoColumn) {
+            set_error("fsai: structurally missing diagonal at column " + std::to_string(h_first[0]));
+            return DPCG_ERR_INVALID;
+        }
+    }
+    if (c.level > 0) {
         Buf<int32_t> xrp, xci;
         DPCG_TRY(xrp.alloc(n + 1));
         DPCG_TRY(xci.alloc(n));

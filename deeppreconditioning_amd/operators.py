@@ -304,7 +304,9 @@ class FSAI(Preconditioner):
     level=k (1, 2 or 3): P = the structural pattern of A^k (level 1: tril(A), as IC(0)).  pattern=: tril(P) by rows as a scipy
     matrix or (rowptr, col) arrays -- lower triangular, ascending columns, the diagonal in every row; values are ignored.
     The factor equals tests/fsai_restatement.py bit for bit; `CsrSystem.factor()` returns it, `CsrSystem.fsai_info()` describes
-    it.  See dpcg_set_precond_fsai in include/dpcg.h for the limits (local systems of at most 64 unknowns).
+    it.  See dpcg_set_precond_fsai in include/dpcg.h for the limits (local systems of at most 64 unknowns).  Unlike the solves, FSAI
+    needs the system's rows to have strictly ascending columns: attaching it to a system created from unsorted parts raises
+    DpcgError (ERR_INVALID, "ascending") and leaves the previous preconditioner in place.
 
     level and pattern are mutually exclusive: with a pattern, level must be left at its default (1, which then means nothing) or
     be None; any other level beside a pattern raises."""

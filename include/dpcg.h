@@ -227,7 +227,9 @@ int dpcg_get_lu_factors(dpcg_handle_t h, int64_t *l_nnz, int64_t *u_nnz, int32_t
  * and C^T y = w column-oriented (s_p -= c_pj w_j for j ascending; s_p -= c_jp y_j for j descending; w_j, y_j = s_j / c_jj);
  * l_p = y_p / sqrt(y_0).  No tree-shaped sums.
  * Limits and errors: m_i <= 64 (beyond: DPCG_ERR_INVALID, the text names the column and its m_i); a structurally missing
- * diagonal and a level outside 1 .. 3 are DPCG_ERR_INVALID; a non-positive or non-finite pivot of a local Cholesky is
+ * diagonal and a level outside 1 .. 3 are DPCG_ERR_INVALID; so is a matrix with a row whose columns do not strictly ascend (the
+ * solves take such rows, but the gather map is built by bisection on A's rows: both calls check every row and refuse, the text
+ * says "ascending" and names the first such row -- they never return a factor of entries they failed to find); a non-positive or non-finite pivot of a local Cholesky is
  * DPCG_ERR_PIVOT (the text names the column); the gather map holds sum m_i (m_i + 1) / 2 int32 entries, at most 2^31
  * (DPCG_ERR_INVALID beyond).  On any failure the previous preconditioner stays.
  * Reuse: the pattern, the gather map and the binning by m_i stay on the handle, keyed on (level | the explicit pattern), across
