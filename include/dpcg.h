@@ -583,7 +583,7 @@ int dpcg_get_deflation(dpcg_handle_t h, int *k, double *W_host, double *AW_host)
  *         rr = <r,r>;  outer_history[s] = rr / bb
  *         stop OK        if rr/bb < rtol_sq or rr < atol_sq
  *         stop MAX_ITER  if total == max_iter or s == max_outer
- *         stop BREAKDOWN if rr is not finite
+ *         stop BREAKDOWN if rr is not finite or rr / bb is not a number
  *         stop MAX_ITER  ("stagnated" in dpcg_last_error) if s >= 1 and rr >= 0.25 * rr_prev
  *         sigma = sqrt(rr);  r32 = fl32(r / sigma)     (scaled: the inner problem never drifts into fp32 denormals)
  *         target = max(inner_rtol_sq, 0.25 * rtol_sq * bb / rr)     (the last outer step does not over-solve)
@@ -601,8 +601,14 @@ int dpcg_get_deflation(dpcg_handle_t h, int *k, double *W_host, double *AW_host)
  * after update t rescaled to the outer problem, <r,r> * rr / bb with the rr of the outer step the update belongs to -- the
  * histories of successive outer steps concatenated, one entry per update (an inner solve's own first entry, which restates the
  * outer value it starts from, is not repeated).  seconds = host wall time around the whole outer loop, device-synchronised.
- * <b,b> == 0 behaves as in dpcg_solve: rr / bb is 0/0, not a number, so the first test is OK only through atol_sq > 0 and
- * DPCG_BREAKDOWN otherwise, with x = x0 or 0.
+ * <b,b> == 0 behaves as in dpcg_solve: from x0 == NULL or an x0 with A x0 == 0, rr / bb is 0/0, not a number, so the first test is
+ * OK only through atol_sq > 0, DPCG_MAX_ITER with max_iter == 0 (the tests run in the order above) and DPCG_BREAKDOWN otherwise, with
+ * x = x0 or 0 and no update done.  (From any other x0 it is rr / 0 = +inf: never OK through rtol_sq, and no breakdown.)  A b that
+ * holds a NaN or an infinity stops the same way at the first test.  inner_rtol_sq > 1 makes every inner solve one of zero updates
+ * (its first test, 1 < target, passes): x stays as it is and the next outer test ends the call "stagnated".
+ * An inner solve that breaks down -- <p,q> is 0 or not finite, as when every value of A rounds to 0 in fp32 (finite, so not
+ * refused) -- ends at that update, which is counted and whose history entry is NaN; its d, not finite, is added to x as it is, and
+ * the next outer residual, not finite either, stops the call with DPCG_BREAKDOWN.
  * An inner update is three launches as in the plain solve: a CSR row SpMV over fp32 values and fp32 p with its partials of <p,q>,
  * one pass over q, r (dinv32) that leaves per-workgroup partials of <r,r> and <r,z>, one pass over r (dinv32), p, d -- 4 bytes a
  * vector entry where the fp64 launches move 8, 8 bytes a non-zero where they move 12.  Each sum is formed in one fixed order: no

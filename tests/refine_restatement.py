@@ -26,8 +26,9 @@ f32 = np.float32
 
 
 def _dot(a, b, reverse):
+    # np.float64, not float: x / 0 is inf or NaN as on the device (under np.errstate), where a Python float would raise
     a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    return float(a[::-1] @ b[::-1]) if reverse else float(a @ b)
+    return np.float64(a[::-1] @ b[::-1]) if reverse else np.float64(a @ b)
 
 
 def rounded_matrix(A):

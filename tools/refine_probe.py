@@ -2,6 +2,7 @@
 
     python tools/refine_probe.py --cpu-spread      # no GPU: the section "Count margin" of profiles/refine_probe.md
     python tools/refine_probe.py                   # on the GPU: the section "Time to the solution"
+    python tools/refine_probe.py --edges           # profiles/refine_edges.md: the CPU sections, and the device's where there is a GPU
 
 Count margin (CPU, the numpy restatement tests/refine_restatement.py): the systems, preconditioners and tolerances of
 tests/test_refine_gpu.py, each solved as it stands, with b perturbed by 1e-16 and by 1e-12 relative, and with every dot summed back to
@@ -28,12 +29,13 @@ sys.path.insert(0, str(ROOT / "tests"))
 
 PROFILE = ROOT / "profiles" / "refine_probe.md"
 BEGIN, END = "<!-- {0}: begin -->", "<!-- {0}: end -->"
+EDGES_PROFILE = ROOT / "profiles" / "refine_edges.md"
 REPEATS = 5
 
 
-def write_section(tag, lines):
+def write_section(tag, lines, PROFILE=PROFILE, title="# Mixed-precision PCG (dpcg_solve_refined)\n"):
     """replace (or append) one section of the profile, leaving the other as it is"""
-    text = PROFILE.read_text() if PROFILE.exists() else "# Mixed-precision PCG (dpcg_solve_refined)\n"
+    text = PROFILE.read_text() if PROFILE.exists() else title
     block = "\n".join([BEGIN.format(tag)] + lines + [END.format(tag)])
     if BEGIN.format(tag) in text:
         head, rest = text.split(BEGIN.format(tag), 1)
@@ -144,8 +146,85 @@ def gpu_timing():
     print("\n".join(lines))
 
 
+def edges():
+    """profiles/refine_edges.md: what tests/test_refine_edges_host.py asserts and tests/test_refine_edges_gpu.py compares, as figures"""
+    import refine_edge_cases as C
+    title = "# Mixed-precision PCG at its edges (tests/test_refine_edges_*.py)\n"
+    put = lambda tag, lines: write_section(tag, lines, EDGES_PROFILE, title)
+    lines = ["## Short runs: CPU spread and tolerance", "", "`python tools/refine_probe.py --edges`.  One inner solve of t updates "
+             "(`max_iter=t, rtol_sq=1e-30, inner_rtol_sq=1e-300`, x0 = None), the numpy restatement as it stands against itself with "
+             + ", ".join(C.PERTURBATIONS) + ": the largest per-entry spread of x in fp32 ulps of ||x||_inf and of a history entry, "
+             "relatively, over both preconditioners and t = 1, 2, 3.  The device may differ by twice the spread, at least by the floor "
+             f"(1 ulp; {C.HIST_FLOOR:.3g} = 2^-22).", "",
+             "| system | rows | lanes per row | spread of x (ulp) | spread of the history | tolerance of x (ulp) | tolerance of the history |",
+             "|---|---|---|---|---|---|---|"]
+    for name in C.SYSTEMS:
+        A, _ = C.system(name)
+        got = [C.measure_spread(name, pre, t) for pre in C.PRES for t in C.TS]
+        sx, sh = max(g[0] for g in got), max(g[1] for g in got)
+        lines.append(f"| {name} | {A.shape[0]} | {C.lanes_per_row(A)} | {sx:.3g} | {sh:.3g} | {max(2 * sx, 1.0):.3g} | {max(2 * sh, C.HIST_FLOOR):.3g} |")
+    lines += ["", "No perturbation flips an fp32 rounding in runs this short: every spread is that of the fp64 scalars alone, and the floors are "
+              "the tolerances."]
+    put("cpu spread", lines)
+    lines = ["## Mutants: one entry of A32 set to zero", "", "Distance of the mutated restatement from the true one over the tolerance of x, "
+             "at t = 1, 2, 3 (the test asks >= 10 at t = 2 and 3; `-`: the system has no such entry).", "",
+             "| system | M | " + " | ".join(C.MUTANTS) + " |", "|---|---|---|---|---|"]
+    for name in C.SYSTEMS:
+        for pre in C.PRES:
+            cells = []
+            for which in C.MUTANTS:
+                f = [C.mutant_factor(name, pre, t, which) for t in C.TS]
+                cells.append("-" if f[0] is None else ", ".join(f"{v:.3g}" for v in f))
+            lines.append(f"| {name} | {pre} | " + " | ".join(cells) + " |")
+    put("mutants", lines)
+    lines = ["## Stagnation candidates", "", "M = I, rtol_sq = 1e-30, b = default_rng(1).random(n); a candidate qualifies when it ends "
+             "\"stagnated\" after at least one productive outer step with every outer margin and the stop's own margin, "
+             "rr / (0.25 rr_prev), >= 1.2.", "",
+             "| system | reason | outer steps | updates | smallest outer margin | margin of the stop | outer history | qualifies |", "|---|---|---|---|---|---|---|---|"]
+    for name in C.STAGNATION_CANDIDATES:
+        _, _, run = C.stagnation_run(name)
+        margin = min(run["outer_margins"]) if run["outer_margins"] else 0.0
+        lines.append(f"| {name} | {run['reason']} | {run['outer_steps']} | {run['iterations']} | {margin:.3g} | {C.stagnation_margin(run):.3g} | "
+                     + ", ".join(f"{h:.2e}" for h in run["outer_history"]) + f" | {'yes' if C.qualifies_as_stagnation(run) else 'no'} |")
+    lines += ["", "Stop cases (tests/refine_edge_cases.py, `stop_cases`): the restatement's status, updates, outer steps and smallest outer margin.", "",
+              "| case | status | updates | outer steps | reason | smallest outer margin |", "|---|---|---|---|---|---|"]
+    for case in C.stop_cases():
+        r = C.stop_restated(case)
+        lines.append(f"| {case} | {r['status']} | {r['iterations']} | {r['outer_steps']} | {r['reason']} | "
+                     + (f"{min(r['outer_margins']):.3g}" if r["outer_margins"] else "-") + " |")
+    lines += ["", f"Power-of-two scalings of {C.SCALING_SYSTEM}: (k, m) = {C.SCALINGS} leave the restatement's x 2^(m-k) x, counts and histories "
+              "bit for bit; k = 60 was not shrunk."]
+    put("stops", lines)
+    try:
+        import torch
+        have = torch.cuda.is_available()
+    except ImportError:
+        have = False
+    if not have:
+        print(f"no GPU: the section of the device's distances in {EDGES_PROFILE} is left as it is")
+        return
+    import deeppreconditioning_amd as D
+    lines = ["## The device against the restatement", "", f"`python tools/refine_probe.py --edges` on {torch.cuda.get_device_properties(0).gcnArchName}: "
+             "per-entry distance of `solve_refined`'s x (fp32 ulps of ||x||_inf) and of its inner history (relative) from the restatement.", "",
+             "| system | M | t | lanes per row | distance of x (ulp) | distance of the history |", "|---|---|---|---|---|---|"]
+    wx = wh = 0.0
+    for name, pre, t in C.SHORT_CASES:
+        A, b = C.system(name)
+        ref = C.short_run(name, pre, t)
+        S = D.CsrSystem.from_any(A, reorder=None)
+        S.set_preconditioner(D.Jacobi() if pre == "jacobi" else None)
+        res = S.solve_refined(torch.from_numpy(b).cuda(), **C.short_kwargs(t))
+        dx, dh = C.x_distance(res.x.cpu().numpy(), ref["x"], b), C.hist_distance(res.res_history, ref["res_history"])
+        wx, wh = max(wx, dx), max(wh, dh)
+        lines.append(f"| {name} | {pre} | {t} | {C.lanes_per_row(A)} | {dx:.3g} | {dh:.3g} |")
+    lines += ["", f"Largest: **{wx:.3g} ulp** of x, **{wh:.3g}** of a history entry: the device's sums, formed in another order, flip no fp32 "
+              "rounding in these runs either."]
+    put("device", lines)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--cpu-spread", action="store_true")
+    ap.add_argument("--edges", action="store_true")
     args = ap.parse_args()
-    cpu_spread() if args.cpu_spread else gpu_timing()
+    edges() if args.edges else cpu_spread() if args.cpu_spread else gpu_timing()
