@@ -211,6 +211,8 @@ int64_t launch_stream_bench(int n_read, bool write, bool nt, int64_t out_bytes, 
 // sparse_matvec_mul (utils.py:26-41): out[b, row] += feature * vec[b, col] over COO triples.
 // One lane per triple, fp32 atomics on the output -- the same scatter-add the reference's own
 // CUDA path performs (torch scatter_reduce on a GPU tensor is an atomicAdd).
+// Range guard (include/dpcg.h): a triple outside [0,batch) x [0,dof)^2 is skipped, nothing is read for it.  There is NO test for
+// a zero feature here, unlike k_batched_coo_spmm: 0 * inf and 0 * NaN reach the output as NaN (IEEE 754), as in the reference.
 __global__ __launch_bounds__(kBlock) void k_batched_coo_spmv(int64_t nnz, const int32_t *__restrict__ idx,
                                                              const float *__restrict__ feat, int batch, int64_t dof,
                                                              const float *__restrict__ vec, float *__restrict__ out,
@@ -227,7 +229,7 @@ __global__ __launch_bounds__(kBlock) void k_batched_coo_spmv(int64_t nnz, const 
 
 // Per-triple products out[k] = a[b, row_k] * c[b, col_k]: the gradient of sparse_matvec_mul with respect to the
 // matrix entries (d/d feature_k of sum_b <g_b, A_b v_b> = g[b,row_k] * v[b,col_k]); needed to train through
-// `frobenius_loss` (metrics.py:28-29).
+// `frobenius_loss` (metrics.py:28-29).  Every out[k] is written: a triple out of range (the range guard) gets 0.0f.
 __global__ __launch_bounds__(kBlock) void k_batched_coo_edge(int64_t nnz, const int32_t *__restrict__ idx, int batch,
                                                              int64_t dof, const float *__restrict__ a,
                                                              const float *__restrict__ c, float *__restrict__ out,
@@ -245,6 +247,8 @@ __global__ __launch_bounds__(kBlock) void k_batched_coo_edge(int64_t nnz, const 
 // The same two operators with `ncols` right-hand sides per sample (row-major panels B[b, row, c]): what the sparse form of
 // `inverse_loss` (metrics.py:34-55) is made of -- L^T (A[:, J]) and L (.) on a panel of columns J instead of dense N x N
 // products.  One lane per (triple, column): consecutive lanes take consecutive columns of a panel row (coalesced).
+// Two guards (include/dpcg.h): a triple out of range is skipped, and so is a triple whose feature is 0.0f (either sign) BEFORE
+// its panel row is read -- an inf or NaN there stays out of the result, where IEEE's 0 * inf would have put a NaN.
 __global__ __launch_bounds__(kBlock) void k_batched_coo_spmm(int64_t nnz, const int32_t *__restrict__ idx,
                                                              const float *__restrict__ feat, int batch, int64_t dof,
                                                              int ncols, const float *__restrict__ B,
@@ -265,7 +269,8 @@ __global__ __launch_bounds__(kBlock) void k_batched_coo_spmm(int64_t nnz, const 
 }
 
 // out[k] = sum_c G[b, row_k, c] * B[b, col_k, c]: the gradient of the panel product with respect to entry k.
-// One wave per triple, lanes over the columns, fixed-order wave sum.
+// One wave per triple, lanes over the columns, fixed-order wave sum.  Every out[k] is written: a triple out of range (the
+// range guard) gets 0.0f.  No feature is read, so there is no zero test: a non-finite panel row gives a non-finite out[k].
 __global__ __launch_bounds__(kBlock) void k_batched_coo_sddmm(int64_t nnz, const int32_t *__restrict__ idx, int batch,
                                                               int64_t dof, int ncols, const float *__restrict__ G,
                                                               const float *__restrict__ B, float *__restrict__ out,

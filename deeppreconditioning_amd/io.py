@@ -21,15 +21,15 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .operators import CsrSystem, _dev_ptr, _stream
+from .operators import CsrSystem, _dev_ptr, _int32_indices, _stream
 
 
 def coo_to_csr_device(rows, cols, vals, n: int, device=None):
     """(rowptr int32[n+1], col int32[nnz'], val float64[nnz']) CUDA tensors from coordinate triplets; duplicates are
     summed, columns ascend within a row."""
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    r = torch.as_tensor(np.asarray(rows) if not isinstance(rows, torch.Tensor) else rows).to(device=device, dtype=torch.int32).contiguous()
-    c = torch.as_tensor(np.asarray(cols) if not isinstance(cols, torch.Tensor) else cols).to(device=device, dtype=torch.int32).contiguous()
+    r = _int32_indices(rows, device, "coo_to_csr_device: rows")       # (ValueError where .to(int32) would wrap an index)
+    c = _int32_indices(cols, device, "coo_to_csr_device: cols")
     v = torch.as_tensor(np.asarray(vals) if not isinstance(vals, torch.Tensor) else vals).to(device=device, dtype=torch.float64).contiguous()
     nnz = r.numel()
     if c.numel() != nnz or v.numel() != nnz:

@@ -92,6 +92,22 @@ def _dev_ptr(t: torch.Tensor | None, dtype=None):
     return C.c_void_p(t.data_ptr())
 
 
+def _int32_indices(t, device, what: str) -> torch.Tensor:
+    """`t` as a contiguous int32 tensor on `device`.  A value that does not fit int32 raises ValueError: `.to(torch.int32)` alone
+    wraps it (3 + 2**32 becomes the valid index 3).  int32 input, the hot path, is not inspected."""
+    is_tensor = isinstance(t, torch.Tensor)
+    if not is_tensor:
+        t = np.asarray(t)
+    narrow = t.dtype == (torch.int32 if is_tensor else np.dtype(np.int32))
+    if not narrow and (t.numel() if is_tensor else t.size) > 0:
+        lo, hi = (int(v) for v in (torch.aminmax(t) if is_tensor else (t.min(), t.max())))
+        if lo < -2 ** 31 or hi > 2 ** 31 - 1:
+            raise ValueError(f"{what}: an index in [{lo}, {hi}] does not fit int32")
+    if not is_tensor:
+        t = torch.from_numpy(np.ascontiguousarray(t, dtype=np.int32))
+    return t.to(device=device, dtype=torch.int32).contiguous()
+
+
 def _np_ptr(a: np.ndarray | None):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 

@@ -7,7 +7,7 @@ import ctypes as C
 import torch
 
 from . import _lib as L
-from .operators import CsrSystem, _dev_ptr, _stream
+from .operators import CsrSystem, _dev_ptr, _int32_indices, _stream
 
 
 def _coo_spmv(idx, feat, vec, transpose: bool) -> torch.Tensor:
@@ -83,15 +83,16 @@ class _SparseMatmat(torch.autograd.Function):
 
 
 def sparse_matmat_mul(spconv_batch, panel: torch.Tensor, transpose: bool) -> torch.Tensor:
-    """`sparse_matvec_mul` for a panel (batch, dof, ncols) of right-hand sides, differentiable."""
+    """`sparse_matvec_mul` for a panel (batch, dof, ncols) of right-hand sides, differentiable.  Computed in fp32, returned in the
+    panel's dtype, as `sparse_matvec_mul` returns its vectors'."""
     if not panel.is_cuda:
         raise ValueError("sparse_matmat_mul runs on the GPU: the panel must be a CUDA tensor")
     dev = panel.device
-    idx = spconv_batch.indices.to(device=dev, dtype=torch.int32).contiguous()
+    idx = _int32_indices(spconv_batch.indices, dev, "sparse_matmat_mul")
     feat = spconv_batch.features.to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
     if panel.shape[0] != spconv_batch.batch_size:
         raise ValueError("batch size mismatch")
-    return _SparseMatmat.apply(feat, panel.to(torch.float32).contiguous(), idx, bool(transpose))
+    return _SparseMatmat.apply(feat, panel.to(torch.float32).contiguous(), idx, bool(transpose)).to(panel.dtype)
 
 
 def sparse_matvec_mul(spconv_batch, vector_batch: torch.Tensor, transpose: bool) -> torch.Tensor:
@@ -103,7 +104,7 @@ def sparse_matvec_mul(spconv_batch, vector_batch: torch.Tensor, transpose: bool)
     dev = vector_batch.device
     if not vector_batch.is_cuda:
         raise ValueError("sparse_matvec_mul runs on the GPU: vector_batch must be a CUDA tensor")
-    idx = spconv_batch.indices.to(device=dev, dtype=torch.int32).contiguous()
+    idx = _int32_indices(spconv_batch.indices, dev, "sparse_matvec_mul")
     feat = spconv_batch.features.to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
     vec = vector_batch.to(torch.float32).contiguous()
     if vec.shape[0] != spconv_batch.batch_size:

@@ -638,12 +638,21 @@ int dpcg_gen_poisson(int dim, int64_t n, int32_t *rowptr, int32_t *col, void *va
                      dpcg_stream_t stream);
 
 /* ---- sparse_matvec_mul (utils.py:15-43): batched COO SpMV / SpMV^T, fp32 ---------------------- */
-/* indices: int32[nnz*3] rows of (batch,row,col); features fp32[nnz]; vectors/out fp32[batch*dof]. */
+/* indices: int32[nnz*3] rows of (batch,row,col); features fp32[nnz]; vectors/out fp32[batch*dof].
+ *
+ * Two guards hold for the four dpcg_batched_coo_* entry points below:
+ *   range:  a triple with batch_k outside [0, batch) or row_k / col_k outside [0, dof) is not an error.  spmv and spmm SKIP it
+ *           (it adds nothing to `out`); edge and sddmm, which own out[k], write out[k] = 0.0f.  No operand is read for it.
+ *   zero:   spmm alone skips a triple whose features[k] == 0.0f (+0 or -0: the masked upper triangle of the network output),
+ *           so a non-finite panel entry under an explicit zero stays out of the result.  spmv has no such test: there
+ *           0 * inf and 0 * NaN are NaN, as IEEE 754 has them.  edge and sddmm read no feature.
+ * Duplicate triples are legal and add up (fp32 atomics: the order of the additions, and so the last bits, vary from run to run). */
 int dpcg_batched_coo_spmv(int64_t nnz, const int32_t *indices, const float *features, int batch, int64_t dof,
                           const float *vectors, float *out, int transpose, dpcg_stream_t stream);
 
 /* Gradient of sparse_matvec_mul w.r.t. the matrix entries (training through frobenius_loss, metrics.py:28-29):
- * out[k] = a[batch_k, row_k] * c[batch_k, col_k] with (row,col) as in dpcg_batched_coo_spmv for `transpose`. */
+ * out[k] = a[batch_k, row_k] * c[batch_k, col_k] with (row,col) as in dpcg_batched_coo_spmv for `transpose`: ONE fp32
+ * product, the same bits on every run.  A triple out of range gives out[k] = 0.0f (the range guard above). */
 int dpcg_batched_coo_edge(int64_t nnz, const int32_t *indices, int batch, int64_t dof, const float *a, const float *c,
                           float *out, int transpose, dpcg_stream_t stream);
 
@@ -651,7 +660,9 @@ int dpcg_batched_coo_edge(int64_t nnz, const int32_t *indices, int batch, int64_
  * building blocks of `inverse_loss` (metrics.py:34-55, the loss train.py:59 minimises) WITHOUT the reference's dense
  * N x N products: || L L^T A - I ||_F is accumulated over panels of columns J as L (L^T A[:, J]) - I[:, J].
  * spmm: out[b, row_k, :] += features[k] * panel[b, col_k, :]; sddmm: out[k] = <g[b, row_k, :], panel[b, col_k, :]> (the
- * gradient of spmm with respect to features[k]).  (row, col) swap under `transpose` as in dpcg_batched_coo_spmv. */
+ * gradient of spmm with respect to features[k]).  (row, col) swap under `transpose` as in dpcg_batched_coo_spmv.
+ * Guards as stated there: spmm skips a triple out of range AND a triple with features[k] == 0.0f; sddmm writes out[k] = 0.0f
+ * for a triple out of range and has no zero test (its result for a zero feature is the full dot product). */
 int dpcg_batched_coo_spmm(int64_t nnz, const int32_t *indices, const float *features, int batch, int64_t dof, int ncols,
                           const float *panel, float *out, int transpose, dpcg_stream_t stream);
 int dpcg_batched_coo_sddmm(int64_t nnz, const int32_t *indices, int batch, int64_t dof, int ncols, const float *g,
