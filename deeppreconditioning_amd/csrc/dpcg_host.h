@@ -172,7 +172,8 @@ bool chip_trsv_shape(const dpcg_system *h, int flags, const double *x_true);
 bool chip_default(const dpcg_system *h, int flags);
 const char *chip_sr_refusal(const dpcg_system *h, int flags, const double *x_true);
 void free_chip_trsv(dpcg_system *h);               // the plan of the triangular-solve form (goes with the preconditioner)
-// one solve as dpcg_solve takes it (b, x0 and x in the caller's numbering; the last four may be null)
+// one solve as dpcg_solve takes it (b, x0 and x in the caller's numbering; everything from iters on may be null): the record every form,
+// its descriptor and its tail take
 struct SolveCall {
     const double *b, *x0;
     double *x;
@@ -181,20 +182,33 @@ struct SolveCall {
     hipStream_t s;
     int *iters;
     double *final_res, *seconds, *res_history;
+    const double *x_true = nullptr;       // (the launch path only: every other form refuses a call that tracks the error)
+    double *err_history = nullptr;
 };
 // ... by a whole-chip form; DPCG_ERR_STATE: not taken (refused up front, or never co-resident), the caller goes on with the launches
 int solve_chip_one(dpcg_system *h, SolveCall c);          // M = I / Jacobi
 int solve_chip_sr_one(dpcg_system *h, SolveCall c);       // ... with the single-reduction recurrence
 int solve_chip_llt_one(dpcg_system *h, SolveCall c);      // M = L L^T multiplied
 int solve_chip_trsv_one(dpcg_system *h, SolveCall c);     // M = (L L^T)^-1 by two triangular solves
-// ---- the pieces of a launch-path solve (dpcg_solve.hip), shared by the plain driver and the two projected ones --------------------------
+// The end of a one-launch solve (one workgroup, one team, the whole chip) whose kernel was enqueued at t0: the scalars, ONE synchronise,
+// the timer, the launch check; never_resident (null: the one-workgroup form, no co-residency to account for): the error of a launch whose
+// workgroups waited in vain, co_residency() is told either way; ran(sc), if any, after a launch that ran; then deliver_results with x in
+// place.  Returns the solve's status.
+int finish_one_launch(dpcg_system *h, const SolveCall &c, std::chrono::steady_clock::time_point t0, const char *never_resident,
+                      const std::function<int(const Scalars &)> &ran = nullptr);
+// ---- the pieces of a launch-path solve (dpcg_solve.hip), shared by the plain driver, the two projected ones and dpcg_solve_refined; the
+// ---- last three of them (deliver_results, hand_over_x, gather_rhs) by the one-launch forms too ----------------------------------------
 // how the vector kernels see M: 0 = I, 1 = Jacobi (z = dinv r on the fly), 2 = anything else (an apply between K2 and K3)
 inline int precond_class(const dpcg_system *h) { return h->precond == DPCG_PRECOND_NONE ? 0 : (h->precond == DPCG_PRECOND_JACOBI ? 1 : 2); }
 // the handle's permutation on the host (empty: the handle is not reordered)
 int read_perm(const dpcg_system *h, std::vector<int32_t> &perm, hipStream_t s);
-// Staging of a call: the work vectors, the progress word zeroed, b gathered into the handle's numbering, x = x0 or 0, and
-// r = b - A x or r = b.  rhs (may be empty) is called with the gathered b and returns the right-hand side to use in its place.
-// *b_used: that right-hand side.
+// Staging of a call, in two parts.  stage_vectors: the work vectors, the progress word zeroed, b gathered into the handle's numbering
+// (*b_used), x = x0 or 0 -- all dpcg_solve_refined takes, it forms its own residual.  stage_residual: r = b - A x or r = b.
+// stage_call: both; rhs (may be empty) is called with the gathered b in between and returns the right-hand side to use in its place
+// (*b_used: that one).
+int stage_vectors(dpcg_system *h, const double *b, const double *x0, int max_iter, bool need_f32, bool need_err, hipStream_t s,
+                  const double **b_used);
+int stage_residual(dpcg_system *h, const double *b, bool have_x0, hipStream_t s);
 int stage_call(dpcg_system *h, const double *b, const double *x0, int max_iter, bool need_f32, bool need_err, hipStream_t s,
                const double **b_used, const std::function<const double *(const double *)> &rhs = nullptr);
 // Waits until the progress word leaves v -- a bounded spin, then a look at the stream so that a fault cannot hang the host.  Returns
@@ -206,8 +220,14 @@ int wait_progress(volatile unsigned long long *prog, unsigned long long v, hipSt
 int run_launch_ahead(dpcg_system *h, int max_iter, hipStream_t s, std::chrono::steady_clock::time_point t0, const char *tag,
                      const std::function<int()> &enqueue_update);
 // The delivery tail, after the finaliser has been enqueued: the scalars, the end of the timer (c.seconds counts from t0), errors of the
-// sync-free triangular solves, iters / final_res / res_history, x in the caller's numbering.  Returns the solve's status.
+// sync-free triangular solves (which only this path can meet), then deliver_results.  Returns the solve's status.
 int deliver_solve(dpcg_system *h, const SolveCall &c, std::chrono::steady_clock::time_point t0);
+// What every tail ends in: iters / final_res / seconds, res_history (a second synchronise only when it was asked for), x handed over in
+// stream order (hand_over_x: h->x to the caller's x and numbering) unless the kernel wrote it in place and the handle is not reordered.
+int deliver_results(dpcg_system *h, const SolveCall &c, const Scalars &sc, double seconds, bool x_in_place);
+int hand_over_x(dpcg_system *h, double *x, hipStream_t s);
+// b into the handle's numbering (h->pb) where the handle is reordered
+int gather_rhs(dpcg_system *h, const double *&b, hipStream_t s);
 // dpcg_nullspace.hip: singular systems with an attached null space (dpcg_set_nullspace).  Why a solve with these arguments is refused
 // (nullptr: it is not); the solve itself, whatever the system's size; the check of A Z = 0 again after dpcg_update_values; the release
 const char *nullspace_refusal(const dpcg_system *h, int flags, const double *x_true);

@@ -481,19 +481,7 @@ extern "C" int dpcg_solve_refined(dpcg_handle_t h, const double *b, const double
     DPCG_TRY(ensure_refine(h, s));
     Refine *rf = h->rf;
     const bool jac = rf->dinv32 != nullptr;
-    // staging, as stage_call: the work vectors, b gathered into the handle's numbering, x = x0 or 0
-    DPCG_TRY(ensure_work(h, max_iter, false, false));
-    if (h->perm) {
-        if (!h->pb) DPCG_TRY(dev_alloc(&h->pb, n));
-        launch_gather_f64(n, h->perm, b, h->pb, s);
-        b = h->pb;
-    }
-    if (x0) {
-        if (h->perm) launch_gather_f64(n, h->perm, x0, h->x, s);
-        else DPCG_HIP(hipMemcpyAsync(h->x, x0, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s));
-    } else {
-        DPCG_HIP(hipMemsetAsync(h->x, 0, (size_t)n * sizeof(double), s));
-    }
+    DPCG_TRY(stage_vectors(h, b, x0, max_iter, false, false, s, &b));       // (the residual is formed below, with its sums)
     DPCG_CHECK_LAUNCH();
     DPCG_HIP(hipStreamSynchronize(s));
     const auto t0 = std::chrono::steady_clock::now();
@@ -556,10 +544,7 @@ extern "C" int dpcg_solve_refined(dpcg_handle_t h, const double *b, const double
     if (iters) *iters = total;
     if (outer) *outer = s_out;
     if (final_res) *final_res = res;
-    if (x) {
-        if (h->perm) launch_scatter_f64(n, h->perm, h->x, x, s);       // back to the caller's numbering
-        else DPCG_HIP(hipMemcpyAsync(x, h->x, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s));
-    }
+    if (x) DPCG_TRY(hand_over_x(h, x, s));
     DPCG_CHECK_LAUNCH();
     return status;
 }

@@ -12,6 +12,7 @@
 
 #include "dpcg_host.h"
 #include "dpcg_prims.h"
+#include "dpcg_stream_set.h"
 
 // ------------------------------------------------------------------------------------------------
 // the solve
@@ -192,28 +193,42 @@ int read_perm(const dpcg_system *h, std::vector<int32_t> &perm, hipStream_t s) {
     return DPCG_OK;
 }
 
-int stage_call(dpcg_system *h, const double *b, const double *x0, int max_iter, bool need_f32, bool need_err, hipStream_t s,
-               const double **b_used, const std::function<const double *(const double *)> &rhs) {
+int gather_rhs(dpcg_system *h, const double *&b, hipStream_t s) {
+    if (!h->perm) return DPCG_OK;          // (b arrives in the caller's numbering)
+    if (!h->pb) DPCG_TRY(dev_alloc(&h->pb, h->A.n));
+    launch_gather_f64(h->A.n, h->perm, b, h->pb, s);
+    b = h->pb;
+    return DPCG_OK;
+}
+
+int stage_vectors(dpcg_system *h, const double *b, const double *x0, int max_iter, bool need_f32, bool need_err, hipStream_t s,
+                  const double **b_used) {
     const int64_t n = h->A.n;
     DPCG_TRY(ensure_work(h, max_iter, need_f32, need_err));
     *extras()[h].prog_host = 0;
-    if (h->perm) {                         // b and x0 arrive in the caller's numbering
-        if (!h->pb) DPCG_TRY(dev_alloc(&h->pb, n));
-        launch_gather_f64(n, h->perm, b, h->pb, s);
-        b = h->pb;
-    }
-    if (rhs) b = rhs(b);
-    if (x0) {
-        if (h->perm) launch_gather_f64(n, h->perm, x0, h->x, s);
-        else DPCG_HIP(hipMemcpyAsync(h->x, x0, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s));
-        launch_spmv(h->A, h->planA, h->x, h->q, nullptr, nullptr, s);
-        launch_residual(n, b, h->q, h->r, h->vec_grid, s);                           // cg.py:60
-    } else {
-        DPCG_HIP(hipMemsetAsync(h->x, 0, (size_t)n * sizeof(double), s));            // cg.py:58
-        DPCG_HIP(hipMemcpyAsync(h->r, b, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s));
-    }
+    DPCG_TRY(gather_rhs(h, b, s));
+    if (!x0) DPCG_HIP(hipMemsetAsync(h->x, 0, (size_t)n * sizeof(double), s));       // cg.py:58
+    else if (h->perm) launch_gather_f64(n, h->perm, x0, h->x, s);                    // (x0 arrives in the caller's numbering too)
+    else DPCG_HIP(hipMemcpyAsync(h->x, x0, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s));
     *b_used = b;
     return DPCG_OK;
+}
+
+int stage_residual(dpcg_system *h, const double *b, bool have_x0, hipStream_t s) {
+    if (have_x0) {
+        launch_spmv(h->A, h->planA, h->x, h->q, nullptr, nullptr, s);
+        launch_residual(h->A.n, b, h->q, h->r, h->vec_grid, s);                      // cg.py:60
+    } else {
+        DPCG_HIP(hipMemcpyAsync(h->r, b, (size_t)h->A.n * sizeof(double), hipMemcpyDeviceToDevice, s));
+    }
+    return DPCG_OK;
+}
+
+int stage_call(dpcg_system *h, const double *b, const double *x0, int max_iter, bool need_f32, bool need_err, hipStream_t s,
+               const double **b_used, const std::function<const double *(const double *)> &rhs) {
+    DPCG_TRY(stage_vectors(h, b, x0, max_iter, need_f32, need_err, s, b_used));
+    if (rhs) *b_used = rhs(*b_used);
+    return stage_residual(h, *b_used, x0 != nullptr, s);
 }
 
 int wait_progress(volatile unsigned long long *prog, unsigned long long v, hipStream_t s, bool behind, const char *tag) {
@@ -254,27 +269,54 @@ int run_launch_ahead(dpcg_system *h, int max_iter, hipStream_t s, std::chrono::s
     }
 }
 
-int deliver_solve(dpcg_system *h, const SolveCall &c, std::chrono::steady_clock::time_point t0) {
-    const int64_t n = h->A.n;
-    hipStream_t s = c.s;
+// the scalars on the host (h->scal_host) and the seconds since t0 once the stream has drained           cg.py:88 (the loop only)
+static int read_scalars(dpcg_system *h, hipStream_t s, std::chrono::steady_clock::time_point t0, double *seconds) {
     DPCG_HIP(hipMemcpyAsync(h->scal_host, h->scal, sizeof(Scalars), hipMemcpyDeviceToHost, s));
     DPCG_HIP(hipStreamSynchronize(s));
-    const auto t1 = std::chrono::steady_clock::now();                            // cg.py:88 (the loop only)
-    DPCG_TRY(check_spin_errors(h, s));
-    const Scalars sc = *h->scal_host;
-    if (c.seconds) *c.seconds = std::chrono::duration<double>(t1 - t0).count();
+    *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return DPCG_OK;
+}
+
+int hand_over_x(dpcg_system *h, double *x, hipStream_t s) {
+    if (h->perm) launch_scatter_f64(h->A.n, h->perm, h->x, x, s);        // back to the caller's numbering
+    else DPCG_HIP(hipMemcpyAsync(x, h->x, (size_t)h->A.n * sizeof(double), hipMemcpyDeviceToDevice, s));
+    return DPCG_OK;
+}
+
+int deliver_results(dpcg_system *h, const SolveCall &c, const Scalars &sc, double seconds, bool x_in_place) {
+    if (c.seconds) *c.seconds = seconds;
     if (c.iters) *c.iters = sc.k;                                                // cg.py:90
     if (c.final_res) *c.final_res = sc.res;
-    if (c.res_history) DPCG_HIP(hipMemcpyAsync(c.res_history, h->hist, (size_t)(sc.k + 1) * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (c.res_history) DPCG_HIP(hipMemcpyAsync(c.res_history, h->hist, (size_t)(sc.k + 1) * sizeof(double), hipMemcpyDeviceToHost, c.s));
     // x is handed over in stream order: the copy is enqueued on the caller's stream, a second host sync is only
     // needed for the host-side history buffer
-    if (c.x) {
-        if (h->perm) launch_scatter_f64(n, h->perm, h->x, c.x, s);       // back to the caller's numbering
-        else DPCG_HIP(hipMemcpyAsync(c.x, h->x, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s));
-    }
-    if (c.res_history) DPCG_HIP(hipStreamSynchronize(s));
+    if (c.x && (h->perm || !x_in_place)) DPCG_TRY(hand_over_x(h, c.x, c.s));
+    if (c.res_history) DPCG_HIP(hipStreamSynchronize(c.s));
     DPCG_CHECK_LAUNCH();
     return sc.status;
+}
+
+int deliver_solve(dpcg_system *h, const SolveCall &c, std::chrono::steady_clock::time_point t0) {
+    double seconds = 0.0;
+    DPCG_TRY(read_scalars(h, c.s, t0, &seconds));
+    DPCG_TRY(check_spin_errors(h, c.s));
+    return deliver_results(h, c, *h->scal_host, seconds, false);
+}
+
+int finish_one_launch(dpcg_system *h, const SolveCall &c, std::chrono::steady_clock::time_point t0, const char *never_resident,
+                      const std::function<int(const Scalars &)> &ran) {
+    double seconds = 0.0;
+    DPCG_TRY(read_scalars(h, c.s, t0, &seconds));
+    DPCG_CHECK_LAUNCH();
+    const Scalars sc = *h->scal_host;
+    if (never_resident && sc.status < 0) {
+        co_residency().timed_out();
+        set_error(never_resident);
+        return sc.status;
+    }
+    if (never_resident) co_residency().launched_fine();
+    if (ran) DPCG_TRY(ran(sc));
+    return deliver_results(h, c, sc, seconds, true);
 }
 
 namespace {
@@ -336,10 +378,17 @@ struct Solve {
 
     // Enqueue the start of the solve (cg.py:58-67); the timer starts after the initial residual /
     // preconditioner work has drained, as the reference's does (cg.py:69).
-    int start(const double *b, const double *x0, double rtol_sq, double atol_sq) {
+    int start(dpcg_system *handle, const SolveCall &c) {
+        h = handle;
+        s = c.s;
+        max_iter = c.max_iter;
+        flags = c.flags;
+        chunk = default_chunk();
+        x_true = c.x_true;
         const int64_t n = h->A.n;
         const bool f32 = (flags & DPCG_SPMV_F32) != 0;
-        DPCG_TRY(stage_call(h, b, x0, max_iter, f32, x_true != nullptr, s, &b));
+        const double *b = nullptr;
+        DPCG_TRY(stage_call(h, c.b, c.x0, max_iter, f32, x_true != nullptr, s, &b));
         if (h->perm && x_true) {           // x_true arrives in the caller's numbering too
             if (!h->pxt) DPCG_TRY(dev_alloc(&h->pxt, n));
             launch_gather_f64(n, h->perm, x_true, h->pxt, s);
@@ -382,7 +431,7 @@ struct Solve {
         if (h->precond != DPCG_PRECOND_NONE) DPCG_TRY(apply_precond(h, h->r, h->z, s));   // cg.py:61
         launch_init_state(n, h->scal, b, h->r, z, h->p, f32 ? h->p32 : nullptr, h->part_bb, h->part_rz, h->part_rr,
                           (flags & DPCG_INIT_CHECK_R) ? 1 : 0, h->vec_grid, s);
-        launch_finalize_init(h->scal, h->part_bb, h->part_rz, h->part_rr, h->vec_grid, rtol_sq, atol_sq, h->hist,
+        launch_finalize_init(h->scal, h->part_bb, h->part_rz, h->part_rr, h->vec_grid, c.rtol_sq, c.atol_sq, h->hist,
                              h->hist_cap, extras()[h].prog_dev, s, kMaxSpmvGrid);
         if (fused) {
             DPCG_HIP(hipMemsetAsync(h->p2, 0, (size_t)n * sizeof(double), s));       // "p_{-1}": multiplied by beta_0 = 0
@@ -418,7 +467,8 @@ struct Solve {
         }
     }
 
-    int finish(double *x, int *iters, double *final_res, double *seconds, double *res_history, double *err_history) {
+    // c: the call start() took (its x_true already stands in the member, in the handle's numbering)
+    int finish(const SolveCall &c) {
         const int64_t n = h->A.n;
         if (fused)
             launch_final_fused(n, h->scal, h->part_rr, h->vec_grid, h->hist, h->hist_cap, h->x, h->p, h->p2, h->vec_grid,
@@ -427,9 +477,9 @@ struct Solve {
             launch_final_deferred(n, h->scal, h->x, h->p, h->p2, h->vec_grid, s);
         else
             launch_final_check(h->scal, s);
-        const int st = deliver_solve(h, {nullptr, nullptr, x, 0.0, 0.0, max_iter, flags, s, iters, final_res, seconds, res_history}, t0);
-        if (st >= 0 && err_history && x_true) {      // (the count of entries is known only now)
-            DPCG_HIP(hipMemcpyAsync(err_history, h->err_hist, (size_t)(h->scal_host->k + 1) * sizeof(double), hipMemcpyDeviceToHost, s));
+        const int st = deliver_solve(h, c, t0);
+        if (st >= 0 && c.err_history && x_true) {      // (the count of entries is known only now)
+            DPCG_HIP(hipMemcpyAsync(c.err_history, h->err_hist, (size_t)(h->scal_host->k + 1) * sizeof(double), hipMemcpyDeviceToHost, s));
             DPCG_HIP(hipStreamSynchronize(s));
         }
         return st;
@@ -483,14 +533,13 @@ static int ensure_small(dpcg_system *h, hipStream_t s) {
     return DPCG_OK;
 }
 
-static SmallDesc make_small_desc(dpcg_system *h, const double *b, const double *x0, double *x, double rtol_sq,
-                                 double atol_sq, int max_iter, int flags) {
+static SmallDesc make_small_desc(dpcg_system *h, const SolveCall &c) {
     SmallDesc d;
     memset(&d, 0, sizeof(d));
     d.n = (int)h->A.n;
     d.precond = h->precond;
-    d.max_iter = max_iter;
-    d.init_check_r = (flags & DPCG_INIT_CHECK_R) ? 1 : 0;
+    d.max_iter = c.max_iter;
+    d.init_check_r = (c.flags & DPCG_INIT_CHECK_R) ? 1 : 0;
     d.hist_cap = h->hist_cap;
     d.lds_vectors = h->precond == DPCG_PRECOND_CSR ? 2 : (h->precond == DPCG_PRECOND_LLT_MULTIPLY ? 3 : 1);
     d.variant = small_variant((int)h->A.n, h->ell_a.W, h->precond);
@@ -499,8 +548,8 @@ static SmallDesc make_small_desc(dpcg_system *h, const double *b, const double *
     d.ell_a = h->ell_a; d.ell_m = h->ell_m; d.ell_t = h->ell_t;
     if (h->precond == DPCG_PRECOND_CSR) d.m_rp = h->M.rowptr;
     if (h->precond == DPCG_PRECOND_LLT_MULTIPLY) { d.m_rp = h->L.rowptr; d.t_rp = h->Lt.rowptr; }
-    d.b = b; d.x0 = x0; d.x = x ? x : h->x; d.hist = h->hist;
-    d.rtol_sq = rtol_sq; d.atol_sq = atol_sq;
+    d.b = c.b; d.x0 = c.x0; d.x = c.x ? c.x : h->x; d.hist = h->hist;
+    d.rtol_sq = c.rtol_sq; d.atol_sq = c.atol_sq;
     d.out = h->scal;
     return d;
 }
@@ -508,30 +557,17 @@ static SmallDesc make_small_desc(dpcg_system *h, const double *b, const double *
 static int small_variant_bit(const SmallDesc &d) { return d.variant == 4 * 16 + 7 ? 2 : (d.variant == 6 * 16 + 5 ? 4 : 1); }
 static int small_lds_bytes(const SmallDesc &d) { return (int)(((size_t)d.lds_vectors * d.n + 64) * sizeof(double)); }
 
-static int solve_small_one(dpcg_system *h, const double *b, const double *x0, double *x, double rtol_sq, double atol_sq,
-                           int max_iter, int flags, hipStream_t s, int *iters, double *final_res, double *seconds,
-                           double *res_history) {
-    DPCG_TRY(ensure_work(h, max_iter, false, false));
+static int solve_small_one(dpcg_system *h, SolveCall c) {
+    hipStream_t s = c.s;
+    DPCG_TRY(ensure_work(h, c.max_iter, false, false));
     DPCG_TRY(ensure_small(h, s));
     if (!h->small_desc) DPCG_TRY(dev_alloc(&h->small_desc, 1));
-    const SmallDesc d = make_small_desc(h, b, x0, x, rtol_sq, atol_sq, max_iter, flags);
+    const SmallDesc d = make_small_desc(h, c);
     DPCG_HIP(hipMemcpyAsync(h->small_desc, &d, sizeof(d), hipMemcpyHostToDevice, s));
     DPCG_HIP(hipStreamSynchronize(s));
     const auto t0 = std::chrono::steady_clock::now();                                // cg.py:69 (the launch is the loop)
     DPCG_TRY(launch_pcg_small(h->small_desc, 1, small_lds_bytes(d), 1 << h->precond, small_variant_bit(d), s));
-    DPCG_HIP(hipMemcpyAsync(h->scal_host, h->scal, sizeof(Scalars), hipMemcpyDeviceToHost, s));
-    DPCG_HIP(hipStreamSynchronize(s));
-    const auto t1 = std::chrono::steady_clock::now();                                // cg.py:88
-    DPCG_CHECK_LAUNCH();
-    const Scalars sc = *h->scal_host;
-    if (seconds) *seconds = std::chrono::duration<double>(t1 - t0).count();
-    if (iters) *iters = sc.k;
-    if (final_res) *final_res = sc.res;
-    if (res_history) {
-        DPCG_HIP(hipMemcpyAsync(res_history, h->hist, (size_t)(sc.k + 1) * sizeof(double), hipMemcpyDeviceToHost, s));
-        DPCG_HIP(hipStreamSynchronize(s));
-    }
-    return sc.status;
+    return finish_one_launch(h, c, t0, nullptr);        // (x straight from the kernel: a reordered handle never takes this form)
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -660,23 +696,22 @@ static int ensure_team(dpcg_system *h, hipStream_t s) {
     return DPCG_OK;
 }
 
-static TeamDesc make_team_desc(dpcg_system *h, const double *b, const double *x0, double *x, double rtol_sq, double atol_sq,
-                               int max_iter, int flags) {
+static TeamDesc make_team_desc(dpcg_system *h, const SolveCall &c) {
     TeamDesc d;
     memset(&d, 0, sizeof(d));
     d.n = (int)h->A.n;
     d.precond = h->precond;
-    d.max_iter = max_iter;
-    d.init_check_r = (flags & DPCG_INIT_CHECK_R) ? 1 : 0;
+    d.max_iter = c.max_iter;
+    d.init_check_r = (c.flags & DPCG_INIT_CHECK_R) ? 1 : 0;
     d.hist_cap = h->hist_cap;
     d.W = h->ell_a.W;
     d.rp = h->A.rowptr;
     d.dinv = h->dinv;
     d.ell_col = h->ell_a.col;
     d.ell_val = h->ell_a.val;
-    d.b = b; d.x0 = x0; d.x = x ? x : h->x; d.hist = h->hist;
+    d.b = c.b; d.x0 = c.x0; d.x = c.x ? c.x : h->x; d.hist = h->hist;
     d.z = h->z; d.p0 = h->p; d.p1 = h->p2;
-    d.rtol_sq = rtol_sq; d.atol_sq = atol_sq;
+    d.rtol_sq = c.rtol_sq; d.atol_sq = c.atol_sq;
     d.out = h->scal;
     d.bar = h->team_sync;
     d.part = h->team_part;
@@ -692,17 +727,16 @@ static int team_slabs_per_wg(int64_t n) {
     return (int)((slabs + 31) / 32);
 }
 
-static int solve_team_one(dpcg_system *h, const double *b, const double *x0, double *x, double rtol_sq, double atol_sq,
-                          int max_iter, int flags, hipStream_t s, int *iters, double *final_res, double *seconds,
-                          double *res_history) {
-    DPCG_TRY(ensure_work(h, max_iter, false, false));
+static int solve_team_one(dpcg_system *h, SolveCall c) {
+    hipStream_t s = c.s;
+    DPCG_TRY(ensure_work(h, c.max_iter, false, false));
     DPCG_TRY(ensure_team(h, s));
     if (!h->team_desc) {
         TeamDesc *td = nullptr;
         DPCG_TRY(dev_alloc(&td, 1));
         h->team_desc = td;
     }
-    const TeamDesc d = make_team_desc(h, b, x0, x, rtol_sq, atol_sq, max_iter, flags);
+    const TeamDesc d = make_team_desc(h, c);
     DPCG_HIP(hipMemcpyAsync(h->team_desc, &d, sizeof(d), hipMemcpyHostToDevice, s));
     DPCG_HIP(hipMemsetAsync(h->team_sync, 0, 2 * sizeof(unsigned int), s));
     launch_fill_pending(h->team_part, 4 * 2 * 32, s);                                // every reduction slot: "not written yet"
@@ -712,33 +746,16 @@ static int solve_team_one(dpcg_system *h, const double *b, const double *x0, dou
     std::lock_guard<std::mutex> one_team_launch(team_launch_mutex());
     const auto t0 = std::chrono::steady_clock::now();                                // cg.py:69 (the launch is the loop)
     DPCG_TRY(launch_pcg_team(static_cast<const TeamDesc *>(h->team_desc), 1, team_slabs_per_wg(h->A.n), h->ell_a.W, s, d.dbg != nullptr));
-    DPCG_HIP(hipMemcpyAsync(h->scal_host, h->scal, sizeof(Scalars), hipMemcpyDeviceToHost, s));
-    DPCG_HIP(hipStreamSynchronize(s));
-    const auto t1 = std::chrono::steady_clock::now();                                // cg.py:88
-    DPCG_CHECK_LAUNCH();
-    const Scalars sc = *h->scal_host;
-    if (sc.status < 0) {
-        co_residency().timed_out();
-        set_error("team solve: a workgroup waited (20 ms) for a team member that never arrived");
-        return sc.status;
-    }
-    co_residency().launched_fine();
-    if (seconds) *seconds = std::chrono::duration<double>(t1 - t0).count();
-    if (iters) *iters = sc.k;
-    if (final_res) *final_res = sc.res;
-    if (d.dbg && sc.k > 0) {
+    return finish_one_launch(h, c, t0, "team solve: a workgroup waited (20 ms) for a team member that never arrived", [&](const Scalars &sc) -> int {
+        if (!d.dbg || sc.k <= 0) return DPCG_OK;
         unsigned long long w[8];
         DPCG_HIP(hipMemcpy(w, d.dbg, sizeof(w), hipMemcpyDeviceToHost));
         const double us = 0.01 / sc.k;       // 100 MHz ticks -> us per update
         fprintf(stderr, "[dpcg team] %d updates, us per update on rank 0: SpMV %.2f, sum <p,Ap> %.2f (block sums %.2f, hand-off %.2f), vector update + publish %.2f, "
                 "sum <r,z> %.2f (drain %.2f, block sums %.2f, hand-off %.2f), total %.2f\n", sc.k, w[0] * us, w[1] * us, w[5] * us, (w[1] - w[5]) * us, w[2] * us,
                 w[3] * us, w[6] * us, w[7] * us, (w[3] - w[6] - w[7]) * us, w[4] * us);
-    }
-    if (res_history) {
-        DPCG_HIP(hipMemcpyAsync(res_history, h->hist, (size_t)(sc.k + 1) * sizeof(double), hipMemcpyDeviceToHost, s));
-        DPCG_HIP(hipStreamSynchronize(s));
-    }
-    return sc.status;
+        return DPCG_OK;
+    });
 }
 
 extern "C" int dpcg_debug_occupy(int workgroups, double milliseconds, dpcg_stream_t stream) {
@@ -770,75 +787,55 @@ extern "C" int dpcg_solve(dpcg_handle_t h, const double *b, const double *x0, do
                           double *final_res, double *seconds, double *res_history, const double *x_true,
                           double *err_history) {
     DPCG_TRY(check_solve_args(h, b, max_iter, flags, x_true, err_history));
-    if (h->ns) {                             // a singular system with its null space attached: its own driver, whatever the size (dpcg_nullspace.hip)
-        if (const char *why = nullspace_refusal(h, flags, x_true)) return invalid(why);
-        h->last_recurrence = 0;
-        h->chip_shared_known = false;
-        return solve_nullspace_one(h, {b, x0, x, rtol_sq, atol_sq, max_iter, flags, (hipStream_t)stream, iters, final_res, seconds, res_history});
-    }
-    if (h->df) {                             // deflation vectors attached: the deflated driver, whatever the size (dpcg_deflation.hip)
-        if (const char *why = deflation_refusal(h, flags, x_true)) return invalid(why);
-        h->last_recurrence = 0;
-        h->chip_shared_known = false;
-        return solve_deflated_one(h, {b, x0, x, rtol_sq, atol_sq, max_iter, flags, (hipStream_t)stream, iters, final_res, seconds, res_history});
-    }
+    // refusals first: nothing of the handle has been touched when one returns
+    const char *why = h->ns ? nullspace_refusal(h, flags, x_true)
+                      : h->df ? deflation_refusal(h, flags, x_true)
+                      : (flags & DPCG_SINGLE_REDUCTION) ? chip_sr_refusal(h, flags, x_true) : nullptr;
+    if (why) return invalid(why);
+    h->last_recurrence = 0;                  // (1: set by the single-reduction chip solve, dpcg_get_last_recurrence)
+    h->chip_shared_known = false;            // (set by the resident standard chip solve, dpcg_get_chip_info)
+    SolveCall call{b, x0, x, rtol_sq, atol_sq, max_iter, flags, (hipStream_t)stream, iters, final_res, seconds, res_history, x_true, err_history};
+    // a singular system with its null space attached, deflation vectors attached: their own drivers, whatever the size
+    if (h->ns) return solve_nullspace_one(h, call);
+    if (h->df) return solve_deflated_one(h, call);
     const bool one_launch_open = co_residency().open();      // (false during the cool-down after repeated co-residency timeouts)
     if (flags & DPCG_SINGLE_REDUCTION) {
-        if (const char *why = chip_sr_refusal(h, flags, x_true)) return invalid(why);     // (nothing of the handle has been touched)
-    }
-    h->last_recurrence = 0;
-    h->chip_shared_known = false;            // (set by the resident standard chip solve, dpcg_get_chip_info)
-    if (flags & DPCG_SINGLE_REDUCTION) {
         if (one_launch_open) {
-            const int st = solve_chip_sr_one(h, {b, x0, x, rtol_sq, atol_sq, max_iter, flags, (hipStream_t)stream, iters, final_res,
-                                             seconds, res_history});
+            const int st = solve_chip_sr_one(h, call);
             if (st != DPCG_ERR_STATE) return st;
         }
         // the workgroups never became co-resident: the launches, with the standard recurrence (dpcg_get_last_recurrence says so)
         // (DPCG_TEAM would take the standard whole-chip kernel "whatever the other flags say" and wait out a second 20 ms: cleared too)
-        flags = (flags & ~(DPCG_SINGLE_REDUCTION | DPCG_TEAM)) | DPCG_NO_SMALL;
+        call.flags = flags = (flags & ~(DPCG_SINGLE_REDUCTION | DPCG_TEAM)) | DPCG_NO_SMALL;
     }
     const bool team_first = one_launch_open && team_eligible(h, flags, x_true) && ((flags & DPCG_TEAM) || single_team_default(h, flags));
-    if (small_eligible(h, flags, x_true) && !team_first)
-        return solve_small_one(h, b, x0, x, rtol_sq, atol_sq, max_iter, flags, (hipStream_t)stream, iters, final_res,
-                               seconds, res_history);
+    if (small_eligible(h, flags, x_true) && !team_first) return solve_small_one(h, call);
     // a single team by default (tools/team_crossover_probe.py)
     if (team_first) {
-        const int st = solve_team_one(h, b, x0, x, rtol_sq, atol_sq, max_iter, flags, (hipStream_t)stream, iters, final_res,
-                                      seconds, res_history);
+        const int st = solve_team_one(h, call);
         if (st != DPCG_ERR_STATE) return st;
         // the team never became co-resident (a plain launch assumes it): the multi-launch path below needs no such thing
     }
-    // cache-sized systems on the whole chip
-    const SolveCall call{b, x0, x, rtol_sq, atol_sq, max_iter, flags, (hipStream_t)stream, iters, final_res, seconds, res_history};
-    if (one_launch_open && chip_eligible(h, flags, x_true) && ((flags & DPCG_TEAM) || chip_default(h, flags))) {
-        const int st = solve_chip_one(h, call);
-        if (st != DPCG_ERR_STATE) return st;
-        // the workgroups never became co-resident, or the kernel was refused up front: the multi-launch path needs no such thing
-    }
-    if (one_launch_open && chip_trsv_shape(h, flags, x_true) && ((flags & DPCG_TEAM) || chip_default(h, flags))) {
-        const int st = solve_chip_trsv_one(h, call);
-        if (st != DPCG_ERR_STATE) return st;
-        // (the factor does not fit the form -- too many levels, rows too long -- or the workgroups never became co-resident: the launches)
-    }
-    if (one_launch_open && chip_llt_eligible(h, flags, x_true) && ((flags & DPCG_TEAM) || chip_default(h, flags))) {
-        const int st = solve_chip_llt_one(h, call);
+    // cache-sized systems on the whole chip, in this order: M = I / Jacobi, two triangular solves, L L^T multiplied.  DPCG_ERR_STATE: the
+    // kernel was refused up front, the factor does not fit the form (too many levels, rows too long) or the workgroups never became
+    // co-resident -- the next form, in the end the multi-launch path, which needs no such thing
+    static const struct {
+        bool (*eligible)(const dpcg_system *, int, const double *);
+        int (*solve)(dpcg_system *, SolveCall);
+    } chip_forms[] = {{chip_eligible, solve_chip_one}, {chip_trsv_shape, solve_chip_trsv_one}, {chip_llt_eligible, solve_chip_llt_one}};
+    for (const auto &form : chip_forms) {
+        if (!(one_launch_open && form.eligible(h, flags, x_true) && ((flags & DPCG_TEAM) || chip_default(h, flags)))) continue;
+        const int st = form.solve(h, call);
         if (st != DPCG_ERR_STATE) return st;
     }
     Solve sv;
-    sv.h = h;
-    sv.s = (hipStream_t)stream;
-    sv.max_iter = max_iter;
-    sv.flags = flags;
-    sv.chunk = default_chunk();
-    sv.x_true = x_true;
-    DPCG_TRY(sv.start(b, x0, rtol_sq, atol_sq));
+    DPCG_TRY(sv.start(h, call));
     for (;;) {
         const int r = sv.step(true);
         if (r < 0) return r;
         if (r == 1) break;
     }
-    return sv.finish(x, iters, final_res, seconds, res_history, err_history);
+    return sv.finish(call);
 }
 
 extern "C" int dpcg_solve_batch(int count, dpcg_handle_t *handles, const double *const *b, const double *const *x0,
@@ -860,24 +857,31 @@ extern "C" int dpcg_solve_batch(int count, dpcg_handle_t *handles, const double 
     // every form below runs the standard recurrence; the single-reduction members set their own word (dpcg_get_last_recurrence)
     for (int i = 0; i < count; ++i) handles[i]->last_recurrence = 0;
     for (int i = 0; i < count; ++i) handles[i]->chip_shared_known = false;
+    // member i as one call on s, its scalar results into o; and the writer of a member's results, which every form below ends in
+    struct Out { int it = 0; double fr = 0.0, sec = 0.0; };
+    auto member = [&](int i, hipStream_t s, Out &o) {
+        return SolveCall{b[i], x0 ? x0[i] : nullptr, x ? x[i] : nullptr, rtol_sq, atol_sq, max_iter, flags, s, &o.it, &o.fr, &o.sec, nullptr};
+    };
+    int worst = DPCG_OK;
+    auto record = [&](int i, int it, double fr, double sec, int st) {
+        if (iters) iters[i] = it;
+        if (final_res) final_res[i] = fr;
+        if (seconds) seconds[i] = sec;
+        if (status) status[i] = st;
+        worst = std::max(worst, st);
+    };
     if (flags & DPCG_SINGLE_REDUCTION) {
         // the flag holds for every system as it does for a single solve: refused when one is not eligible, else one whole-chip launch
         // after the other (a member that cannot become co-resident goes through the launches with the standard recurrence)
-        int worst_sr = DPCG_OK;
         for (int i = 0; i < count; ++i) {
-            int it = 0;
-            double fr = 0.0, sec = 0.0;
-            const int st = dpcg_solve(handles[i], b[i], x0 ? x0[i] : nullptr, x ? x[i] : nullptr, rtol_sq, atol_sq, max_iter, flags, nullptr,
-                                      &it, &fr, &sec, nullptr, nullptr, nullptr);
+            Out o;
+            const SolveCall c = member(i, nullptr, o);
+            const int st = dpcg_solve(handles[i], c.b, c.x0, c.x, rtol_sq, atol_sq, max_iter, flags, nullptr, &o.it, &o.fr, &o.sec, nullptr, nullptr, nullptr);
             if (st < 0) return st;
-            if (iters) iters[i] = it;
-            if (final_res) final_res[i] = fr;
-            if (seconds) seconds[i] = sec;
-            if (status) status[i] = st;
-            worst_sr = std::max(worst_sr, st);
+            record(i, o.it, o.fr, o.sec, st);
         }
         DPCG_HIP(hipStreamSynchronize(nullptr));
-        return worst_sr;
+        return worst;
     }
     {   // a handle owns ONE set of work vectors: the same handle twice would share them across streams
         std::vector<dpcg_handle_t> sorted(handles, handles + count);
@@ -891,12 +895,12 @@ extern "C" int dpcg_solve_batch(int count, dpcg_handle_t *handles, const double 
         // one launch, one workgroup (one CU) per system
         std::vector<SmallDesc> descs((size_t)count);
         int lds = 0, kinds = 0, variants = 0;
+        Out unused;
         for (int i = 0; i < count; ++i) {
             kinds |= 1 << handles[i]->precond;
             DPCG_TRY(ensure_work(handles[i], max_iter, false, false));
             DPCG_TRY(ensure_small(handles[i], nullptr));
-            descs[i] = make_small_desc(handles[i], b[i], x0 ? x0[i] : nullptr, x ? x[i] : nullptr, rtol_sq, atol_sq,
-                                       max_iter, flags);
+            descs[i] = make_small_desc(handles[i], member(i, nullptr, unused));
             lds = std::max(lds, small_lds_bytes(descs[i]));
             variants |= small_variant_bit(descs[i]);
         }
@@ -930,40 +934,27 @@ extern "C" int dpcg_solve_batch(int count, dpcg_handle_t *handles, const double 
         const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         DPCG_HIP(e);
         if (st < 0) return st;
-        int worst_small = DPCG_OK;
-        for (int i = 0; i < count; ++i) {
-            if (iters) iters[i] = out[i].k;
-            if (final_res) final_res[i] = out[i].res;
-            if (seconds) seconds[i] = sec;   // the batch ran as one launch
-            if (status) status[i] = out[i].status;
-            worst_small = std::max(worst_small, out[i].status);
-        }
-        return worst_small;
+        for (int i = 0; i < count; ++i) record(i, out[i].k, out[i].res, sec, out[i].status);      // (sec: the batch ran as one launch)
+        return worst;
     }
     bool all_chip = true;
     for (int i = 0; i < count; ++i) all_chip = all_chip && chip_eligible(handles[i], flags, nullptr);
     if (all_chip && co_residency().open() && ((flags & DPCG_TEAM) || chip_default(handles[0], flags))) {
         // cache-sized systems: the whole chip serves one system at a time (7-13 us per update against 30 for the launches -- nothing to
         // interleave), and a batch member's result is bit for bit that of its single solve
-        int worst_chip = DPCG_OK;
         bool refused = false;
         for (int i = 0; i < count && !refused; ++i) {
-            int it = 0;
-            double fr = 0.0, sec = 0.0;
-            const int st = solve_chip_one(handles[i], {b[i], x0 ? x0[i] : nullptr, x ? x[i] : nullptr, rtol_sq, atol_sq, max_iter, flags,
-                                          nullptr, &it, &fr, &sec, nullptr});
+            Out o;
+            const int st = solve_chip_one(handles[i], member(i, nullptr, o));
             if (st == DPCG_ERR_STATE) { refused = true; break; }     // never co-resident: the whole batch takes the streams below
             if (st < 0) return st;
-            if (iters) iters[i] = it;
-            if (final_res) final_res[i] = fr;
-            if (seconds) seconds[i] = sec;
-            if (status) status[i] = st;
-            worst_chip = std::max(worst_chip, st);
+            record(i, o.it, o.fr, o.sec, st);
         }
         if (!refused) {
             DPCG_HIP(hipStreamSynchronize(nullptr));
-            return worst_chip;
+            return worst;
         }
+        worst = DPCG_OK;                   // (every member is solved again)
     }
     bool all_team = true;
     for (int i = 0; i < count; ++i) all_team = all_team && team_eligible(handles[i], flags, nullptr);
@@ -975,7 +966,7 @@ extern "C" int dpcg_solve_batch(int count, dpcg_handle_t *handles, const double 
         };
         static thread_local TeamScratch scratch;
         if (!scratch.descs) DPCG_TRY(dev_alloc(&scratch.descs, 8));
-        int worst_team = DPCG_OK;
+        Out unused;
         bool team_timed_out = false;       // a team waited in vain for its members (the chip shared with another process, a long kernel
                                            // holding CUs: the launch is a plain one, co-residency is assumed, not guaranteed)
         for (int g0 = 0; g0 < count && !team_timed_out; g0 += 8) {
@@ -986,8 +977,7 @@ extern "C" int dpcg_solve_batch(int count, dpcg_handle_t *handles, const double 
                 dpcg_system *hi = handles[g0 + i];
                 DPCG_TRY(ensure_work(hi, max_iter, false, false));
                 DPCG_TRY(ensure_team(hi, nullptr));
-                descs[i] = make_team_desc(hi, b[g0 + i], x0 ? x0[g0 + i] : nullptr, x ? x[g0 + i] : nullptr, rtol_sq, atol_sq,
-                                          max_iter, flags);
+                descs[i] = make_team_desc(hi, member(g0 + i, nullptr, unused));
                 DPCG_HIP(hipMemsetAsync(hi->team_sync, 0, 2 * sizeof(unsigned int), nullptr));
                 launch_fill_pending(hi->team_part, 4 * 2 * 32, nullptr);
                 slabs = std::max(slabs, team_slabs_per_wg(hi->A.n));
@@ -1009,28 +999,22 @@ extern "C" int dpcg_solve_batch(int count, dpcg_handle_t *handles, const double 
                     co_residency().timed_out();
                     break;
                 }
-                if (iters) iters[g0 + i] = sc.k;
-                if (final_res) final_res[g0 + i] = sc.res;
-                if (seconds) seconds[g0 + i] = sec;      // the group ran as one launch
-                if (status) status[g0 + i] = sc.status;
-                worst_team = std::max(worst_team, sc.status);
+                record(g0 + i, sc.k, sc.res, sec, sc.status);      // (sec: the group ran as one launch)
             }
         }
-        if (!team_timed_out) return worst_team;
+        if (!team_timed_out) return worst;
+        worst = DPCG_OK;
         // not an error: the whole batch runs again through the multi-launch path below, which needs no co-residency
-        static bool warned = false;
-        if (!warned) {
-            warned = true;
+        static std::atomic<bool> warned{false};
+        if (!warned.exchange(true))
             fprintf(stderr, "[dpcg] team solve: a workgroup waited 20 ms for a team member that never became resident; "
                             "the batch is solved through the multi-launch path instead\n");
-        }
     }
-    std::vector<hipStream_t> streams((size_t)n_streams, nullptr);
-    for (auto &st : streams) DPCG_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    StreamSet streams;                       // (synchronised and destroyed on every way out)
+    DPCG_TRY(streams.create(n_streams));
     std::vector<Solve> sv((size_t)count);
-    std::vector<int> state((size_t)count, 0);  // 0 = waiting, 1 = running, 2 = finished
     std::vector<int> slot_owner((size_t)n_streams, -1);
-    int worst = DPCG_OK, next = 0, done = 0, err = 0;
+    int next = 0, done = 0, err = 0;
     while (done < count && !err) {
         bool progressed = false;
         for (int sl = 0; sl < n_streams && !err; ++sl) {
@@ -1039,38 +1023,25 @@ extern "C" int dpcg_solve_batch(int count, dpcg_handle_t *handles, const double 
                 if (next >= count) continue;
                 i = next++;
                 slot_owner[sl] = i;
-                Solve &v = sv[i];
-                v.h = handles[i];
-                v.s = streams[sl];
-                v.max_iter = max_iter;
-                v.flags = flags;
-                v.chunk = default_chunk();
-                int st = v.start(b[i], x0 ? x0[i] : nullptr, rtol_sq, atol_sq);
+                Out unused;
+                const int st = sv[i].start(handles[i], member(i, streams.s[(size_t)sl], unused));
                 if (st < 0) { err = st; break; }
-                state[i] = 1;
                 progressed = true;
             }
             Solve &v = sv[i];
             const int r = v.step(false);
             if (r < 0) { err = r; break; }
             if (r == 1) {
-                const int st = v.finish(x ? x[i] : nullptr, iters ? &iters[i] : nullptr,
-                                        final_res ? &final_res[i] : nullptr, seconds ? &seconds[i] : nullptr, nullptr,
-                                        nullptr);
+                Out o;
+                const int st = v.finish(member(i, v.s, o));
                 if (st < 0) { err = st; break; }
-                if (status) status[i] = st;
-                worst = std::max(worst, st);
-                state[i] = 2;
+                record(i, o.it, o.fr, o.sec, st);
                 slot_owner[sl] = -1;
                 ++done;
                 progressed = true;
             }
         }
         if (!progressed) std::this_thread::yield();
-    }
-    for (auto &st : streams) {
-        (void)hipStreamSynchronize(st);
-        (void)hipStreamDestroy(st);
     }
     return err ? err : worst;
 }

@@ -264,14 +264,10 @@ static int chip_prepare(dpcg_system *h, SolveCall &c, const ChipForm &form) {
     if (form.part2 && !h->chip_part2) DPCG_TRY(dev_alloc(&h->chip_part2, ChipPart::slots()));
     if (!h->chip_zp) DPCG_TRY(dev_alloc(&h->chip_zp, chip_zp_doubles(n)));
     if (form.rt && !h->chip_rt) DPCG_TRY(dev_alloc(&h->chip_rt, 2 * chip_zp_doubles(n)));      // two vectors of 2 x (n + pad) granules
-    if (h->perm) {                         // b and x0 arrive in the caller's numbering
-        if (!h->pb) DPCG_TRY(dev_alloc(&h->pb, n));
-        launch_gather_f64(n, h->perm, c.b, h->pb, c.s);
-        c.b = h->pb;
-        if (c.x0) {
-            launch_gather_f64(n, h->perm, c.x0, h->t, c.s);
-            c.x0 = h->t;
-        }
+    DPCG_TRY(gather_rhs(h, c.b, c.s));
+    if (h->perm && c.x0) {                 // (x0 arrives in the caller's numbering too; the kernel reads it, h->x is what it writes)
+        launch_gather_f64(n, h->perm, c.x0, h->t, c.s);
+        c.x0 = h->t;
     }
     return DPCG_OK;
 }
@@ -304,8 +300,8 @@ static void fill_jacobi(ChipDesc &d, const dpcg_system *h) {
     d.rp_nnz = (int)std::min<int64_t>(h->A.nnz, 0x1fffffff);
 }
 
-// The launch and what surrounds it.  launch(check_only) launches the form's kernel; ran(sc, events), if any, runs after a launch whose
-// workgroups were all resident.
+// The launch and what precedes it; the end is finish_one_launch, which the one-workgroup and the team form share.  launch(check_only)
+// launches the form's kernel; ran(sc, events), if any, runs after a launch whose workgroups were all resident.
 static int chip_run(dpcg_system *h, const SolveCall &c, const ChipForm &form, const std::function<int(bool)> &launch,
                     const std::function<int(const Scalars &, bool)> &ran = nullptr) {
     hipStream_t s = c.s;
@@ -331,30 +327,14 @@ static int chip_run(dpcg_system *h, const SolveCall &c, const ChipForm &form, co
     if (events) DPCG_HIP(hipEventRecord(ev[0], s));
     DPCG_TRY(launch(false));
     if (events) DPCG_HIP(hipEventRecord(ev[1], s));
-    DPCG_HIP(hipMemcpyAsync(h->scal_host, h->scal, sizeof(Scalars), hipMemcpyDeviceToHost, s));
-    DPCG_HIP(hipStreamSynchronize(s));
-    const auto t1 = std::chrono::steady_clock::now();                                // cg.py:88
-    if (events) {
-        float ms = 0.0f;
-        DPCG_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
-        h->chip_trace_x[5] = (double)ms;
-    }
-    DPCG_CHECK_LAUNCH();
-    const Scalars sc = *h->scal_host;
-    if (sc.status < 0) {
-        co_residency().timed_out();
-        set_error(form.never_resident);
-        return sc.status;
-    }
-    co_residency().launched_fine();
-    if (ran) DPCG_TRY(ran(sc, events));
-    if (c.seconds) *c.seconds = std::chrono::duration<double>(t1 - t0).count();
-    if (c.iters) *c.iters = sc.k;
-    if (c.final_res) *c.final_res = sc.res;
-    if (c.res_history) DPCG_HIP(hipMemcpyAsync(c.res_history, h->hist, (size_t)(sc.k + 1) * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (c.x && h->perm) launch_scatter_f64(h->A.n, h->perm, h->x, c.x, s);           // back to the caller's numbering
-    if (c.res_history) DPCG_HIP(hipStreamSynchronize(s));
-    return sc.status;
+    return finish_one_launch(h, c, t0, form.never_resident, [&](const Scalars &sc) -> int {
+        if (events) {
+            float ms = 0.0f;
+            DPCG_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
+            h->chip_trace_x[5] = (double)ms;
+        }
+        return ran ? ran(sc, events) : DPCG_OK;
+    });
 }
 
 // DPCG_CHIP_TRACE=1, the standard form: ticks per phase and workgroup into what dpcg_get_chip_info reports
@@ -402,7 +382,6 @@ int solve_chip_one(dpcg_system *h, SolveCall c) {
     d.dbg = trace ? ChipPart{h->chip_part}.dbg() : nullptr;
     d.shared = chip_shared_on(h) ? 1 : 0;
     d.shared_out = d.stream_cap > 0 ? nullptr : ChipPart{h->chip_part}.shared();
-    h->chip_shared_known = false;
     return chip_run(h, c, form, [&](bool check_only) { return launch_pcg_chip(d, h->planA.max_row_len, c.s, check_only); },
                     [&](const Scalars &sc, bool) {
                         h->chip_shared_known = d.shared_out != nullptr;

@@ -31,17 +31,21 @@ def sha(a):
     return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
 
 
+def chip_cases():
+    """(name, matrix, preconditioner of a matrix, recurrence, max_iter) per whole-chip family (tools/solve_forms_digest.py takes them too)"""
+    a3, a79, a40 = O.poisson3d(41), O.poisson2d(79), O.poisson2d(40)
+    return [("standard_jacobi", a3, lambda A: D.Jacobi(), "standard", 1024),
+            ("single_reduction_jacobi", a3, lambda A: D.Jacobi(), "single_reduction", 1024),
+            ("standard_identity", a3, lambda A: D.Identity(), "standard", 1024),
+            ("llt_multiply", a79, lambda A: D.LLtMultiply(CO.ic0(A)), "standard", 40),
+            ("triangular_solves_resident", a40, lambda A: D.IC0("solve", ordering="multicolor"), "standard", 1024)]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=0)
     args = ap.parse_args()
-    a3, a79, a40 = O.poisson3d(41), O.poisson2d(79), O.poisson2d(40)
-    cases = [("standard_jacobi", a3, lambda A: D.Jacobi(), "standard", 1024),
-             ("single_reduction_jacobi", a3, lambda A: D.Jacobi(), "single_reduction", 1024),
-             ("standard_identity", a3, lambda A: D.Identity(), "standard", 1024),
-             ("llt_multiply", a79, lambda A: D.LLtMultiply(CO.ic0(A)), "standard", 40),
-             ("triangular_solves_resident", a40, lambda A: D.IC0("solve", ordering="multicolor"), "standard", 1024)]
-    for name, A, precond, recurrence, max_iter in cases:
+    for name, A, precond, recurrence, max_iter in chip_cases():
         n = A.shape[0]
         b = torch.from_numpy(np.ascontiguousarray(O.rhs(n, 0))).cuda()
         x0 = torch.from_numpy(np.ascontiguousarray(np.cos(np.arange(n, dtype=np.float64)))).cuda()
