@@ -67,6 +67,7 @@ SIGNATURES = {
     "dpcg_get_precond_ordering": (_int, [_p, C.POINTER(_int), _p]),
     "dpcg_set_precond_ict": (_int, [_p, _int, _int, _dbl, _p]),
     "dpcg_set_precond_icholt": (_int, [_p, _int, _int, _dbl, _p]),
+    "dpcg_get_icholt_info": (_int, [_p, _p]),
     "dpcg_set_precond_ilut": (_int, [_p, _int, _int, _dbl, _p]),
     "dpcg_set_precond_fsai": (_int, [_p, _int, _p]),
     "dpcg_set_precond_fsai_pattern": (_int, [_p, _i64, _p, _p, _int, _p]),

@@ -354,6 +354,8 @@ void free_precond(dpcg_system *h, bool keep_parked) {
     free_amg(h->amg);
     if (!keep_parked) free_amg(h->amg_parked);
     if (keep_parked) fsai_detach(h->fsai); else free_fsai(h->fsai);
+    h->icholt_info[0] = h->icholt_info[1] = h->icholt_info[3] = 0;
+    h->icholt_info[2] = -1;
     h->precond = DPCG_PRECOND_NONE;
 }
 

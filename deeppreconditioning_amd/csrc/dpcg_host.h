@@ -70,7 +70,9 @@ inline void dev_free(T *&p) {
 
 void free_csr(CsrDev &c);
 // dpcg_icholt.hip: ILU++-style thresholded incomplete Cholesky of a symmetric CSR matrix into an owned lower-triangular CSR
-int icholt_factor(const CsrDev &A, int add_fill_in, double threshold, CsrDev &Lf, hipStream_t s);
+// info: {form (1 LDS pipeline, 2 workspace pipeline, 3 one-wave), waves of the pipeline that produced Lf (0: one-wave), the column at
+// which a pipeline attempt gave the factorisation to the one-wave kernel (-1: none did), the pool bound} -- dpcg_get_icholt_info
+int icholt_factor(const CsrDev &A, int add_fill_in, double threshold, CsrDev &Lf, hipStream_t s, int32_t info[4]);
 // dpcg_ilut.hip: Saad's dual-threshold ILUT of a CSR matrix into owned L (unit lower, diagonal last) and U (upper, diagonal first)
 int ilut_factor(const CsrDev &A, int add_fill_in, double threshold, CsrDev &Lf, CsrDev &Uf, hipStream_t s);
 // dpcg_fsai.hip: the factorised sparse approximate inverse of the handle's matrix (caller's numbering) into an owned lower-triangular

@@ -71,7 +71,7 @@ __global__ __launch_bounds__(64) void k_icholt(int n, const int32_t *__restrict_
     __shared__ int used[kIctCand];
     __shared__ int ci[kIctCand], si[kIctCand], keep[kIctCand];
     __shared__ double cv[kIctCand], sv[kIctCand];
-    __shared__ int s_nused, s_err, s_pk, s_fwd;
+    __shared__ int s_nused, s_err, s_pk, s_fwd, s_hasd;
     __shared__ double s_diag, s_fwd_l;
     const int lane = threadIdx.x;
     const unsigned long long below = (1ull << lane) - 1ull;    // the lanes before this one
@@ -129,7 +129,7 @@ __global__ __launch_bounds__(64) void k_icholt(int n, const int32_t *__restrict_
         ac = -1;
         if (k + 1 < n && p1 + lane < p2) { ac = aci[p1 + lane]; ax = av[p1 + lane]; }
         p0 = p1; p1 = p2; p2 = p3;
-        if (lane == 0) { s_pk = 0; s_diag = __builtin_nan(""); s_fwd = 0; }
+        if (lane == 0) { s_pk = 0; s_hasd = 0; s_fwd = 0; }
         wave_sync();
         // ---- the dependencies j (ascending: columns finish in order; lane d holds dependency d): L_kj, and where the entries of
         // column j below row k lie
@@ -182,7 +182,8 @@ __global__ __launch_bounds__(64) void k_icholt(int n, const int32_t *__restrict_
         const int alen = a1 - a0;
         const unsigned long long at_diag = __ballot(my_c == k);
         int pk = __popcll(__ballot(my_c > k));
-        double dg = at_diag ? lane_d(my_v, __ffsll((long long)at_diag) - 1) : __builtin_nan("");
+        bool has_diag = at_diag != 0ull;                       // (a stored NaN is a diagonal entry: the pivot test refuses it, not this one)
+        double dg = has_diag ? lane_d(my_v, __ffsll((long long)at_diag) - 1) : 0.0;
         const bool regs = use_regs && alen + total <= 64;
         int me = kNone;                                        // this lane's candidate (regs): row, value; nl lanes in use
         double val = 0.0;
@@ -196,7 +197,7 @@ __global__ __launch_bounds__(64) void k_icholt(int n, const int32_t *__restrict_
                 for (int q = a0 + 64 + lane; q < a1; q += 64) {
                     const int c = aci[q];
                     const double v = av[q];
-                    if (c == k) s_diag = v;
+                    if (c == k) { s_diag = v; s_hasd = 1; }
                     else if (c > k) {
                         hval[slot_of(c)] = v;
                         atomicAdd(&s_pk, 1);
@@ -204,12 +205,11 @@ __global__ __launch_bounds__(64) void k_icholt(int n, const int32_t *__restrict_
                 }
                 wave_sync();
                 pk += first_i(s_pk);
-                const double late = s_diag;
-                if (late == late) dg = late;
+                if (first_i(s_hasd)) { dg = s_diag; has_diag = true; }
             }
         }
         pk += add_fill;
-        if (!(dg == dg)) {                                   // no diagonal entry
+        if (!has_diag) {                                     // no diagonal entry
             if (lane == 0) { status[0] = ICHOLT_NODIAG; status[1] = k; }
             return;
         }
@@ -778,9 +778,14 @@ __global__ __launch_bounds__(kBlock) void k_icholt_emit(int n, const int *__rest
 
 }  // namespace dpcg
 
-// Factor `A` (the caller's matrix: a symmetric CSR with sorted columns) into `Lf` (owned CSR, diagonal last).  Leaves Lf empty on failure.
-int icholt_factor(const CsrDev &A, int add_fill_in, double threshold, CsrDev &Lf, hipStream_t s) {
+// Factor `A` (the caller's matrix) into `Lf` (owned CSR, diagonal last).  Of A only the entries at or right of the diagonal are read,
+// in whatever order a row stores them (the candidates of a column are sorted by row before anything depends on their order): the
+// lower triangle may be absent or incomplete.  The pipeline's pool bound takes nnz for that of a symmetric pattern; where it is
+// not, the staged columns may not fit and the one-wave kernel factors instead (info[2] = 0).  Leaves Lf empty on failure.
+// `info`: see dpcg_host.h.
+int icholt_factor(const CsrDev &A, int add_fill_in, double threshold, CsrDev &Lf, hipStream_t s, int32_t info[4]) {
     const int64_t n = A.n;
+    info[0] = 3; info[1] = 0; info[2] = -1; info[3] = 0;
     if (n > 0x7fffffff / kIctCap) return invalid("dpcg_set_precond_icholt: too many rows for the per-row lists");
     int *rcnt = nullptr, *rcol = nullptr, *rcc = nullptr, *crow = nullptr, *status = nullptr;
     int32_t *cnt = nullptr;
@@ -806,6 +811,7 @@ int icholt_factor(const CsrDev &A, int add_fill_in, double threshold, CsrDev &Lf
         // DPCG_ICHOLT_LDS = 2: the workspace form even where the LDS form fits (development / tests)
         const bool in_lds = n <= kLdsMaxRows && icholt_lds_bytes((int)n, (int)pool_cap, waves) + 64 <= 160 * 1024 && !(e_lds && e_lds[0] == '2');
         const bool in_mem = !in_lds && n <= kGmMaxRows;
+        info[3] = (int32_t)std::min<int64_t>(pool_cap, 0x7fffffff);
         if (lds_on && n >= 1 && pool_cap < 0xff00 && (in_lds || in_mem)) {
             const int64_t cap_nnz = pool_cap + n;
             double *ws = nullptr;
@@ -853,8 +859,11 @@ int icholt_factor(const CsrDev &A, int add_fill_in, double threshold, CsrDev &Lf
             }
             if (h_st[0] == ICHOLT_OK) {
                 Lf.nnz = h_st[2];
+                info[0] = in_lds ? 1 : 2;
+                info[1] = trace ? (waves == 8 && !in_mem ? 8 : 4) : (in_mem && waves == 16 ? 4 : waves);
                 return cleanup(DPCG_OK);
             }
+            info[2] = h_st[1];
             // not the plain case: the one-wave kernel runs it again (and names what is wrong, if something is)
             dev_free(status); dev_free(Lf.rowptr); dev_free(Lf.col); dev_free(Lf.val);
             status = nullptr; Lf.rowptr = nullptr; Lf.col = nullptr; Lf.val = nullptr;

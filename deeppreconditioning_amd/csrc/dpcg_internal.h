@@ -276,6 +276,9 @@ struct dpcg_system {
     // dpcg_set_precond_fsai (dpcg_fsai.hip): pattern, gather map and binning of the last FSAI factor, keyed on level | explicit pattern and
     // kept across dpcg_update_values (the next attach computes only values); any other preconditioner call frees it
     dpcg::FsaiCache *fsai = nullptr;
+    // dpcg_set_precond_icholt: which form of the device routine produced the attached factor (dpcg_get_icholt_info); [0] = 0: the
+    // attached preconditioner is not an ICholT factor.  Written by the attach, cleared by free_precond.
+    int32_t icholt_info[4] = {0, 0, -1, 0};
     // dpcg_reorder: the handle iterates on A = P A_user P^T; perm[new] = old, iperm[old] = new (device)
     int32_t *perm = nullptr, *iperm = nullptr;
     dpcg::CsrDev A_user;                  // the caller's matrix once A has been replaced by the reordered one

@@ -1464,14 +1464,29 @@ extern "C" int dpcg_set_precond_icholt(dpcg_handle_t h, int mode, int add_fill_i
     const CsrDev &Asrc = h->perm ? h->A_user : h->A;
     PhaseTimer pt(s);
     CsrDev Lf;
-    int st = icholt_factor(Asrc, add_fill_in, threshold, Lf, s);
+    int32_t info[4] = {0, 0, -1, 0};
+    int st = icholt_factor(Asrc, add_fill_in, threshold, Lf, s, info);
     if (st < 0) return st;
     pt.mark("icholt: columns");
     free_precond(h);
     h->L = Lf;
     st = finish_llt(h, mode, s);
-    if (st < 0) free_precond(h);
+    if (st < 0) {
+        free_precond(h);
+        return st;
+    }
+    for (int q = 0; q < 4; ++q) h->icholt_info[q] = info[q];
     return st;
+}
+
+extern "C" int dpcg_get_icholt_info(dpcg_handle_t h, int32_t out[4]) {
+    if (!h || !out) return invalid("dpcg_get_icholt_info: NULL handle or output");
+    if (h->icholt_info[0] == 0 || (h->precond != DPCG_PRECOND_LLT_MULTIPLY && h->precond != DPCG_PRECOND_LLT_SOLVE)) {
+        set_error("dpcg_get_icholt_info: the attached preconditioner is not an ICholT factor");
+        return DPCG_ERR_STATE;
+    }
+    for (int q = 0; q < 4; ++q) out[q] = h->icholt_info[q];
+    return DPCG_OK;
 }
 
 // The factorised sparse approximate inverse (contract: tests/fsai_restatement.py; device routine: dpcg_fsai.hip): an LLT_MULTIPLY

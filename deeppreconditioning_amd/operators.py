@@ -270,7 +270,9 @@ class ICholT(Preconditioner):
     nnz(A[k+1:, k]) + add_fill_in largest are kept.  The ilupp binary is not available: the factor equals the restatement of
     the published algorithm (oracle/oracle.py::icholt) bit for bit, PARITY UNPINNED against ilupp's own output.
     mode="multiply" is the reference's use (it multiplies by L L^T, test.py:88), mode="solve" applies the factor by triangular
-    solves.  See dpcg_set_precond_icholt in include/dpcg.h for the limits (64 kept entries per row / column)."""
+    solves.  See dpcg_set_precond_icholt in include/dpcg.h for the limits (64 kept entries per row / column), the refusals and
+    the three forms of the device routine (`CsrSystem.icholt_info()` says which one ran).  Of the matrix only the entries at or
+    right of the diagonal are read, in whatever order a row stores them: the factor is that of the matrix with sorted rows."""
 
     def __init__(self, mode: str = "multiply", add_fill_in: int = 1, threshold: float = 0.1):
         if mode not in ("solve", "multiply"):
@@ -960,6 +962,15 @@ class CsrSystem:
         L.check(L.lib().dpcg_get_fsai_info(self._h, out))
         return {"level": out[0], "max_m": out[1], "columns_by_width": {w: out[2 + k] for k, w in enumerate((4, 8, 16, 32, 64))},
                 "pattern_reused": bool(out[7])}
+
+    def icholt_info(self) -> dict:
+        """How the attached `ICholT` factor was produced (dpcg_get_icholt_info): `form` (1 the LDS pipeline, 2 the workspace pipeline,
+        3 one wave), `waves` of that pipeline (0 for form 3), `retry_column` (the column at which a pipeline attempt stopped and
+        form 3 factored the matrix again; None when no pipeline ran or it finished) and `pool_cap`, the pool bound the dispatcher
+        compared with its limits.  DpcgError (ERR_STATE) when the attached preconditioner is not an `ICholT` factor."""
+        out = (C.c_int32 * 4)()
+        L.check(L.lib().dpcg_get_icholt_info(self._h, out))
+        return {"form": out[0], "waves": out[1], "retry_column": None if out[2] < 0 else out[2], "pool_cap": out[3]}
 
     def lu_factors(self):
         """The attached `ILUT` factors (L, U) as scipy CSR in the caller's numbering: L unit lower (diagonal last), U upper

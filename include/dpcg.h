@@ -192,10 +192,38 @@ int dpcg_set_precond_ict(dpcg_handle_t h, int mode, int fill_in, double threshol
  * threshold * ||w_offdiag||_2 are dropped, of the rest the nnz(A[k+1:, k]) + add_fill_in largest are kept (ties: smaller row).
  * The ilupp binary is absent from the build image: the restatement (oracle/oracle.py::icholt) is pinned to the published
  * description, not to ilupp's output; the device factor equals the restatement bit for bit.  Limits: at most 64 kept entries
- * per row / column of L and 256 candidates per column (DPCG_ERR_INVALID beyond); a non-positive pivot is DPCG_ERR_PIVOT.  The
- * columns are walked in order by one wave (the pattern of a column depends on the values before it): milliseconds at the
- * reference's 2.4K-22K rows, ~3 us per row beyond. */
+ * per row / column of L and 256 candidates per column (DPCG_ERR_INVALID beyond); a non-positive pivot is DPCG_ERR_PIVOT.
+ * What of A is read: in row k only the entries at or right of the diagonal (column k of the symmetric matrix), in whatever order
+ * the row stores them; entries left of the diagonal are skipped, so the lower triangle may be incomplete or absent.  The factor
+ * is that of the matrix with sorted rows (a reordered handle factors the CALLER's matrix: the same bits).
+ * The pattern of a column depends on the values before it, so the columns are a chain.  Three forms of the device routine walk it
+ * (dpcg_get_icholt_info says which one produced the attached factor); with pool_cap = (nnz - n + 1) / 2 + n add_fill_in + 1, the
+ * bound on the kept off-diagonal entries of a symmetric pattern, and W = 4 waves (DPCG_ICHOLT_WAVES = 8 | 16: development):
+ *   1  the LDS pipeline: W waves of one workgroup, wave w takes the columns w, w + W, ...; the factor lives in one CU's LDS.
+ *      Needs n <= 4096 (12-bit row and column fields), pool_cap < 0xff00 and
+ *        bytes(n, pool_cap, W) + 64 <= 160 KiB,  bytes = 4096 + 256 (W + 8) + 14 P + 2 (P mod 2) + 18 R,
+ *        P = pool_cap + 64, R = n rounded up to a multiple of 4;
+ *   2  the workspace pipeline: the same pipeline with the factor in a workspace in memory (13-bit fields), for what does not fit
+ *      form 1 with n <= 8192 and pool_cap < 0xff00 (W = 4 or 8);
+ *   3  one wave walks every column: everything else (~3 us per row).
+ * A pipeline ends early -- and form 3 factors the whole matrix again, so the caller receives the same factor or form 3's refusal --
+ * on: more than 64 candidates in a column, a full row of L, a non-positive pivot, a pool that would overflow (a pattern that is
+ * not symmetric makes pool_cap too small), nnz(A[k+1:, k]) + add_fill_in > 64, a missing diagonal, or after 1 s.
+ * dpcg_get_icholt_info then reports form 3 and the column at which the pipeline stopped (0 for what it finds while staging A).
+ * Refusals (the text names the column k; the previous preconditioner stays attached):
+ *   DPCG_ERR_PIVOT    "icholt: non-positive pivot at column k" (w_k <= 0 or not a number: an indefinite matrix, a NaN, an inf
+ *                     below the diagonal; an inf ON the diagonal is a pivot like any other: L_kk = inf and zeros below it);
+ *   DPCG_ERR_PIVOT    "icholt: missing diagonal entry at column k";
+ *   DPCG_ERR_INVALID  "icholt: nnz + add_fill_in exceeds 64 entries at column k";
+ *   DPCG_ERR_INVALID  "icholt: more than 256 candidates at column k";
+ *   DPCG_ERR_INVALID  "icholt: a row of L would keep more than 64 entries (reached at column k)".
+ * add_fill_in >= 0; threshold >= 0 (inf included: every candidate is dropped unless the column's norm is 0; a candidate EQUAL to
+ * threshold * norm is kept). */
 int dpcg_set_precond_icholt(dpcg_handle_t h, int mode, int add_fill_in, double threshold, dpcg_stream_t stream);
+/* out = {the form that produced the attached ICholT factor (1 LDS pipeline, 2 workspace pipeline, 3 one wave), the waves W of that
+ * pipeline (0 for form 3), the column at which a pipeline attempt stopped and handed the matrix to form 3 (-1: no pipeline ran, or
+ * it finished), pool_cap}.  DPCG_ERR_STATE when the attached preconditioner did not come from dpcg_set_precond_icholt. */
+int dpcg_get_icholt_info(dpcg_handle_t h, int32_t out[4]);
 /* ilupp.ilut(A) as Saad's dual-threshold ILUT(p, tau) -- the reference harness's `incomplete_lu` technique (test.py:90-93: the
  * factors are MULTIPLIED, M = L U: mode DPCG_PRECOND_LU_MULTIPLY; DPCG_PRECOND_LU_SOLVE applies them by triangular solves).
  * Row by row in the caller's numbering (tests/ilut_restatement.py): w = A[i, :]; tau_i = threshold * ||A[i, :]||_2; for the

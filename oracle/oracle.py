@@ -387,7 +387,22 @@ def ict(A: sp.csr_matrix, fill_in: int = 1, threshold: float = 0.1, row_cap: int
     return sp.csr_matrix((lv[keep], ci[keep], out_rp), shape=A.shape)
 
 
-def icholt(A: sp.csr_matrix, add_fill_in: int = 0, threshold: float = 0.0, cand_cap: int = 256, row_cap: int = 64) -> sp.csr_matrix:
+class IcholtError(ValueError):
+    """What `icholt` refuses, as the device routine does: `kind` is "colcap" (nnz + add_fill_in of a column over row_cap), "cand"
+    (more candidates than cand_cap), "pivot" (non-positive or NaN pivot), "nodiag" (no stored diagonal entry) or "rowcap" (a row
+    of L over row_cap; `column` is the column whose entry did not fit)."""
+
+    def __init__(self, kind: str, column: int, text: str):
+        super().__init__(text)
+        self.kind, self.column = kind, column
+
+
+ICHOLT_DEFECTS = ("ties_to_larger_row", "drop_on_equal", "norm_with_diagonal", "dependencies_descending", "count_without_fill",
+                  "scale_by_unreduced_diagonal")
+
+
+def icholt(A: sp.csr_matrix, add_fill_in: int = 0, threshold: float = 0.0, cand_cap: int = 256, row_cap: int = 64,
+           stats: dict | None = None, defect: str | None = None) -> sp.csr_matrix:
     """Thresholded incomplete Cholesky as ILU++ defines it -- the contract of `ilupp.icholt(A, add_fill_in, threshold)`, the
     reference harness's DEFAULT incomplete-Cholesky technique (test.py:81-88: `icholt(matrix, add_fill_in=1, threshold=0.1)`).
 
@@ -410,50 +425,84 @@ def icholt(A: sp.csr_matrix, add_fill_in: int = 0, threshold: float = 0.0, cand_
     threshold = 0 keeps the p_k largest (IC with `add_fill_in` extra entries per column); add_fill_in = 0, threshold = 0 on a
     matrix whose IC(0) creates no fill-free cancellation is NOT IC(0): ICT picks the largest entries, which may be fill.
     `cand_cap` / `row_cap` are the bounds of the device routine (candidates per column, kept entries per row of L): exceeding
-    them raises here as it fails there.  Returns L as lower-triangular CSR, columns ascending, diagonal last."""
+    them raises here as it fails there (IcholtError, a ValueError that names the kind and the column).  Of A only the entries at
+    or right of the diagonal are read (row k of the symmetric matrix = its column k), in sorted order.
+    `stats` (tests): a dict that receives, per column, "candidates" (how many), "passed" (how many the threshold left), "p"
+    (the count bound), "kept", "tie_cut" (the count bound cut through candidates of equal magnitude), "on_bound" (a candidate's
+    magnitude EQUALS threshold * norm) and "squares_finite" (the sum of squares is finite and the square of every non-zero
+    candidate is a normal number).  `defect` (tests of the tests): one of ICHOLT_DEFECTS, a deliberate single deviation from the rule above.
+    Returns L as lower-triangular CSR, columns ascending, diagonal last."""
+    assert defect is None or defect in ICHOLT_DEFECTS
     A = sp.csr_matrix(A)
     A.sort_indices()
     n = A.shape[0]
     arp, aci, av = A.indptr, A.indices, A.data.astype(np.float64)
     rows_j = [[] for _ in range(n)]      # row i of L: the kept (j, L_ij), ascending j by construction
     cols = [None] * n                    # column j of L: kept (i, L_ij), ascending i
+    if stats is not None:
+        stats.update({key: [0] * n for key in ("candidates", "passed", "p", "kept")})
+        stats.update({key: [False] * n for key in ("tie_cut", "on_bound")})
+        stats["squares_finite"] = [True] * n
     for k in range(n):
         cand = {}
         diag = 0.0
+        has_diag = False
         p_k = 0
         for q in range(arp[k], arp[k + 1]):          # row k of the symmetric A = column k: entries with index >= k
             i = int(aci[q])
             if i == k:
                 diag = float(av[q])
+                has_diag = True
             elif i > k:
                 cand[i] = float(av[q])
                 p_k += 1
         p_k += int(add_fill_in)
         if p_k > row_cap:
-            raise ValueError("icholt: nnz + add_fill_in of a column exceeds row_cap")
-        for j, lkj in rows_j[k]:
+            raise IcholtError("colcap", k, "icholt: nnz + add_fill_in of a column exceeds row_cap")
+        if not has_diag:
+            raise IcholtError("nodiag", k, f"icholt: non-positive pivot at column {k} (no diagonal entry)")
+        unreduced = diag
+        for j, lkj in (reversed(rows_j[k]) if defect == "dependencies_descending" else rows_j[k]):
             diag = diag - lkj * lkj
             for i, lij in cols[j]:
                 if i > k:
                     cand[i] = cand.get(i, 0.0) - lkj * lij
         if len(cand) > cand_cap:
-            raise ValueError("icholt: more candidates in a column than cand_cap")
+            raise IcholtError("cand", k, "icholt: more candidates in a column than cand_cap")
         if not diag > 0.0:
-            raise ValueError(f"icholt: non-positive pivot at column {k}")
+            raise IcholtError("pivot", k, f"icholt: non-positive pivot at column {k}")
         d = float(np.sqrt(diag))
         items = sorted(cand.items())
-        ss = 0.0
+        ss = diag * diag if defect == "norm_with_diagonal" else 0.0
         for _, v in items:
             ss = ss + v * v
         norm = float(np.sqrt(ss))
-        kept = [(i, v) for i, v in items if not abs(v) < threshold * norm]
+        bound = threshold * norm
+        if defect == "drop_on_equal":
+            kept = [(i, v) for i, v in items if not abs(v) <= bound]
+        else:
+            kept = [(i, v) for i, v in items if not abs(v) < bound]
+        passed = len(kept)
+        if defect == "count_without_fill":
+            p_k -= int(add_fill_in)
         if len(kept) > p_k:
-            kept = sorted(sorted(kept, key=lambda t: (-abs(t[1]), t[0]))[:p_k])
-        col = [(i, v / d) for i, v in kept]
+            sign = -1 if defect == "ties_to_larger_row" else 1
+            by_size = sorted(kept, key=lambda t: (-abs(t[1]), sign * t[0]))
+            if stats is not None and p_k > 0:
+                stats["tie_cut"][k] = abs(by_size[p_k - 1][1]) == abs(by_size[p_k][1])
+            kept = sorted(by_size[:p_k])
+        if stats is not None:
+            stats["candidates"][k], stats["passed"][k], stats["p"][k], stats["kept"][k] = len(items), passed, p_k, len(kept)
+            stats["on_bound"][k] = any(abs(v) == bound for _, v in items)
+            stats["squares_finite"][k] = bool(np.isfinite(ss)) and all(v * v >= 2.2250738585072014e-308 for _, v in items if v != 0.0)
+        if defect == "scale_by_unreduced_diagonal":
+            col = [(i, v / float(np.sqrt(unreduced))) for i, v in kept]
+        else:
+            col = [(i, v / d) for i, v in kept]
         cols[k] = col
         for i, lik in col:
             if len(rows_j[i]) >= row_cap:
-                raise ValueError("icholt: more kept entries in a row than row_cap")
+                raise IcholtError("rowcap", k, "icholt: more kept entries in a row than row_cap")
             rows_j[i].append((k, lik))
         rows_j[k].append((k, d))
     rp = np.zeros(n + 1, dtype=np.int32)
