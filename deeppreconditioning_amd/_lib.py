@@ -23,6 +23,8 @@ F64, F32 = 0, 1
 DEVICE, HOST = 0, 1
 PRECOND_NONE, PRECOND_JACOBI, PRECOND_CSR, PRECOND_LLT_MULTIPLY, PRECOND_LLT_SOLVE, PRECOND_CALLBACK, PRECOND_AMG = 0, 1, 2, 3, 4, 5, 6
 PRECOND_LU_MULTIPLY, PRECOND_LU_SOLVE = 7, 8
+PRECOND_BLOCK_LLT_SOLVE = 9
+BLOCK_IC_IC0, BLOCK_IC_DIC = 0, 1
 PRECOND_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p)   # dpcg_precond_fn
 INIT_CHECK_R, SPMV_F32, NO_GRAPH, NO_SMALL, VAL32_IF_LOSSLESS, NO_FUSE, NO_TEAM, TEAM = 1, 2, 4, 8, 16, 32, 64, 128
 SINGLE_REDUCTION = 256
@@ -72,6 +74,8 @@ SIGNATURES = {
     "dpcg_set_precond_fsai": (_int, [_p, _int, _p]),
     "dpcg_set_precond_fsai_pattern": (_int, [_p, _i64, _p, _p, _int, _p]),
     "dpcg_get_fsai_info": (_int, [_p, _p]),
+    "dpcg_set_precond_block_ic": (_int, [_p, _int, _int, _p, _int, _p]),
+    "dpcg_get_block_ic_info": (_int, [_p, _p]),
     "dpcg_get_lu_factors": (_int, [_p, C.POINTER(_i64), C.POINTER(_i64), _p, _p, _p, _p, _p, _p]),
     "dpcg_get_reduction_geometry": (_int, [_p, _p]),
     "dpcg_get_chip_info": (_int, [_p, _p, _p]),

@@ -354,6 +354,7 @@ void free_precond(dpcg_system *h, bool keep_parked) {
     free_amg(h->amg);
     if (!keep_parked) free_amg(h->amg_parked);
     if (keep_parked) fsai_detach(h->fsai); else free_fsai(h->fsai);
+    if (keep_parked) block_ic_detach(h->bic); else free_block_ic(h->bic);
     h->icholt_info[0] = h->icholt_info[1] = h->icholt_info[3] = 0;
     h->icholt_info[2] = -1;
     h->precond = DPCG_PRECOND_NONE;
@@ -448,8 +449,12 @@ extern "C" int dpcg_reorder(dpcg_handle_t h, int mode, dpcg_stream_t stream, int
     SetupScope scope(s, true);
     // Everything that can fail is built FIRST, into locals; the handle is switched over only when all of it exists
     // (a failure half way would otherwise leave the old plan on the new matrix).
-    auto adopt = [&](int32_t *perm, int32_t *iperm, CsrDev &B, SpmvPlan &planB) {
-        free_precond(h);                 // an attached preconditioner referred to the old matrix
+    auto adopt = [&](int32_t *perm, int32_t *iperm, CsrDev &B, SpmvPlan &planB) -> int {
+        // a block incomplete-Cholesky factor is the caller's matrix's, in the caller's numbering: it stays, only its way into the
+        // handle's vectors is rebuilt (block_ic_renumbered)
+        BlockIc *bic = h->precond == DPCG_PRECOND_BLOCK_LLT_SOLVE ? h->bic : nullptr;
+        if (bic) h->bic = nullptr;
+        free_precond(h);                 // any other attached preconditioner referred to the old matrix
         dev_free(h->mc_perm);            // ... and so did a cached colouring
         dev_free(h->mc_iperm);
         h->mc_colors = 0;
@@ -465,6 +470,10 @@ extern "C" int dpcg_reorder(dpcg_handle_t h, int mode, dpcg_stream_t stream, int
         h->perm = perm;
         h->iperm = iperm;
         if (applied) *applied = 1;
+        h->bic = bic;
+        const int st = block_ic_renumbered(h, s);
+        if (st < 0) free_precond(h);
+        return st;
     };
     // order -> P A P^T -> its SpMV plan, all in locals; *keep = false (AUTO by regions) when the plan is not the x-tile one
     auto build = [&](bool by_regions, bool tile_or_nothing, bool *keep) -> int {
@@ -487,8 +496,7 @@ extern "C" int dpcg_reorder(dpcg_handle_t h, int mode, dpcg_stream_t stream, int
             free_plan(planB);
             return st;
         }
-        adopt(perm, iperm, B, planB);
-        return DPCG_OK;
+        return adopt(perm, iperm, B, planB);
     };
     bool kept = false;
     if (mode == DPCG_REORDER_AUTO) {
@@ -645,7 +653,8 @@ extern "C" int dpcg_get_info(dpcg_handle_t h, int64_t *n, int64_t *nnz, int *spm
     if (precond_nnz) {
         const bool lu = h->precond == DPCG_PRECOND_LU_MULTIPLY || h->precond == DPCG_PRECOND_LU_SOLVE;
         *precond_nnz = h->precond == DPCG_PRECOND_CSR ? h->M.nnz
-                     : (h->precond == DPCG_PRECOND_AMG ? amg_nnz(h->amg) : (lu ? h->L.nnz + h->Lt.nnz : h->L.nnz));
+                     : (h->precond == DPCG_PRECOND_AMG ? amg_nnz(h->amg)
+                     : (h->precond == DPCG_PRECOND_BLOCK_LLT_SOLVE ? block_ic_nnz(h->bic) : (lu ? h->L.nnz + h->Lt.nnz : h->L.nnz)));
     }
     if ((n_levels_lower || n_levels_upper) && h->lvlL.n_levels < 0) DPCG_TRY(count_levels_on_demand(h));
     if (n_levels_lower) *n_levels_lower = h->lvlL.n_levels;
@@ -743,6 +752,7 @@ int rz_partial_count(const dpcg_system *h) {
     if (h->precond == DPCG_PRECOND_LLT_MULTIPLY || h->precond == DPCG_PRECOND_LU_MULTIPLY) return h->planL.grid;
     if ((h->precond == DPCG_PRECOND_LLT_SOLVE || h->precond == DPCG_PRECOND_LU_SOLVE) && h->lvlU.sweep) return h->lvlU.sweep_grid;   // colour sweeps
     if (h->precond == DPCG_PRECOND_AMG && amg_rz_partials(h->amg) > 0) return amg_rz_partials(h->amg);   // level 0's last smoothing pass
+    if (h->precond == DPCG_PRECOND_BLOCK_LLT_SOLVE && block_ic_rz_partials(h->bic) > 0) return block_ic_rz_partials(h->bic);   // one per block
     return h->vec_grid;
 }
 
@@ -776,6 +786,9 @@ int apply_precond(dpcg_system *h, const double *r, double *z, hipStream_t s, boo
             break;
         case DPCG_PRECOND_AMG:                // one V-cycle; its last kernel sums <r, z> on the way when asked to
             DPCG_TRY(amg_apply(h, r, z, s, part_rz, n_part_rz, in_loop ? &h->scal->done : nullptr));
+            break;
+        case DPCG_PRECOND_BLOCK_LLT_SOLVE:    // one launch, one workgroup per block; it sums <r, z> on the way when asked to
+            DPCG_TRY(block_ic_apply(h, r, z, s, part_rz, n_part_rz, in_loop ? &h->scal->done : nullptr));
             break;
         case DPCG_PRECOND_CALLBACK:
             if (h->perm) {                        // the caller's function sees the caller's numbering; t and q (dead

@@ -83,6 +83,17 @@ int fsai_upload_pattern(int64_t n, int64_t nnz, const int32_t *rowptr, const int
 void free_fsai(FsaiCache *&c);
 void fsai_detach(FsaiCache *c);                         // the handle's preconditioner is no longer this factor
 void fsai_mark_attached(FsaiCache *c);
+// dpcg_block_ic.hip: the block-Jacobi incomplete Cholesky -- release; the handle's preconditioner is no longer this factor; the handle has
+// been renumbered (the way into its vectors is rebuilt, the factor stays attached); the apply (part_rz: the workgroups leave their
+// shares of <r, z>); how many partials an in-loop apply leaves (0: none, more blocks than the partial buffer holds); nnz(L); the getters
+void free_block_ic(BlockIc *&c);
+void block_ic_detach(BlockIc *c);
+int block_ic_renumbered(dpcg_system *h, hipStream_t s);
+int block_ic_apply(dpcg_system *h, const double *r, double *z, hipStream_t s, double *part_rz, int *n_part_rz, const int *done = nullptr);
+int block_ic_rz_partials(const BlockIc *c);
+int64_t block_ic_nnz(const BlockIc *c);
+int block_ic_get_factor(const dpcg_system *h, int32_t *rowptr, int32_t *col, double *val);
+int block_ic_get_ordering(const dpcg_system *h, int32_t *perm_host);
 void free_parked(dpcg_system *h);                       // dpcg_api.hip: the multicolour IC(0) parked by dpcg_update_values
 void free_levels(Levels &l);
 namespace dpcg { void orphan_guesses(dpcg_system *h); }   // dpcg_guess.hip: the handle is going away

@@ -215,6 +215,7 @@ void launch_sfs_block_max(const int32_t *blk, int nblk, const int32_t *lo_rowptr
 
 struct AmgState;   // dpcg_amg.hip: a smoothed-aggregation hierarchy
 struct FsaiCache;  // dpcg_fsai.hip: what the symbolic phase of an FSAI factor leaves on the handle
+struct BlockIc;    // dpcg_block_ic.hip: a block-Jacobi incomplete-Cholesky factor (symbolic phase and values)
 struct NullSpace;  // dpcg_nullspace.hip: the null space attached to a singular (semi-definite) system and its solve state
 struct Deflation;  // dpcg_deflation.hip: the A-orthonormal deflation vectors W, A W and the partial buffer of a deflated solve
 struct Refine;     // dpcg_refine.hip: the fp32 copies and fp32 work vectors of dpcg_solve_refined
@@ -276,6 +277,9 @@ struct dpcg_system {
     // dpcg_set_precond_fsai (dpcg_fsai.hip): pattern, gather map and binning of the last FSAI factor, keyed on level | explicit pattern and
     // kept across dpcg_update_values (the next attach computes only values); any other preconditioner call frees it
     dpcg::FsaiCache *fsai = nullptr;
+    // dpcg_set_precond_block_ic (dpcg_block_ic.hip): the factor DPCG_PRECOND_BLOCK_LLT_SOLVE applies.  dpcg_update_values keeps its symbolic
+    // phase (numbering, block extraction, level sets) for the next attach with the same block ids; any other preconditioner call frees it
+    dpcg::BlockIc *bic = nullptr;
     // dpcg_set_precond_icholt: which form of the device routine produced the attached factor (dpcg_get_icholt_info); [0] = 0: the
     // attached preconditioner is not an ICholT factor.  Written by the attach, cleared by free_precond.
     int32_t icholt_info[4] = {0, 0, -1, 0};

@@ -1270,6 +1270,7 @@ extern "C" int dpcg_get_precond_ordering(dpcg_handle_t h, int *n_colors, int32_t
     if (!h) return invalid("NULL handle");
     if (n_colors) *n_colors = h->precond_colors;
     if (!perm_host) return DPCG_OK;
+    if (h->precond == DPCG_PRECOND_BLOCK_LLT_SOLVE) return block_ic_get_ordering(h, perm_host);    // (the caller's rows, block by block)
     const int64_t n = h->A.n;
     if (!h->fmap) {
         for (int64_t k = 0; k < n; ++k) perm_host[k] = (int32_t)k;
@@ -1535,6 +1536,7 @@ extern "C" int dpcg_set_precond_fsai_pattern(dpcg_handle_t h, int64_t nnz, const
 
 extern "C" int dpcg_get_factor(dpcg_handle_t h, int32_t *rowptr, int32_t *col, double *val) {
     if (!h) return invalid("NULL handle");
+    if (h->precond == DPCG_PRECOND_BLOCK_LLT_SOLVE) return block_ic_get_factor(h, rowptr, col, val);
     if (h->precond != DPCG_PRECOND_LLT_MULTIPLY && h->precond != DPCG_PRECOND_LLT_SOLVE) {
         set_error("dpcg_get_factor: no L factor set");
         return DPCG_ERR_STATE;

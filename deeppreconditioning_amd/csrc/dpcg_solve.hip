@@ -158,6 +158,7 @@ static int precond_launches(const dpcg_system *h) {
         case DPCG_PRECOND_LLT_MULTIPLY: case DPCG_PRECOND_LU_MULTIPLY: return 2;
         case DPCG_PRECOND_LLT_SOLVE: case DPCG_PRECOND_LU_SOLVE: return trsv(h->lvlL) + trsv(h->lvlU);
         case DPCG_PRECOND_AMG: return amg_launches(h->amg);
+        case DPCG_PRECOND_BLOCK_LLT_SOLVE: return 1;
         default: return 0;
     }
 }
@@ -626,6 +627,7 @@ extern "C" int dpcg_get_reduction_geometry(dpcg_handle_t h, int32_t out[16]) {
             rzk = h->lvlU.sweep ? 9 : ((h->lvlU.level_major && h->lvlU.strips.n_strips == 0) ? 2 : 1);
             break;
         case DPCG_PRECOND_AMG: rzk = amg_rz_partials(h->amg) > 0 ? 9 : 1; break;   // (the V-cycle's last smoothing pass)
+        case DPCG_PRECOND_BLOCK_LLT_SOLVE: rzk = block_ic_rz_partials(h->bic) > 0 ? 9 : 1; break;   // (one partial per block)
         default: rzk = 1; break;
     }
     out[9] = out[10] = out[11] = 0;

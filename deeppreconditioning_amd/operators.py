@@ -367,6 +367,51 @@ class FSAI(Preconditioner):
         raise TypeError("FSAI needs the system matrix: attach it with CsrSystem.set_preconditioner")
 
 
+class BlockIC(Preconditioner):
+    """Block-Jacobi incomplete Cholesky: the unknowns are partitioned into blocks of at most 4096 rows, every block is factored on its
+    own and couplings between blocks are dropped -- OpenFOAM's DIC per subdomain of a decomposed run, PETSc's bjacobi + icc.  One
+    launch applies it, one workgroup per block with the block's slice of the vector in LDS: no workgroup waits for another.  Not in
+    the reference.  Between Jacobi and the global IC(0) in iterations (20^3 Poisson, 27 boxes: 46 / 22 / 15).
+
+    blocks: an int (contiguous runs of that many rows, 1 .. 4096) or an (n,) integer array of non-negative block ids in the caller's
+    numbering (any values; `poisson.subdomain_blocks` gives the boxes of a grid).  variant: "ic0" (IC(0) of the block-diagonal part)
+    or "dic" (OpenFOAM's diagonal-based variant: the same on 5- / 7-point grids up to rounding, cheaper to set up, different where the
+    lower triangle holds triangles).  The factor equals tests/block_ic_restatement.py bit for bit; `CsrSystem.factor()` and
+    `CsrSystem.precond_ordering()` return it and its numbering, `CsrSystem.block_ic_info()` describes it.  See
+    dpcg_set_precond_block_ic in include/dpcg.h for the contract, the errors and what is kept across `update_values`."""
+
+    def __init__(self, blocks=1024, variant: str = "ic0"):
+        if variant not in ("ic0", "dic"):
+            raise ValueError("variant must be 'ic0' or 'dic'")
+        self.variant = L.BLOCK_IC_DIC if variant == "dic" else L.BLOCK_IC_IC0
+        if isinstance(blocks, (int, np.integer)) and not isinstance(blocks, bool):
+            if not 1 <= int(blocks) <= 4096:
+                raise ValueError("blocks must be in 1 .. 4096 rows")
+            self.block_rows, self.ids = int(blocks), None
+        else:
+            if isinstance(blocks, torch.Tensor):
+                blocks = blocks.detach().cpu().numpy()
+            ids = np.asarray(blocks)
+            if ids.ndim != 1 or ids.size == 0:
+                raise ValueError("blocks must be an int or an (n,) integer array")
+            if not np.issubdtype(ids.dtype, np.integer):
+                raise ValueError("blocks must hold integers")
+            if ids.size and (ids.min() < -2**31 or ids.max() > 2**31 - 1):
+                raise ValueError("block ids must fit int32")
+            self.block_rows, self.ids = 0, np.ascontiguousarray(ids, dtype=np.int32)
+
+    def _attach(self, system):
+        if self.ids is None:
+            L.check(L.lib().dpcg_set_precond_block_ic(system._h, self.variant, self.block_rows, None, L.HOST, _stream()))
+            return
+        if self.ids.size != system.n:
+            raise ValueError("blocks has the wrong length")
+        L.check(L.lib().dpcg_set_precond_block_ic(system._h, self.variant, 0, _np_ptr(self.ids), L.HOST, _stream()))
+
+    def __matmul__(self, r):
+        raise TypeError("BlockIC needs the system matrix: attach it with CsrSystem.set_preconditioner")
+
+
 class ICT(Preconditioner):
     """Thresholded incomplete Cholesky on a STATIC pattern -- tril(A) plus level-1 fill -- with MATLAB's 'ict' drop rule
     (contract: oracle/oracle.py::ict).  Not what `ilupp.icholt` computes (that is `ICholT`: a per-column entry count instead
@@ -962,6 +1007,15 @@ class CsrSystem:
         L.check(L.lib().dpcg_get_fsai_info(self._h, out))
         return {"level": out[0], "max_m": out[1], "columns_by_width": {w: out[2 + k] for k, w in enumerate((4, 8, 16, 32, 64))},
                 "pattern_reused": bool(out[7])}
+
+    def block_ic_info(self) -> dict:
+        """The attached `BlockIC` factor (dpcg_get_block_ic_info): variant, number of blocks, rows of the largest block, the most
+        dependency levels of L and of L^T in any block (the barriers of an apply), the apply kernel's workgroup size, whether the last
+        attach reused the symbolic phase.  DpcgError (ERR_STATE) otherwise."""
+        out = (C.c_int32 * 8)()
+        L.check(L.lib().dpcg_get_block_ic_info(self._h, out))
+        return {"variant": ("ic0", "dic")[out[0]], "blocks": out[1], "max_block": out[2], "levels_lower": out[3], "levels_upper": out[4],
+                "threads": out[5], "pattern_reused": bool(out[6])}
 
     def icholt_info(self) -> dict:
         """How the attached `ICholT` factor was produced (dpcg_get_icholt_info): `form` (1 the LDS pipeline, 2 the workspace pipeline,

@@ -81,11 +81,8 @@ def neumann_csr(dims, coefficient_seed=None):
     return A
 
 
-def subdomain_indicators(shape, blocks):
-    """The piecewise-constant deflation vectors of a box partition (Nicolaides' subdomain deflation; `CsrSystem.set_deflation`): the
-    grid `shape` (first index fastest, as `neumann_csr` and `poisson_csr` number it) is cut into blocks[0] x blocks[1] [x ...] boxes,
-    axis a into blocks[a] runs of near-equal length, and column j of the (prod(shape), prod(blocks)) result is 1 on box j and 0
-    elsewhere -- every row sums to 1.  ValueError when a box would be empty (more blocks than grid points along an axis)."""
+def _subdomain_boxes(shape, blocks):
+    """(box id per grid point, number of boxes) of the box partition `subdomain_indicators` and `subdomain_blocks` share."""
     shape = tuple(int(d) for d in shape)
     blocks = tuple(int(d) for d in blocks)
     if len(shape) != len(blocks) or not shape or min(shape) < 1 or min(blocks) < 1:
@@ -100,8 +97,23 @@ def subdomain_indicators(shape, blocks):
         box += ((idx // off) % d) * nb // d * boff         # point c of the axis lies in run floor(c nb / d)
         off *= d
         boff *= nb
-    W = np.zeros((rows, int(np.prod(blocks))), order="F")
-    W[idx, box] = 1.0
+    return box, int(np.prod(blocks))
+
+
+def subdomain_blocks(shape, blocks):
+    """The box id of every grid point, (prod(shape),) int32, for the box partition of `subdomain_indicators` (the same cut rule:
+    axis a into blocks[a] runs of near-equal length, box ids with the first axis fastest) -- the `blocks=` of `BlockIC`."""
+    return _subdomain_boxes(shape, blocks)[0].astype(np.int32)
+
+
+def subdomain_indicators(shape, blocks):
+    """The piecewise-constant deflation vectors of a box partition (Nicolaides' subdomain deflation; `CsrSystem.set_deflation`): the
+    grid `shape` (first index fastest, as `neumann_csr` and `poisson_csr` number it) is cut into blocks[0] x blocks[1] [x ...] boxes,
+    axis a into blocks[a] runs of near-equal length, and column j of the (prod(shape), prod(blocks)) result is 1 on box j and 0
+    elsewhere -- every row sums to 1.  ValueError when a box would be empty (more blocks than grid points along an axis)."""
+    box, n_boxes = _subdomain_boxes(shape, blocks)
+    W = np.zeros((box.size, n_boxes), order="F")
+    W[np.arange(box.size, dtype=np.int64), box] = 1.0
     return W
 
 

@@ -55,7 +55,8 @@ enum dpcg_precond {
     DPCG_PRECOND_CALLBACK = 5,     /* z = M r by a caller-supplied function (the duck-typed `M @ rk`) */
     DPCG_PRECOND_AMG = 6,          /* z = M r by one smoothed-aggregation V-cycle  test.py:95-98 (algebraic_multigrid) */
     DPCG_PRECOND_LU_MULTIPLY = 7,  /* z = L (U r), the reference's M = L U          test.py:90-93 (incomplete_lu)       */
-    DPCG_PRECOND_LU_SOLVE = 8      /* z = U^-1 (L^-1 r), level-scheduled SpTRSVs of an L U factor                      */
+    DPCG_PRECOND_LU_SOLVE = 8,     /* z = U^-1 (L^-1 r), level-scheduled SpTRSVs of an L U factor                      */
+    DPCG_PRECOND_BLOCK_LLT_SOLVE = 9 /* z = P^T L^-T L^-1 P r, L block diagonal: one workgroup per block (dpcg_set_precond_block_ic) */
 };
 
 /* dpcg_solve flags */
@@ -270,6 +271,41 @@ int dpcg_set_precond_fsai_pattern(dpcg_handle_t h, int64_t nnz, const int32_t *r
 /* out = {level (0: explicit pattern), max m_i, columns with m_i <= 4, 5 .. 8, 9 .. 16, 17 .. 32, 33 .. 64, 1 when the last attach
  * reused the symbolic phase}; nnz(L) is dpcg_get_info's.  DPCG_ERR_STATE when the attached preconditioner is not an FSAI factor. */
 int dpcg_get_fsai_info(dpcg_handle_t h, int32_t out[8]);
+/* Block-Jacobi incomplete Cholesky: the unknowns are partitioned, every block is factored on its own, couplings between blocks
+ * are dropped (what OpenFOAM's DIC does per subdomain of a decomposed run and PETSc's bjacobi + icc does by default).  Not in the
+ * reference.  Contract (tests/block_ic_restatement.py; the device equals it bit for bit):
+ *   numbering  rows sorted stably by (block id, caller's row); perm[k] = the caller's row at factor position k; blocks = the maximal
+ *              runs of equal id.  Ids are any non-negative int32, need not be dense; a block holds at most 4096 rows.
+ *   A_B        P A P^T without the entries whose row and column lie in different blocks.
+ *   IC(0)      DPCG_BLOCK_IC_IC0: L = oracle.ic0(A_B) -- pattern tril(A_B), rows in factor order, sums over ascending columns one
+ *              product at a time, no contraction (the order of dpcg_set_precond_ic0).
+ *   DIC        DPCG_BLOCK_IC_DIC: d_i = a_ii - sum a_ij a_ij / d_j over the stored j < i of row i of A_B ascending (per term one
+ *              product, one division, one subtraction); L_ij = a_ij / sqrt(d_j), L_ii = sqrt(d_i).  Equal to IC(0) mathematically
+ *              (not bitwise) where tril(A_B) holds no triangle (5- / 7-point grids), different on meshes with hanging nodes.
+ *   apply      z = P^T L^-T L^-1 P r by substitution: row sums in the factor's CSR order, then the division (oracle.sptrsv_lower,
+ *              oracle.sptrsv_upper_t).  M is SPD for every SPD A.
+ * block_of_row == NULL: contiguous runs of block_rows caller rows (1 .. 4096; the last run may be shorter); otherwise n ids
+ * (memspace DPCG_HOST or DPCG_DEVICE) and block_rows is ignored.
+ * One launch applies M: one workgroup per block gathers its slice of r into LDS, solves L and L^T in place level by level with a
+ * workgroup barrier between levels and scatters z; in the PCG loop it leaves one partial of <r, z> per block (up to 2048 blocks;
+ * beyond, the dot kernel runs).  The workgroup has 64 lanes for blocks of up to 64 rows, 128 up to 512, 256 up to 2048, else 512.
+ * Served by the multi-launch PCG driver (graph replay included), the null-space and deflated drivers, dpcg_precond_apply,
+ * dpcg_spectrum, dpcg_guess_* and -- through the launches, as kinds 4 and 8 -- dpcg_solve_batch; no one-launch form (one workgroup,
+ * team, whole chip), DPCG_SINGLE_REDUCTION, dpcg_solve_refined or dpcg_sptrsv takes it.  dpcg_get_factor returns L in the factor
+ * numbering, dpcg_get_precond_ordering gives 0 colours and perm, dpcg_get_info nnz(L) (its level counts are those of other kinds:
+ * see dpcg_get_block_ic_info).
+ * Errors: DPCG_ERR_PIVOT for a non-positive or non-finite pivot (the text names the caller's row); DPCG_ERR_INVALID for a block of
+ * more than 4096 rows (the text names the block id and its size), a negative id, a missing diagonal, a row whose columns do not
+ * strictly ascend.  After any failure the previous preconditioner stays.
+ * Reuse: numbering, block extraction and level sets stay on the handle across dpcg_update_values; an attach with the same ids (either
+ * variant) computes only values.  dpcg_reorder keeps an attached block factor attached -- blocks and factor are the caller's, a
+ * reordered handle gives the same bits -- and rebuilds its maps into the handle's vectors. */
+enum dpcg_block_ic_variant { DPCG_BLOCK_IC_IC0 = 0, DPCG_BLOCK_IC_DIC = 1 };
+int dpcg_set_precond_block_ic(dpcg_handle_t h, int variant, int block_rows, const int32_t *block_of_row, int memspace,
+                              dpcg_stream_t stream);
+/* out = {variant, blocks, rows of the largest block, most levels of L in any block, the same for L^T, the apply kernel's workgroup
+ * size, 1 when the last attach reused the symbolic phase, 0}.  DPCG_ERR_STATE for any other preconditioner. */
+int dpcg_get_block_ic_info(dpcg_handle_t h, int32_t out[8]);
 /* The reference's operator protocol asks of M nothing but `M @ rk` (cg.py:61,81).  An M that is not a matrix this library
  * can hold (a Python object with __matmul__, a multigrid cycle, ...) is applied through a function the caller supplies:
  * fn(user, r, z, n, stream) must ENQUEUE z = M r on `stream` (device pointers, caller's numbering; it is called from the
