@@ -112,6 +112,7 @@ SIGNATURES = {
                           C.POINTER(_dbl), _p, _p, _p]),
     "dpcg_solve_refined": (_int, [_p, _p, _p, _p, _dbl, _dbl, _int, _dbl, _int, _int, _p, C.POINTER(_int), C.POINTER(_int),
                                   C.POINTER(_dbl), C.POINTER(_dbl), _p, _p]),
+    "dpcg_solve_bicgstab": (_int, [_p, _p, _p, _p, _dbl, _dbl, _int, _int, _p, C.POINTER(_int), C.POINTER(_dbl), C.POINTER(_dbl), _p]),
     "dpcg_solve_batch": (_int, [_int, _p, _p, _p, _p, _dbl, _dbl, _int, _int, _int, _p, _p, _p, _p]),
     "dpcg_poisson_sizes": (_int, [_int, _i64, C.POINTER(_i64), C.POINTER(_i64)]),
     "dpcg_gen_poisson": (_int, [_int, _i64, _p, _p, _p, _int, _p]),

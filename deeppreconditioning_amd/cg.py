@@ -78,6 +78,20 @@ def preconditioned_conjugate_gradient(A, b, M, x0=None, x_true=None, rtol=1e-8, 
     return result.seconds, iterations, 0
 
 
+def bicgstab(A, b, M=None, x0=None, rtol=1e-8, max_iter=1024, *, details=False):
+    """Right-preconditioned BiCGStab for systems whose values are not symmetric (`CsrSystem.solve_bicgstab`; no reference
+    counterpart, the return value has the shape of the reference's PCG).  Returns `(duration_seconds, iterations, info)` with `info`
+    the status (0 converged, 1 `max_iter` reached, 2 breakdown); `details=True` returns the `SolveResult`.  `rtol` is compared with
+    <r,r>/<b,b> of the original system (squared ratio).  `M`: None, a matrix or any `Preconditioner` but an operator with
+    `__matmul__` (the callback path is refused: DpcgError)."""
+    system = _system_and_device(A, b)
+    system.set_preconditioner(M)
+    result = system.solve_bicgstab(b, x0, rtol_sq=float(rtol), max_iter=int(max_iter))
+    if details:
+        return result
+    return result.seconds, result.iterations, result.status
+
+
 def conjugate_gradient(A, b, x0=None, x_true=None, rtol=1e-8, max_iter=1024, *, recurrence="standard", nullspace=None,
                        deflation=None):
     """Unpreconditioned CG, cg.py:20-47.  Returns `(errors, x_hat)` with

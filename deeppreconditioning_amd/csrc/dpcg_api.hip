@@ -404,6 +404,7 @@ extern "C" int dpcg_destroy(dpcg_handle_t h) {
     orphan_guesses(h);
     free_nullspace(h);
     free_deflation(h);
+    free_bicgstab(h);
     free_precond(h);
     free_csr(h->A);
     free_csr(h->A_user);

@@ -255,6 +255,9 @@ void free_deflation(dpcg_system *h);
 // dpcg_refine.hip: what dpcg_solve_refined keeps on the handle (fp32 values, fp32 reciprocal diagonal, fp32 work vectors); free_precond
 // calls it, so new values, a new preconditioner and a reordering all drop it
 void free_refine(dpcg_system *h);
+// dpcg_bicgstab.hip: what dpcg_solve_bicgstab keeps on the handle (four work vectors, partial buffers, its scalar record); dpcg_destroy
+// calls it
+void free_bicgstab(dpcg_system *h);
 // dpcg_guess.hip, shared with dpcg_deflation.hip: the device and host pieces of CholQR2 on a tall-skinny pair X, W = A X (column-major, ld a
 // multiple of 1024 rows apart, padding rows zero).  gs_gram_column: out[i] = <X[:, i], v>, i < l (part: l x ld / 128 doubles of scratch);
 // gs_cholesky_rinv: G = R^T R (G[j * l + i] = G_ij), T = R^-1 of the leading keep x keep block (row-major), keep = the first j whose pivot is

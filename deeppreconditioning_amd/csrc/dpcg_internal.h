@@ -219,6 +219,7 @@ struct BlockIc;    // dpcg_block_ic.hip: a block-Jacobi incomplete-Cholesky fact
 struct NullSpace;  // dpcg_nullspace.hip: the null space attached to a singular (semi-definite) system and its solve state
 struct Deflation;  // dpcg_deflation.hip: the A-orthonormal deflation vectors W, A W and the partial buffer of a deflated solve
 struct Refine;     // dpcg_refine.hip: the fp32 copies and fp32 work vectors of dpcg_solve_refined
+struct BiCgStab;   // dpcg_bicgstab.hip: the vectors, partial buffers and scalar record of dpcg_solve_bicgstab
 
 // (dpcg_chip_trsv.hip; the comment is with ChipTrsvDesc below)
 struct ChipTrsvLists {
@@ -340,6 +341,8 @@ struct dpcg_system {
     // dpcg_solve_refined (dpcg_refine.hip): made by its first call, dropped with the preconditioner (new values, a reordering); no other
     // entry point reads it
     dpcg::Refine *rf = nullptr;
+    // dpcg_solve_bicgstab (dpcg_bicgstab.hip): made by its first call, kept until dpcg_destroy; no other entry point reads it
+    dpcg::BiCgStab *bi = nullptr;
 };
 
 namespace dpcg {

@@ -1114,6 +1114,25 @@ class CsrSystem:
         return RefinedSolveResult(x, k, outer.value, status, res.value, sec.value,
                                   hist[: k + 1] if hist is not None else np.empty(0), outer_hist[: outer.value + 1])
 
+    def solve_bicgstab(self, b, x0=None, *, rtol_sq: float = 1e-8, atol_sq: float = 0.0, max_iter: int = 1024,
+                       graph: bool = True) -> SolveResult:
+        """Right-preconditioned BiCGStab (dpcg_solve_bicgstab in include/dpcg.h) for a system whose values are not symmetric, or
+        whose preconditioner is not (`ILUT`, an explicit `CsrPreconditioner`).  Every preconditioner but an `OperatorPreconditioner`
+        is taken; a handle with a null space or a deflation raises DpcgError (ERR_INVALID) with the reason.  `res_history[k]` is
+        <r_k,r_k>/<b,b> of the original system, `status` 0 converged / 1 max_iter / 2 breakdown; `recurrence` says "bicgstab".
+        `graph=False` passes DPCG_NO_GRAPH (accepted: this driver replays no graph, the bits are the same)."""
+        bv = self._vec(b)
+        x0v = None if x0 is None else self._vec(x0)
+        x = torch.empty_like(bv)
+        hist = np.full(max(int(max_iter), 0) + 1, np.nan)
+        iters, res, sec = C.c_int(), C.c_double(), C.c_double()
+        with torch.cuda.device(self.device):
+            status = L.check(L.lib().dpcg_solve_bicgstab(
+                self._h, _dev_ptr(bv), _dev_ptr(x0v), _dev_ptr(x), rtol_sq, atol_sq, int(max_iter), 0 if graph else L.NO_GRAPH,
+                _stream(), C.byref(iters), C.byref(res), C.byref(sec), _np_ptr(hist)))
+        k = iters.value
+        return SolveResult(x, k, status, res.value, sec.value, hist[: k + 1], None, "bicgstab")
+
     def amg_hierarchy(self) -> AmgHierarchy:
         """The smoothed-aggregation hierarchy of the attached `SmoothedAggregation` preconditioner (DpcgError otherwise)."""
         cap = 64

@@ -81,6 +81,54 @@ def neumann_csr(dims, coefficient_seed=None):
     return A
 
 
+def convection_diffusion_csr(shape, peclet, coefficient_seed=None):
+    """Host-side first-order-upwind finite-volume convection-diffusion matrix on a shape[0] x shape[1] [x shape[2]] grid of unit
+    cells, first index fastest: a structurally symmetric 5-point (2-D) or 7-point (3-D) pattern with NON-symmetric values -- what
+    OpenFOAM's momentum and phase-fraction matrices look like, and what `CsrSystem.solve_bicgstab` is for.  Every face carries a
+    diffusion coefficient d_f drawn from [1, 2) (`default_rng(coefficient_seed)`, None meaning seed 0; axis by axis: the interior
+    faces in row order, then the faces on the lower boundary, then those on the upper one), so 1/diag is not a scalar.  A constant
+    flux F = `peclet` >= 0 crosses every face in the positive direction of every axis (the cell Peclet number F / d_f lies in
+    (peclet / 2, peclet]).  Across the face between cell i and its upper neighbour j: a_ii += d_f + F, a_ij = -d_f,
+    a_ji = -(d_f + F), a_jj += d_f.  Dirichlet boundaries (value 0 on the boundary face): a_ii += d_f on both, and a_ii += F on the
+    outflow side.  Off-diagonals are negative, every row is weakly and every boundary row strictly diagonally dominant: a
+    nonsingular M-matrix.  peclet = 0 gives a symmetric variable-coefficient Poisson matrix.  Returns a scipy CSR matrix with sorted
+    int32 indices."""
+    import scipy.sparse as sp
+    shape = tuple(int(d) for d in shape)
+    if len(shape) not in (2, 3) or min(shape) < 1:
+        raise ValueError("shape must be 2 or 3 positive grid sizes")
+    flux = float(peclet)
+    if not (flux >= 0.0 and np.isfinite(flux)):
+        raise ValueError("peclet must be finite and >= 0")
+    rows = int(np.prod(shape))
+    idx = np.arange(rows, dtype=np.int64)
+    rng = np.random.default_rng(0 if coefficient_seed is None else coefficient_seed)
+    r_list, c_list, v_list = [], [], []
+    diag = np.zeros(rows)
+    off = 1
+    for d in shape:
+        pos = (idx // off) % d
+        lo = idx[pos < d - 1]                         # the lower cell of every interior face along this axis
+        w = rng.uniform(1.0, 2.0, lo.size)
+        r_list += [lo, lo + off]
+        c_list += [lo + off, lo]
+        v_list += [-w, -(w + flux)]
+        np.add.at(diag, lo, w + flux)
+        np.add.at(diag, lo + off, w)
+        first, last = idx[pos == 0], idx[pos == d - 1]
+        np.add.at(diag, first, rng.uniform(1.0, 2.0, first.size))
+        np.add.at(diag, last, rng.uniform(1.0, 2.0, last.size) + flux)
+        off *= d
+    r_list.append(idx)
+    c_list.append(idx)
+    v_list.append(diag)
+    A = sp.csr_matrix((np.concatenate(v_list), (np.concatenate(r_list), np.concatenate(c_list))), shape=(rows, rows))
+    A.sort_indices()
+    A.indices = A.indices.astype(np.int32)
+    A.indptr = A.indptr.astype(np.int32)
+    return A
+
+
 def _subdomain_boxes(shape, blocks):
     """(box id per grid point, number of boxes) of the box partition `subdomain_indicators` and `subdomain_blocks` share."""
     shape = tuple(int(d) for d in shape)

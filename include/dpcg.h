@@ -688,6 +688,39 @@ int dpcg_solve_refined(dpcg_handle_t h, const double *b, const double *x0, doubl
                        int max_iter, double inner_rtol_sq, int max_outer, int flags, dpcg_stream_t stream,
                        int *iters, int *outer, double *final_res, double *seconds, double *res_history, double *outer_history);
 
+/* ---- BiCGStab: systems whose VALUES are not symmetric, and preconditioners that are not ------------------------------------
+ * Every other solve form here is a conjugate-gradient recurrence and needs a symmetric positive definite A and a symmetric M.  This
+ * one is right-preconditioned BiCGStab (van der Vorst, SIAM J. Sci. Stat. Comput. 13, 1992), what OpenFOAM pairs PCG with (PBiCGStab)
+ * for its momentum and phase-fraction matrices: a structurally symmetric pattern with non-symmetric values.  Not in the reference.
+ * Right-preconditioned: the residual it recurs is the residual of the ORIGINAL system.
+ *     r0 = b - A x0;  rhat = r0;  bb = <b,b>;  rho = alpha = omega = 1;  v = p = 0;  history[0] = <r0,r0>/bb, tested (always on r:
+ *                                                                                     there is no z0 quirk here)
+ *     update k:  rho' = <rhat,r>;  beta = (rho'/rho)(alpha/omega);  rho = rho'
+ *                p = r + beta (p - omega v);  ph = M p;  v = A ph;  alpha = rho / <rhat,v>
+ *                s = r - alpha v;  ss = <s,s>
+ *                if ss meets the test:  x += alpha ph;  history[k+1] = ss/bb;  count = k+1;  stop (DPCG_OK)
+ *                sh = M s;  t = A sh;  omega = <t,s>/<t,t>
+ *                x += alpha ph + omega sh  (as (x + alpha ph) + omega sh);  r = s - omega t;  history[k+1] = <r,r>/bb;  test
+ * The pointer rules, the stream semantics, `seconds`, the squared-ratio test (res < rtol_sq or <r,r> < atol_sq) and the meaning of
+ * iters / final_res / res_history are dpcg_solve's.  DPCG_BREAKDOWN: rho', <rhat,v> or <t,t> is exactly zero, or one of the sums is not
+ * finite (a history entry that is not a number included, as for <b,b> = 0); x is then the last iterate that was completed, iters its
+ * index, and the history ends there.  DPCG_MAX_ITER after max_iter updates; max_iter = 0 tests r0 only.  (omega = 0 is not examined: the
+ * next update's sums are then not finite and end the solve.)
+ * An update is the launches P | v = A ph | S | t = A sh | <t,t> | X: three fused vector passes (dpcg_bicgstab.hip) around the handle's own
+ * SpMV, whose epilogue leaves the partials of <rhat,v> and of <s,t>; M = I and Jacobi are fused into the passes, any other M runs as the
+ * pass, the handle's apply (dpcg_precond_apply's internals), the SpMV.  The scalars live on the device and every decision -- the test, the
+ * half-step exit, a breakdown -- is taken there; the host keeps updates enqueued ahead of a progress word, at most max_iter of them.
+ * Every dot product is per-workgroup partials summed in one fixed order (no float atomics): two runs of the same call give the same bits.
+ * A: any CSR dpcg_create accepts; a reordered handle works as in dpcg_solve (b, x0, x keep the caller's numbering).
+ * M: DPCG_PRECOND_NONE, JACOBI, CSR, LLT_MULTIPLY, LLT_SOLVE, LU_MULTIPLY, LU_SOLVE, BLOCK_LLT_SOLVE and AMG; no symmetry is asked of it.
+ * flags: 0 or DPCG_NO_GRAPH (accepted; this driver replays no graph).  Refused with DPCG_ERR_INVALID and a reason in dpcg_last_error,
+ * the handle unchanged: DPCG_PRECOND_CALLBACK (the driver enqueues updates ahead of the test and a callback cannot be skipped once it has
+ * passed); a handle with a null space or a deflation; any other flag; a tolerance that is not finite; max_iter < 0.  dpcg_solve and
+ * every other entry point keep their paths and bits.  Returns DPCG_OK / DPCG_MAX_ITER / DPCG_BREAKDOWN or a negative error. */
+int dpcg_solve_bicgstab(dpcg_handle_t h, const double *b, const double *x0, double *x, double rtol_sq, double atol_sq,
+                        int max_iter, int flags, dpcg_stream_t stream, int *iters, double *final_res, double *seconds,
+                        double *res_history);
+
 /* `count` independent systems (train.py:90-108 / test.py:121-149 loop over samples): handles[i],
  * b[i], x0[i], x[i] as above; outputs are arrays of length count.  Systems are interleaved on
  * `n_streams` internal streams (1..8).  Returns the worst status. */
