@@ -109,6 +109,7 @@ int gs_block_rows() {
 }
 
 enum MisState : int8_t { MIS_OUT = 0, MIS_UND = 1, MIS_IN = 2 };
+constexpr int kAmgGrid = 65536;       // most workgroups of a setup or cycle kernel that strides over its items
 
 __device__ __forceinline__ uint64_t amg_hash(uint64_t seed, uint64_t i) {   // splitmix64 finaliser of a counter (as k_lz_start)
     uint64_t x = seed * 0x9E3779B97F4A7C15ull + (i + 1) * 0xBF58476D1CE4E5B9ull;
@@ -120,10 +121,6 @@ __device__ __forceinline__ uint64_t amg_hash(uint64_t seed, uint64_t i) {   // s
     return x;
 }
 
-inline int grid_of(int64_t n, int per_block = kBlock) {
-    int64_t g = (n + per_block - 1) / per_block;
-    return (int)std::max<int64_t>(1, std::min<int64_t>(g, 65536));
-}
 
 // ---- setup kernels ---------------------------------------------------------------------------------------------
 // dinv[i] = 1 / a_ii; *bad |= 1 when a diagonal is missing, zero, negative or not finite
@@ -702,13 +699,6 @@ void launch_cheb(const AmgLevel &L, const AT *av, const AT *dinv, double c1, dou
 }
 
 // ---- host helpers ---------------------------------------------------------------------------------------------------
-template <typename T>
-int read1(const T *dev, T *host, hipStream_t s) {
-    DPCG_HIP(hipMemcpyAsync(host, dev, sizeof(T), hipMemcpyDeviceToHost, s));
-    DPCG_HIP(hipStreamSynchronize(s));
-    return DPCG_OK;
-}
-
 void free_level(AmgLevel &L, bool keep_a) {
     if (!keep_a) free_csr(L.A);
     dev_free(L.dinv);
@@ -727,20 +717,6 @@ void free_level(AmgLevel &L, bool keep_a) {
     L = AmgLevel();
 }
 
-// scoped temporaries of the setup (freed on every return path)
-struct Tmp {
-    std::vector<void *> blocks;
-    template <typename T>
-    int alloc(T **p, int64_t count) {
-        DPCG_TRY(dev_alloc(p, count));
-        blocks.push_back(*p);
-        return DPCG_OK;
-    }
-    ~Tmp() {
-        for (void *p : blocks) cached_free(p);
-    }
-};
-
 // an owned CSR matrix that is freed unless released (a Galerkin product in flight between two levels)
 struct CsrOwner {
     CsrDev c;
@@ -751,52 +727,50 @@ struct CsrOwner {
 int spgemm(const CsrDev &X, const CsrDev &Y, int64_t ncols, CsrDev &C, int epi, const int32_t *agg, const double *tval,
            const double *dinv, double omega, hipStream_t s) {
     const int64_t m = X.n;
-    Tmp t;
-    int32_t *cnt = nullptr, *lpad = nullptr, *loff = nullptr;
-    DPCG_TRY(t.alloc(&cnt, m));
-    DPCG_TRY(t.alloc(&lpad, m + 1));
-    DPCG_TRY(t.alloc(&loff, m + 1));
-    unsigned long long *total = nullptr;
-    DPCG_TRY(t.alloc(&total, 1));
-    hipLaunchKernelGGL(k_sg_products, dim3(grid_of(m)), dim3(kBlock), 0, s, m, X.rowptr, X.col, Y.rowptr, cnt, lpad);
-    hipLaunchKernelGGL(k_set_last, dim3(1), dim3(1), 0, s, lpad, m);
+    DevBuf<int32_t> cnt, lpad, loff, len;
+    DevBuf<unsigned long long> total;
+    DPCG_TRY(cnt.alloc(m));
+    DPCG_TRY(lpad.alloc(m + 1));
+    DPCG_TRY(loff.alloc(m + 1));
+    DPCG_TRY(total.alloc(1));
+    hipLaunchKernelGGL(k_sg_products, dim3(grid_blocks(m, kAmgGrid)), dim3(kBlock), 0, s, m, X.rowptr, X.col, Y.rowptr, cnt.p, lpad.p);
+    hipLaunchKernelGGL(k_set_last, dim3(1), dim3(1), 0, s, lpad.p, m);
     // the scratch offsets are an int32 scan: its total is checked in 64 bits first (a sum past 2^32 would wrap back to a small
     // positive number, and the long rows would be sorted outside the scratch)
-    DPCG_HIP(hipMemsetAsync(total, 0, sizeof(unsigned long long), s));
-    hipLaunchKernelGGL(k_sum_i64, dim3(grid_of(m)), dim3(kBlock), 0, s, m, lpad, total);
+    DPCG_HIP(hipMemsetAsync(total.p, 0, sizeof(unsigned long long), s));
+    hipLaunchKernelGGL(k_sum_i64, dim3(grid_blocks(m, kAmgGrid)), dim3(kBlock), 0, s, m, lpad.p, total.p);
     unsigned long long scratch64 = 0;
-    DPCG_TRY(read1(total, &scratch64, s));
+    DPCG_TRY(fetch(&scratch64, total.p, 1, s));
     if (scratch64 >= 0x7fffffffull) {
         set_error("dpcg_set_precond_amg: the long rows of a Galerkin product need more than 2^31 scratch entries");
         return DPCG_ERR_INVALID;
     }
-    DPCG_TRY(exclusive_scan_i32(lpad, loff, m + 1, s));
+    DPCG_TRY(exclusive_scan_i32(lpad.p, loff.p, m + 1, s));
     const int32_t scratch = (int32_t)scratch64;
-    uint64_t *gkey = nullptr;
-    double *gval = nullptr;
-    DPCG_TRY(t.alloc(&gkey, std::max<int64_t>(1, scratch)));
-    DPCG_TRY(t.alloc(&gval, std::max<int64_t>(1, scratch)));
+    DevBuf<uint64_t> gkey;
+    DevBuf<double> gval;
+    DPCG_TRY(gkey.alloc(std::max<int64_t>(1, scratch)));
+    DPCG_TRY(gval.alloc(std::max<int64_t>(1, scratch)));
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(m, 1 << 20));
     const bool symbolic = C.rowptr == nullptr;
     if (symbolic) {
         C = CsrDev();
         C.n = m;
         C.owned = true;
-        int32_t *len = nullptr;
-        DPCG_TRY(t.alloc(&len, m + 1));
+        DPCG_TRY(len.alloc(m + 1));
         DPCG_TRY(dev_alloc(&C.rowptr, m + 1));
         hipLaunchKernelGGL((k_spgemm<SG_COUNT, SG_PLAIN>), dim3(grid), dim3(64), 0, s, m, X.rowptr, X.col, X.val, Y.rowptr, Y.col,
-                           Y.val, cnt, loff, gkey, gval, nullptr, nullptr, nullptr, len, nullptr, nullptr, nullptr, 0.0);
-        hipLaunchKernelGGL(k_set_last, dim3(1), dim3(1), 0, s, len, m);
-        DPCG_HIP(hipMemsetAsync(total, 0, sizeof(unsigned long long), s));
-        hipLaunchKernelGGL(k_sum_i64, dim3(grid_of(m)), dim3(kBlock), 0, s, m, len, total);
+                           Y.val, cnt.p, loff.p, gkey.p, gval.p, nullptr, nullptr, nullptr, len.p, nullptr, nullptr, nullptr, 0.0);
+        hipLaunchKernelGGL(k_set_last, dim3(1), dim3(1), 0, s, len.p, m);
+        DPCG_HIP(hipMemsetAsync(total.p, 0, sizeof(unsigned long long), s));
+        hipLaunchKernelGGL(k_sum_i64, dim3(grid_blocks(m, kAmgGrid)), dim3(kBlock), 0, s, m, len.p, total.p);
         unsigned long long nnz64 = 0;
-        DPCG_TRY(read1(total, &nnz64, s));
+        DPCG_TRY(fetch(&nnz64, total.p, 1, s));
         if (nnz64 > 0x7fffffffull) {
             set_error("dpcg_set_precond_amg: a Galerkin product has more than 2^31 entries");
             return DPCG_ERR_INVALID;
         }
-        DPCG_TRY(exclusive_scan_i32(len, C.rowptr, m + 1, s));
+        DPCG_TRY(exclusive_scan_i32(len.p, C.rowptr, m + 1, s));
         const int32_t nnz = (int32_t)nnz64;
         C.nnz = nnz;
         DPCG_TRY(dev_alloc(&C.col, std::max<int64_t>(1, nnz)));
@@ -805,31 +779,22 @@ int spgemm(const CsrDev &X, const CsrDev &Y, int64_t ncols, CsrDev &C, int epi, 
     (void)ncols;
     if (epi == SG_SMOOTH)
         hipLaunchKernelGGL((k_spgemm<SG_NUMERIC, SG_SMOOTH>), dim3(grid), dim3(64), 0, s, m, X.rowptr, X.col, X.val, Y.rowptr, Y.col,
-                           Y.val, cnt, loff, gkey, gval, C.rowptr, C.col, C.val, nullptr, agg, tval, dinv, omega);
+                           Y.val, cnt.p, loff.p, gkey.p, gval.p, C.rowptr, C.col, C.val, nullptr, agg, tval, dinv, omega);
     else
         hipLaunchKernelGGL((k_spgemm<SG_NUMERIC, SG_PLAIN>), dim3(grid), dim3(64), 0, s, m, X.rowptr, X.col, X.val, Y.rowptr, Y.col,
-                           Y.val, cnt, loff, gkey, gval, C.rowptr, C.col, C.val, nullptr, nullptr, nullptr, nullptr, 0.0);
+                           Y.val, cnt.p, loff.p, gkey.p, gval.p, C.rowptr, C.col, C.val, nullptr, nullptr, nullptr, nullptr, 0.0);
     DPCG_CHECK_LAUNCH();
     DPCG_HIP(hipStreamSynchronize(s));
     return DPCG_OK;
 }
 
-// P^T (nc x n) by a stable sort of P's entries by column; `order` (entry of P^T -> entry of P) kept for a values-only refresh
+// P^T (nc x n); `order` (entry of P^T -> entry of P) kept for a values-only refresh
 int transpose_p(const CsrDev &P, int64_t nc, CsrDev &Pt, int32_t **order_io, hipStream_t s) {
     const int64_t nnz = P.nnz;
-    Tmp t;
-    int32_t *row_of = nullptr;
-    DPCG_TRY(t.alloc(&row_of, nnz));
-    launch_row_of(P.n, P.rowptr, row_of, s);
-    if (!*order_io) {
-        int32_t *iota = nullptr;
-        uint32_t *keys = nullptr;
-        DPCG_TRY(t.alloc(&iota, nnz));
-        DPCG_TRY(t.alloc(&keys, nnz));
+    if (*order_io) {
+        launch_gather_f64(nnz, *order_io, P.val, Pt.val, s);
+    } else {
         DPCG_TRY(dev_alloc(order_io, nnz));
-        launch_iota(nnz, iota, s);
-        DPCG_TRY(sort_pairs_u32_i32(reinterpret_cast<const uint32_t *>(P.col), keys, iota, *order_io, nnz,
-                                    bits_for((uint64_t)std::max<int64_t>(1, nc - 1)), s));
         free_csr(Pt);
         Pt.n = nc;
         Pt.nnz = nnz;
@@ -837,9 +802,8 @@ int transpose_p(const CsrDev &P, int64_t nc, CsrDev &Pt, int32_t **order_io, hip
         DPCG_TRY(dev_alloc(&Pt.rowptr, nc + 1));
         DPCG_TRY(dev_alloc(&Pt.col, nnz));
         DPCG_TRY(dev_alloc(&Pt.val, nnz));
-        launch_group_offsets(nnz, keys, (int)nc, Pt.rowptr, s);
+        DPCG_TRY(transpose_csr(P.n, nc, nnz, P.rowptr, P.col, P.val, Pt.rowptr, Pt.col, Pt.val, *order_io, s));
     }
-    launch_transpose_gather(nnz, *order_io, row_of, P.val, Pt.col, Pt.val, s);
     DPCG_HIP(hipStreamSynchronize(s));
     return DPCG_OK;
 }
@@ -958,10 +922,10 @@ int make_f32_copies(AmgLevel &L, hipStream_t s) {
     DPCG_TRY(dev_alloc(&L.p32, pn));
     DPCG_TRY(dev_alloc(&L.pt32, pn));
     DPCG_TRY(dev_alloc(&L.dinv32, n));
-    hipLaunchKernelGGL(k_amg_to_f32, dim3(grid_of(L.A.nnz)), dim3(kBlock), 0, s, L.A.nnz, L.A.val, nullptr, L.a32);
-    hipLaunchKernelGGL(k_amg_to_f32, dim3(grid_of(L.P.nnz)), dim3(kBlock), 0, s, L.P.nnz, L.P.val, nullptr, L.p32);
-    hipLaunchKernelGGL(k_amg_to_f32, dim3(grid_of(L.P.nnz)), dim3(kBlock), 0, s, L.P.nnz, L.P.val, L.pt_order, L.pt32);
-    hipLaunchKernelGGL(k_amg_to_f32, dim3(grid_of(n)), dim3(kBlock), 0, s, n, L.dinv, nullptr, L.dinv32);
+    hipLaunchKernelGGL(k_amg_to_f32, dim3(grid_blocks(L.A.nnz, kAmgGrid)), dim3(kBlock), 0, s, L.A.nnz, L.A.val, nullptr, L.a32);
+    hipLaunchKernelGGL(k_amg_to_f32, dim3(grid_blocks(L.P.nnz, kAmgGrid)), dim3(kBlock), 0, s, L.P.nnz, L.P.val, nullptr, L.p32);
+    hipLaunchKernelGGL(k_amg_to_f32, dim3(grid_blocks(L.P.nnz, kAmgGrid)), dim3(kBlock), 0, s, L.P.nnz, L.P.val, L.pt_order, L.pt32);
+    hipLaunchKernelGGL(k_amg_to_f32, dim3(grid_blocks(n, kAmgGrid)), dim3(kBlock), 0, s, n, L.dinv, nullptr, L.dinv32);
     DPCG_CHECK_LAUNCH();
     DPCG_HIP(hipStreamSynchronize(s));
     return DPCG_OK;
@@ -1051,22 +1015,21 @@ int level_error(int status, int level, const char *what) {
 // MIS(2) of the strong graph of level L: L.roots (1 = root)
 int mis2(AmgLevel &L, const int32_t *perm, uint64_t seed, int *flags, int8_t *st, uint64_t *hsh, int32_t *cid, hipStream_t s) {
     const int64_t n = L.A.n;
-    Tmp t;
-    int8_t *st2 = nullptr;
-    int32_t *m1 = nullptr, *m2 = nullptr;
-    DPCG_TRY(t.alloc(&st2, n));
-    DPCG_TRY(t.alloc(&m1, n));
-    DPCG_TRY(t.alloc(&m2, n));
-    const int g = grid_of(n);
+    DevBuf<int8_t> st2;
+    DevBuf<int32_t> m1, m2;
+    DPCG_TRY(st2.alloc(n));
+    DPCG_TRY(m1.alloc(n));
+    DPCG_TRY(m2.alloc(n));
+    const int g = grid_blocks(n, kAmgGrid);
     for (int round = 0;; ++round) {
         if (round > 100000) return invalid("dpcg_set_precond_amg: MIS(2) did not terminate");
-        hipLaunchKernelGGL(k_mis_max, dim3(g), dim3(kBlock), 0, s, n, L.A.rowptr, L.A.col, L.strong, st, hsh, cid, nullptr, m1);
-        hipLaunchKernelGGL(k_mis_max, dim3(g), dim3(kBlock), 0, s, n, L.A.rowptr, L.A.col, L.strong, st, hsh, cid, m1, m2);
+        hipLaunchKernelGGL(k_mis_max, dim3(g), dim3(kBlock), 0, s, n, L.A.rowptr, L.A.col, L.strong, st, hsh, cid, nullptr, m1.p);
+        hipLaunchKernelGGL(k_mis_max, dim3(g), dim3(kBlock), 0, s, n, L.A.rowptr, L.A.col, L.strong, st, hsh, cid, m1.p, m2.p);
         DPCG_HIP(hipMemsetAsync(flags, 0, sizeof(int), s));
-        hipLaunchKernelGGL(k_mis_update, dim3(g), dim3(kBlock), 0, s, n, st, m2, st2, flags);
-        DPCG_HIP(hipMemcpyAsync(st, st2, (size_t)n, hipMemcpyDeviceToDevice, s));
+        hipLaunchKernelGGL(k_mis_update, dim3(g), dim3(kBlock), 0, s, n, st, m2.p, st2.p, flags);
+        DPCG_HIP(hipMemcpyAsync(st, st2.p, (size_t)n, hipMemcpyDeviceToDevice, s));
         int left = 0;
-        DPCG_TRY(read1(flags, &left, s));
+        DPCG_TRY(fetch(&left, flags, 1, s));
         if (!left) break;
     }
     (void)perm;
@@ -1081,9 +1044,8 @@ int mis2(AmgLevel &L, const int32_t *perm, uint64_t seed, int *flags, int8_t *st
 // entry that cancels to zero leaves the strength graph.)
 int build(dpcg_system *h, AmgState &S, AmgState *old, hipStream_t s) {
     PhaseTimer pt(s);
-    Tmp keep;
-    int *flags = nullptr;
-    DPCG_TRY(keep.alloc(&flags, 2));
+    DevBuf<int> flags;
+    DPCG_TRY(flags.alloc(2));
     bool reuse = old != nullptr;
     CsrOwner next_owner;                            // A_{l+1} as the Galerkin product of level l left it (freed on an error return)
     CsrDev &nextA = next_owner.c;
@@ -1100,38 +1062,37 @@ int build(dpcg_system *h, AmgState &S, AmgState *old, hipStream_t s) {
             nextA = CsrDev();
         }
         const int64_t n = L.A.n;
-        const int g = grid_of(n);
-        Tmp t;
-        double *diag = nullptr;
+        const int g = grid_blocks(n, kAmgGrid);
+        DevBuf<double> diag;
         DPCG_TRY(dev_alloc(&L.dinv, n));
-        DPCG_TRY(t.alloc(&diag, n));
-        DPCG_HIP(hipMemsetAsync(flags, 0, 2 * sizeof(int), s));
-        hipLaunchKernelGGL(k_amg_diag, dim3(g), dim3(kBlock), 0, s, n, L.A.rowptr, L.A.col, L.A.val, L.dinv, diag, flags);
+        DPCG_TRY(diag.alloc(n));
+        DPCG_HIP(hipMemsetAsync(flags.p, 0, 2 * sizeof(int), s));
+        hipLaunchKernelGGL(k_amg_diag, dim3(g), dim3(kBlock), 0, s, n, L.A.rowptr, L.A.col, L.A.val, L.dinv, diag.p, flags.p);
         int bad = 0;
-        DPCG_TRY(read1(flags, &bad, s));
+        DPCG_TRY(fetch(&bad, flags.p, 1, s));
         if (bad) return level_error(DPCG_ERR_PIVOT, l, "a diagonal entry is missing, zero, negative or not finite");
         bool coarsest = n <= S.max_coarse || l == S.max_levels - 1;
-        int32_t *cid = nullptr, *flag_by_cid = nullptr, *rank = nullptr;
+        DevBuf<int32_t> cid, flag_by_cid, rank;
         int64_t nc = 0;
         if (!coarsest) {
             DPCG_TRY(dev_alloc(&L.strong, std::max<int64_t>(1, L.A.nnz)));
-            hipLaunchKernelGGL(k_amg_strength, dim3(g), dim3(kBlock), 0, s, n, L.A.rowptr, L.A.col, L.A.val, diag, S.theta, L.strong);
-            int8_t *st = nullptr;
-            uint64_t *hsh = nullptr;
-            DPCG_TRY(t.alloc(&st, n));
-            DPCG_TRY(t.alloc(&hsh, n));
-            DPCG_TRY(t.alloc(&cid, n));
+            hipLaunchKernelGGL(k_amg_strength, dim3(g), dim3(kBlock), 0, s, n, L.A.rowptr, L.A.col, L.A.val, diag.p, S.theta, L.strong);
+            DevBuf<int8_t> st;
+            DevBuf<uint64_t> hsh;
+            DPCG_TRY(st.alloc(n));
+            DPCG_TRY(hsh.alloc(n));
+            DPCG_TRY(cid.alloc(n));
             const int32_t *perm = l == 0 ? h->perm : nullptr;
-            hipLaunchKernelGGL(k_mis_init, dim3(g), dim3(kBlock), 0, s, n, (unsigned long long)S.seed, perm, st, hsh, cid);
-            DPCG_TRY(t.alloc(&flag_by_cid, n + 1));
-            DPCG_TRY(t.alloc(&rank, n + 1));
+            hipLaunchKernelGGL(k_mis_init, dim3(g), dim3(kBlock), 0, s, n, (unsigned long long)S.seed, perm, st.p, hsh.p, cid.p);
+            DPCG_TRY(flag_by_cid.alloc(n + 1));
+            DPCG_TRY(rank.alloc(n + 1));
             DPCG_TRY(dev_alloc(&L.roots, n));
-            DPCG_TRY(mis2(L, perm, S.seed, flags, st, hsh, cid, s));
-            hipLaunchKernelGGL(k_root_flags, dim3(g), dim3(kBlock), 0, s, n, st, cid, L.roots, flag_by_cid);
-            hipLaunchKernelGGL(k_set_last, dim3(1), dim3(1), 0, s, flag_by_cid, n);
-            DPCG_TRY(exclusive_scan_i32(flag_by_cid, rank, n + 1, s));
+            DPCG_TRY(mis2(L, perm, S.seed, flags.p, st.p, hsh.p, cid.p, s));
+            hipLaunchKernelGGL(k_root_flags, dim3(g), dim3(kBlock), 0, s, n, st.p, cid.p, L.roots, flag_by_cid.p);
+            hipLaunchKernelGGL(k_set_last, dim3(1), dim3(1), 0, s, flag_by_cid.p, n);
+            DPCG_TRY(exclusive_scan_i32(flag_by_cid.p, rank.p, n + 1, s));
             int32_t nc32 = 0;
-            DPCG_TRY(read1(rank + n, &nc32, s));
+            DPCG_TRY(fetch(&nc32, rank.p + n, 1, s));
             nc = nc32;
             if (nc <= 0 || (double)nc > 0.9 * (double)n) coarsest = true;      // coarsening stalls
             pt.mark("amg: strength + MIS(2)");
@@ -1153,20 +1114,20 @@ int build(dpcg_system *h, AmgState &S, AmgState *old, hipStream_t s) {
         }
         L.nc = nc;
         // aggregates
-        int32_t *agg1 = nullptr;
-        DPCG_TRY(t.alloc(&agg1, n));
+        DevBuf<int32_t> agg1;
+        DPCG_TRY(agg1.alloc(n));
         DPCG_TRY(dev_alloc(&L.agg, n));
-        hipLaunchKernelGGL(k_agg_near, dim3(g), dim3(kBlock), 0, s, n, L.A.rowptr, L.A.col, L.strong, L.roots, cid, rank, agg1);
-        DPCG_HIP(hipMemsetAsync(flags, 0, sizeof(int), s));
-        hipLaunchKernelGGL(k_agg_far, dim3(g), dim3(kBlock), 0, s, n, L.A.rowptr, L.A.col, L.A.val, L.strong, cid, agg1, L.agg, flags);
-        DPCG_TRY(read1(flags, &bad, s));
+        hipLaunchKernelGGL(k_agg_near, dim3(g), dim3(kBlock), 0, s, n, L.A.rowptr, L.A.col, L.strong, L.roots, cid.p, rank.p, agg1.p);
+        DPCG_HIP(hipMemsetAsync(flags.p, 0, sizeof(int), s));
+        hipLaunchKernelGGL(k_agg_far, dim3(g), dim3(kBlock), 0, s, n, L.A.rowptr, L.A.col, L.A.val, L.strong, cid.p, agg1.p, L.agg, flags.p);
+        DPCG_TRY(fetch(&bad, flags.p, 1, s));
         if (bad) return level_error(DPCG_ERR_STATE, l, "a row was left without an aggregate");
         bool same = false;
         if (O && O->agg && O->nc == nc && O->P.rowptr) {
-            DPCG_HIP(hipMemsetAsync(flags, 0, sizeof(int), s));
-            hipLaunchKernelGGL(k_diff_i32, dim3(g), dim3(kBlock), 0, s, n, L.agg, O->agg, flags);
+            DPCG_HIP(hipMemsetAsync(flags.p, 0, sizeof(int), s));
+            hipLaunchKernelGGL(k_diff_i32, dim3(g), dim3(kBlock), 0, s, n, L.agg, O->agg, flags.p);
             int diff = 1;
-            DPCG_TRY(read1(flags, &diff, s));
+            DPCG_TRY(fetch(&diff, flags.p, 1, s));
             same = diff == 0 && l + 1 < (int)old->lv.size() && old->lv[l + 1].A.rowptr;
         }
         if (same) {                                 // the pattern of P, A P, P^T and A_{l+1} is the parked one: values only
@@ -1180,17 +1141,19 @@ int build(dpcg_system *h, AmgState &S, AmgState *old, hipStream_t s) {
             reuse = false;
         }
         // tentative prolongator and the spectral radius of D^-1 A
-        CsrDev T;
-        int32_t *size = nullptr;
-        DPCG_TRY(t.alloc(&size, nc));
-        DPCG_TRY(t.alloc(&T.rowptr, n + 1));
-        DPCG_TRY(t.alloc(&T.col, n));
-        DPCG_TRY(t.alloc(&T.val, n));
+        CsrOwner t_owner;
+        CsrDev &T = t_owner.c;
+        DevBuf<int32_t> size;
+        DPCG_TRY(size.alloc(nc));
+        T.owned = true;
+        DPCG_TRY(dev_alloc(&T.rowptr, n + 1));
+        DPCG_TRY(dev_alloc(&T.col, n));
+        DPCG_TRY(dev_alloc(&T.val, n));
         T.n = n;
         T.nnz = n;
-        DPCG_HIP(hipMemsetAsync(size, 0, (size_t)nc * sizeof(int32_t), s));
-        hipLaunchKernelGGL(k_agg_size, dim3(g), dim3(kBlock), 0, s, n, L.agg, size);
-        hipLaunchKernelGGL(k_tentative, dim3(grid_of(n + 1)), dim3(kBlock), 0, s, n, L.agg, size, T.rowptr, T.col, T.val);
+        DPCG_HIP(hipMemsetAsync(size.p, 0, (size_t)nc * sizeof(int32_t), s));
+        hipLaunchKernelGGL(k_agg_size, dim3(g), dim3(kBlock), 0, s, n, L.agg, size.p);
+        hipLaunchKernelGGL(k_tentative, dim3(grid_blocks(n + 1, kAmgGrid)), dim3(kBlock), 0, s, n, L.agg, size.p, T.rowptr, T.col, T.val);
         pt.mark("amg: aggregates");
         DPCG_TRY(estimate_rho(L.A, l == 0 ? h->perm : nullptr, S.seed, &L.rho, s));
         L.omega = (4.0 / 3.0) / L.rho;
@@ -1411,7 +1374,7 @@ int apply_cycle(AmgState &S, const double *r, double *z, hipStream_t s, double *
         else level_down<W, W>(S.lv[l], nu, LevelView<W>(S.lv[l]).b, bnext, x[l], alt[l], s, done);
     }
     const LevelView<W> C(S.lv[Lc]);
-    hipLaunchKernelGGL(k_amg_gemv<W>, dim3(grid_of(S.nco * 64)), dim3(kBlock), 0, s, S.nco, S.cinv, (const W *)C.b, C.xa, done);
+    hipLaunchKernelGGL(k_amg_gemv<W>, dim3(grid_blocks(S.nco * 64, kAmgGrid)), dim3(kBlock), 0, s, S.nco, S.cinv, (const W *)C.b, C.xa, done);
     const W *xcoarse = C.xa;
     for (int l = Lc - 1; l >= 0; --l) {               // up: prolongation with correction, post-smoothing
         if (l == 0) xcoarse = level_up<W, true>(S.lv[l], nu, r, xcoarse, x[l], alt[l], z, part_rz, n_part_rz, s, done);
@@ -1430,7 +1393,7 @@ int amg_apply(dpcg_system *h, const double *r, double *z, hipStream_t s, double 
     AmgState &S = *h->amg;
     if (n_part_rz) *n_part_rz = 0;
     if (S.lv.size() == 1) {                           // (one level: the dense inverse alone, fp64 in either precision)
-        hipLaunchKernelGGL(k_amg_gemv<double>, dim3(grid_of(S.nco * 64)), dim3(kBlock), 0, s, S.nco, S.cinv, r, z, done);
+        hipLaunchKernelGGL(k_amg_gemv<double>, dim3(grid_blocks(S.nco * 64, kAmgGrid)), dim3(kBlock), 0, s, S.nco, S.cinv, r, z, done);
         return DPCG_OK;
     }
     if (S.precision == DPCG_AMG_FP32) return apply_cycle<float>(S, r, z, s, part_rz, n_part_rz, done);

@@ -1,16 +1,14 @@
-// Structural analysis of triangular factors on the device (setup of LLT_SOLVE / IC(0)): validation, transpose, level
-// sets, level-ordered copies, LDS-ring records.  Integer work on data that already lives in HBM -- a factor that comes
-// "straight from the CNN" (dpcg_set_precond_llt with DEVICE pointers) never crosses PCIe.  Sort / scan come from
-// dpcg_prims.h; everything else is a plain kernel.
+// Structural analysis of triangular factors on the device (setup of LLT_SOLVE / IC(0)): validation, level sets,
+// level-ordered copies, LDS-ring records.  Integer work on data that already lives in HBM -- a factor that comes
+// "straight from the CNN" (dpcg_set_precond_llt with DEVICE pointers) never crosses PCIe.  Sort / scan, the generic index
+// kernels and the transpose come from dpcg_prims.h; everything else is a plain kernel.
 #include "dpcg_device.h"
+#include "dpcg_host.h"
 
 namespace dpcg {
 
 namespace {
-inline int grid_rows(int64_t n, int cap = 8192) {
-    int64_t g = (n + kBlock - 1) / kBlock;
-    return (int)(g < 1 ? 1 : (g > cap ? cap : g));
-}
+constexpr int kAnalysisGrid = 8192;   // most workgroups of an analysis kernel (the ones that poll or use atomics pass 1024)
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------
@@ -36,29 +34,7 @@ __global__ __launch_bounds__(kBlock) void k_check_lower(int64_t n, const int32_t
 }
 
 void launch_check_lower(const CsrDev &L, int *flags, hipStream_t s) {
-    hipLaunchKernelGGL(k_check_lower, dim3(grid_rows(L.n)), dim3(kBlock), 0, s, L.n, L.rowptr, L.col, L.val, flags);
-}
-
-// ------------------------------------------------------------------------------------------------
-// transpose pieces
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kBlock) void k_row_of(int64_t n, const int32_t *__restrict__ rp, int32_t *__restrict__ row_of) {
-    const int64_t stride = (int64_t)gridDim.x * kBlock;
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride)
-        for (int k = rp[i]; k < rp[i + 1]; ++k) row_of[k] = (int32_t)i;
-}
-
-void launch_row_of(int64_t n, const int32_t *rp, int32_t *row_of, hipStream_t s) {
-    hipLaunchKernelGGL(k_row_of, dim3(grid_rows(n)), dim3(kBlock), 0, s, n, rp, row_of);
-}
-
-__global__ __launch_bounds__(kBlock) void k_iota(int64_t count, int32_t *__restrict__ out) {
-    const int64_t stride = (int64_t)gridDim.x * kBlock;
-    for (int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x; k < count; k += stride) out[k] = (int32_t)k;
-}
-
-void launch_iota(int64_t count, int32_t *out, hipStream_t s) {
-    hipLaunchKernelGGL(k_iota, dim3(grid_rows(count)), dim3(kBlock), 0, s, count, out);
+    hipLaunchKernelGGL(k_check_lower, dim3(grid_blocks(L.n, kAnalysisGrid)), dim3(kBlock), 0, s, L.n, L.rowptr, L.col, L.val, flags);
 }
 
 // key64[i] = level[i] << 32 | (order_by ? order_by[i] : i): rows sorted by it are grouped by level and, inside a level, ordered
@@ -95,48 +71,14 @@ __global__ __launch_bounds__(kBlock) void k_reverse_levels(int64_t n, const int3
 
 void launch_reverse_levels(int64_t n, const int32_t *rows_lo, const uint32_t *lvl_lo, const int32_t *level_ptr_lo, int nl,
                            int32_t *rows_up, uint32_t *lvl_up, hipStream_t s) {
-    hipLaunchKernelGGL(k_reverse_levels, dim3(grid_rows(n)), dim3(kBlock), 0, s, n, rows_lo, lvl_lo, level_ptr_lo, nl, rows_up, lvl_up);
+    hipLaunchKernelGGL(k_reverse_levels, dim3(grid_blocks(n, kAnalysisGrid)), dim3(kBlock), 0, s, n, rows_lo, lvl_lo, level_ptr_lo, nl, rows_up, lvl_up);
 }
 
 void launch_level_keys(int64_t n, const int32_t *level, const int32_t *order_by, uint64_t *key, hipStream_t s) {
-    hipLaunchKernelGGL(k_level_keys, dim3(grid_rows(n)), dim3(kBlock), 0, s, n, level, order_by, key);
+    hipLaunchKernelGGL(k_level_keys, dim3(grid_blocks(n, kAnalysisGrid)), dim3(kBlock), 0, s, n, level, order_by, key);
 }
 void launch_key_levels(int64_t n, const uint64_t *key_sorted, uint32_t *lvl, hipStream_t s) {
-    hipLaunchKernelGGL(k_key_levels, dim3(grid_rows(n)), dim3(kBlock), 0, s, n, key_sorted, lvl);
-}
-
-// Offsets of the groups of a SORTED key array: ptr[g] = first position with key >= g, for g = 0..groups (ptr[groups] =
-// count).  Empty groups get the offset of the next non-empty one.
-__global__ __launch_bounds__(kBlock) void k_group_offsets(int64_t count, const uint32_t *__restrict__ keys, int groups,
-                                                          int32_t *__restrict__ ptr) {
-    const int64_t stride = (int64_t)gridDim.x * kBlock;
-    for (int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x; k <= count; k += stride) {
-        const int64_t lo = k == 0 ? 0 : (int64_t)keys[k - 1] + 1;
-        const int64_t hi = k == count ? groups : (int64_t)keys[k];
-        for (int64_t g = lo; g <= hi; ++g) ptr[g] = (int32_t)k;
-    }
-}
-
-void launch_group_offsets(int64_t count, const uint32_t *keys_sorted, int groups, int32_t *ptr, hipStream_t s) {
-    hipLaunchKernelGGL(k_group_offsets, dim3(grid_rows(count + 1)), dim3(kBlock), 0, s, count, keys_sorted, groups, ptr);
-}
-
-// Entries of the transposed matrix from the sort permutation: tcol[d] = row_of[perm[d]], tval[d] = val[perm[d]].
-__global__ __launch_bounds__(kBlock) void k_transpose_gather(int64_t nnz, const int32_t *__restrict__ perm,
-                                                             const int32_t *__restrict__ row_of,
-                                                             const double *__restrict__ val, int32_t *__restrict__ tcol,
-                                                             double *__restrict__ tval) {
-    const int64_t stride = (int64_t)gridDim.x * kBlock;
-    for (int64_t d = (int64_t)blockIdx.x * kBlock + threadIdx.x; d < nnz; d += stride) {
-        const int32_t k = perm[d];
-        tcol[d] = row_of[k];
-        tval[d] = val[k];
-    }
-}
-
-void launch_transpose_gather(int64_t nnz, const int32_t *perm, const int32_t *row_of, const double *val, int32_t *tcol,
-                             double *tval, hipStream_t s) {
-    hipLaunchKernelGGL(k_transpose_gather, dim3(grid_rows(nnz)), dim3(kBlock), 0, s, nnz, perm, row_of, val, tcol, tval);
+    hipLaunchKernelGGL(k_key_levels, dim3(grid_blocks(n, kAnalysisGrid)), dim3(kBlock), 0, s, n, key_sorted, lvl);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -224,7 +166,7 @@ __global__ __launch_bounds__(kBlock) void k_strip_keys(int64_t n, const int32_t 
 }
 
 void launch_strip_keys(int64_t n, const int32_t *level, StripMap map, int nlev, bool upper, uint32_t *key, hipStream_t s) {
-    hipLaunchKernelGGL(k_strip_keys, dim3(grid_rows(n)), dim3(kBlock), 0, s, n, level, map, nlev, upper ? 1 : 0, key);
+    hipLaunchKernelGGL(k_strip_keys, dim3(grid_blocks(n, kAnalysisGrid)), dim3(kBlock), 0, s, n, level, map, nlev, upper ? 1 : 0, key);
 }
 
 // Records of the strip solve, one per position j of the (strip, level, row) order:
@@ -346,7 +288,7 @@ __global__ __launch_bounds__(kBlock) void k_ic0_cross_terms(int64_t n, const int
 }
 
 void launch_ic0_cross_terms(int64_t n, const int32_t *rp, const int32_t *ci, int *flags_zeroed, hipStream_t s) {
-    hipLaunchKernelGGL(k_ic0_cross_terms, dim3(grid_rows(n, 1024)), dim3(kBlock), 0, s, n, rp, ci, flags_zeroed);
+    hipLaunchKernelGGL(k_ic0_cross_terms, dim3(grid_blocks(n, 1024)), dim3(kBlock), 0, s, n, rp, ci, flags_zeroed);
 }
 
 // Descriptors of the general factorisation through the ring walk (k_sptrsv_ring_pipe, FACTOR = 2), per level-order position j
@@ -387,7 +329,7 @@ __global__ __launch_bounds__(kBlock) void k_ring_factor_desc(int64_t n, const in
 
 void launch_ring_factor_desc(int64_t n, const int32_t *lo_rp, const int32_t *lo_ci, const int32_t *lo_cp, const double *colnorm,
                              double tau, int32_t *xdesc, double *thr, hipStream_t s) {
-    hipLaunchKernelGGL(k_ring_factor_desc, dim3(grid_rows(n, 1024)), dim3(kBlock), 0, s, n, lo_rp, lo_ci, lo_cp, colnorm, tau, xdesc,
+    hipLaunchKernelGGL(k_ring_factor_desc, dim3(grid_blocks(n, 1024)), dim3(kBlock), 0, s, n, lo_rp, lo_ci, lo_cp, colnorm, tau, xdesc,
                        colnorm ? thr : nullptr);
 }
 
@@ -411,19 +353,19 @@ __global__ __launch_bounds__(kBlock) void k_points_along_band(int64_t n, const i
 }
 
 void launch_points_along_band(int64_t n, const int32_t *rp, const int32_t *ci, bool upper, int band, int *flag_zeroed, hipStream_t s) {
-    hipLaunchKernelGGL(k_points_along_band, dim3(grid_rows(n, 1024)), dim3(kBlock), 0, s, n, rp, ci, upper ? 1 : 0, band, flag_zeroed);
+    hipLaunchKernelGGL(k_points_along_band, dim3(grid_blocks(n, 1024)), dim3(kBlock), 0, s, n, rp, ci, upper ? 1 : 0, band, flag_zeroed);
 }
 
 void launch_max_band(int64_t n, const int32_t *rp, const int32_t *ci, bool upper, int *out_dev, hipStream_t s) {
-    hipLaunchKernelGGL(k_max_band, dim3(grid_rows(n, 1024)), dim3(kBlock), 0, s, n, rp, ci, upper ? 1 : 0, out_dev);
+    hipLaunchKernelGGL(k_max_band, dim3(grid_blocks(n, 1024)), dim3(kBlock), 0, s, n, rp, ci, upper ? 1 : 0, out_dev);
 }
 
 void launch_strip_records(int64_t n, const uint32_t *key_of_pos, int nlev, const int32_t *level_ptr, const int32_t *rows,
                           const int32_t *lo_rp, const int32_t *lo_ci, const int32_t *lo_cp, const double *lo_v, bool upper,
                           int ring_reach, int32_t *meta, double *pv, int32_t *exported_zeroed, int *stats, hipStream_t s) {
-    hipLaunchKernelGGL(k_strip_records, dim3(grid_rows(n, 1024)), dim3(kBlock), 0, s, n, key_of_pos, nlev, level_ptr, rows, lo_rp,
+    hipLaunchKernelGGL(k_strip_records, dim3(grid_blocks(n, 1024)), dim3(kBlock), 0, s, n, key_of_pos, nlev, level_ptr, rows, lo_rp,
                        lo_ci, lo_cp, lo_v, upper ? 1 : 0, ring_reach, meta, pv, exported_zeroed, stats);
-    hipLaunchKernelGGL(k_strip_mark_exported, dim3(grid_rows(n, 1024)), dim3(kBlock), 0, s, n, exported_zeroed, meta);
+    hipLaunchKernelGGL(k_strip_mark_exported, dim3(grid_blocks(n, 1024)), dim3(kBlock), 0, s, n, exported_zeroed, meta);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -445,7 +387,7 @@ __global__ __launch_bounds__(kBlock) void k_lo_lengths(int64_t n, const int32_t 
 }
 
 void launch_lo_lengths(int64_t n, const int32_t *rows, const int32_t *rp, int32_t *len, int32_t *pos, hipStream_t s) {
-    hipLaunchKernelGGL(k_lo_lengths, dim3(grid_rows(n + 1)), dim3(kBlock), 0, s, n, rows, rp, len, pos);
+    hipLaunchKernelGGL(k_lo_lengths, dim3(grid_blocks(n + 1, kAnalysisGrid)), dim3(kBlock), 0, s, n, rows, rp, len, pos);
 }
 
 // (a workgroup copies the entries of kBlock consecutive level-ordered rows: they are contiguous in the copy, so its lanes walk them
@@ -487,7 +429,7 @@ __global__ __launch_bounds__(kBlock) void k_lo_copy(int64_t n, const int32_t *__
 void launch_lo_copy(int64_t n, const int32_t *rows, const int32_t *rp, const int32_t *ci, const double *v,
                     const int32_t *pos, const int32_t *lo_rp, int32_t *lo_ci, int32_t *lo_cp, double *lo_v,
                     hipStream_t s) {
-    hipLaunchKernelGGL(k_lo_copy, dim3(grid_rows(n)), dim3(kBlock), 0, s, n, rows, rp, ci, v, pos, lo_rp, lo_ci, lo_cp,
+    hipLaunchKernelGGL(k_lo_copy, dim3(grid_blocks(n, kAnalysisGrid)), dim3(kBlock), 0, s, n, rows, rp, ci, v, pos, lo_rp, lo_ci, lo_cp,
                        lo_v);
 }
 
@@ -507,7 +449,7 @@ __global__ __launch_bounds__(kBlock) void k_stream_fit(int64_t n, const uint32_t
 
 void launch_stream_fit(int64_t n, const uint32_t *lvl_of_pos, const int32_t *level_ptr, const int32_t *lo_rp, int *flag,
                        hipStream_t s) {
-    hipLaunchKernelGGL(k_stream_fit, dim3(grid_rows(n)), dim3(kBlock), 0, s, n, lvl_of_pos, level_ptr, lo_rp, flag);
+    hipLaunchKernelGGL(k_stream_fit, dim3(grid_blocks(n, kAnalysisGrid)), dim3(kBlock), 0, s, n, lvl_of_pos, level_ptr, lo_rp, flag);
 }
 
 // For the rows of merged segments: how far back (in level order, within the segment) does a row reach?
@@ -549,7 +491,7 @@ __global__ __launch_bounds__(kBlock) void k_ring_reach(int64_t n, const uint32_t
 
 void launch_ring_reach(int64_t n, const uint32_t *lvl_of_pos, const int32_t *seg_of_level, const int32_t *seg_start,
                        const int32_t *lo_rp, const int32_t *lo_cp, int32_t *maxdist, hipStream_t s) {
-    hipLaunchKernelGGL(k_ring_reach, dim3(grid_rows(n)), dim3(kBlock), 0, s, n, lvl_of_pos, seg_of_level, seg_start, lo_rp,
+    hipLaunchKernelGGL(k_ring_reach, dim3(grid_blocks(n, kAnalysisGrid)), dim3(kBlock), 0, s, n, lvl_of_pos, seg_of_level, seg_start, lo_rp,
                        lo_cp, maxdist);
 }
 
@@ -595,7 +537,7 @@ __global__ __launch_bounds__(kBlock) void k_ring_records(int64_t n, const uint32
 void launch_ring_records(int64_t n, const uint32_t *lvl_of_pos, const int32_t *ring_start_of_level, const int32_t *rows,
                          const int32_t *lo_rp, const int32_t *lo_ci, const int32_t *lo_cp, const double *lo_v,
                          int32_t *meta, double *pv, hipStream_t s) {
-    hipLaunchKernelGGL(k_ring_records, dim3(grid_rows(n)), dim3(kBlock), 0, s, n, lvl_of_pos, ring_start_of_level, rows,
+    hipLaunchKernelGGL(k_ring_records, dim3(grid_blocks(n, kAnalysisGrid)), dim3(kBlock), 0, s, n, lvl_of_pos, ring_start_of_level, rows,
                        lo_rp, lo_ci, lo_cp, lo_v, meta, pv);
 }
 
@@ -639,33 +581,14 @@ __global__ __launch_bounds__(kBlock) void k_sf_records(int64_t n, const int32_t 
     }
 }
 
-__global__ __launch_bounds__(kBlock) void k_invert_positions(int64_t n, const int32_t *__restrict__ rows, int32_t *__restrict__ pos) {
-    const int64_t stride = (int64_t)gridDim.x * kBlock;
-    for (int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x; j < n; j += stride) pos[rows[j]] = (int32_t)j;
-}
-
-void launch_invert_positions(int64_t n, const int32_t *rows, int32_t *pos, hipStream_t s) {
-    hipLaunchKernelGGL(k_invert_positions, dim3(grid_rows(n)), dim3(kBlock), 0, s, n, rows, pos);
-}
-
-__global__ __launch_bounds__(kBlock) void k_compose_positions(int64_t n, const int32_t *__restrict__ rows,
-                                                              const int32_t *__restrict__ pos, int32_t *__restrict__ out) {
-    const int64_t stride = (int64_t)gridDim.x * kBlock;
-    for (int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x; j < n; j += stride) out[j] = pos[rows[j]];
-}
-
-void launch_compose_positions(int64_t n, const int32_t *rows, const int32_t *pos, int32_t *out, hipStream_t s) {
-    hipLaunchKernelGGL(k_compose_positions, dim3(grid_rows(n)), dim3(kBlock), 0, s, n, rows, pos, out);
-}
-
 void launch_sf_records(int64_t n, const int32_t *rows, const int32_t *lo_rp, const int32_t *lo_ci, const double *lo_v,
                        bool upper, int32_t *meta, double *pv, int width, hipStream_t s) {
     if (width == 14)
-        hipLaunchKernelGGL(k_sf_records<14>, dim3(grid_rows(n)), dim3(kBlock), 0, s, n, rows, lo_rp, lo_ci, lo_v, upper ? 1 : 0, meta, pv);
+        hipLaunchKernelGGL(k_sf_records<14>, dim3(grid_blocks(n, kAnalysisGrid)), dim3(kBlock), 0, s, n, rows, lo_rp, lo_ci, lo_v, upper ? 1 : 0, meta, pv);
     else if (width == 6)
-        hipLaunchKernelGGL(k_sf_records<6>, dim3(grid_rows(n)), dim3(kBlock), 0, s, n, rows, lo_rp, lo_ci, lo_v, upper ? 1 : 0, meta, pv);
+        hipLaunchKernelGGL(k_sf_records<6>, dim3(grid_blocks(n, kAnalysisGrid)), dim3(kBlock), 0, s, n, rows, lo_rp, lo_ci, lo_v, upper ? 1 : 0, meta, pv);
     else
-        hipLaunchKernelGGL(k_sf_records<3>, dim3(grid_rows(n)), dim3(kBlock), 0, s, n, rows, lo_rp, lo_ci, lo_v, upper ? 1 : 0, meta, pv);
+        hipLaunchKernelGGL(k_sf_records<3>, dim3(grid_blocks(n, kAnalysisGrid)), dim3(kBlock), 0, s, n, rows, lo_rp, lo_ci, lo_v, upper ? 1 : 0, meta, pv);
 }
 
 // *counter += rows of the level-ordered copy with more than `limit` off-diagonal entries (one atomic per wave)
@@ -678,7 +601,7 @@ __global__ __launch_bounds__(kBlock) void k_count_long_rows(int64_t n, const int
 }
 
 void launch_count_long_rows(int64_t n, const int32_t *lo_rp, int limit, int *counter, hipStream_t s) {
-    hipLaunchKernelGGL(k_count_long_rows, dim3(grid_rows(n)), dim3(kBlock), 0, s, n, lo_rp, limit, counter);
+    hipLaunchKernelGGL(k_count_long_rows, dim3(grid_blocks(n, kAnalysisGrid)), dim3(kBlock), 0, s, n, lo_rp, limit, counter);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -726,7 +649,7 @@ __global__ __launch_bounds__(kBlock) void k_tril_count(int64_t n, const int32_t 
 }
 
 void launch_tril_count(int64_t n, const int32_t *rp, const int32_t *ci, int32_t *cnt, int *flag, hipStream_t s) {
-    hipLaunchKernelGGL(k_tril_count, dim3(grid_rows(n)), dim3(kBlock), 0, s, n, rp, ci, cnt, flag);
+    hipLaunchKernelGGL(k_tril_count, dim3(grid_blocks(n, kAnalysisGrid)), dim3(kBlock), 0, s, n, rp, ci, cnt, flag);
 }
 
 __global__ __launch_bounds__(kBlock) void k_tril_copy(int64_t n, const int32_t *__restrict__ rp,
@@ -760,14 +683,14 @@ __global__ __launch_bounds__(kBlock) void k_iota_f64(int64_t count, double *out)
     for (int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x; k < count; k += stride) out[k] = (double)k;
 }
 void launch_iota_f64(int64_t count, double *out, hipStream_t s) {
-    hipLaunchKernelGGL(k_iota_f64, dim3(grid_rows(count)), dim3(kBlock), 0, s, count, out);
+    hipLaunchKernelGGL(k_iota_f64, dim3(grid_blocks(count, kAnalysisGrid)), dim3(kBlock), 0, s, count, out);
 }
 __global__ __launch_bounds__(kBlock) void k_f64_to_i32(int64_t count, const double *__restrict__ in, int32_t *__restrict__ out) {
     const int64_t stride = (int64_t)gridDim.x * kBlock;
     for (int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x; k < count; k += stride) out[k] = (int32_t)in[k];
 }
 void launch_f64_to_i32(int64_t count, const double *in, int32_t *out, hipStream_t s) {
-    hipLaunchKernelGGL(k_f64_to_i32, dim3(grid_rows(count)), dim3(kBlock), 0, s, count, in, out);
+    hipLaunchKernelGGL(k_f64_to_i32, dim3(grid_blocks(count, kAnalysisGrid)), dim3(kBlock), 0, s, count, in, out);
 }
 // the values of the level-ordered copy again: position j holds factor row rows[j], entries in the row's own order (k_lo_copy)
 __global__ __launch_bounds__(kBlock) void k_lo_values(int64_t n, const int32_t *__restrict__ rows, const int32_t *__restrict__ rp,
@@ -782,12 +705,12 @@ __global__ __launch_bounds__(kBlock) void k_lo_values(int64_t n, const int32_t *
 }
 void launch_lo_values(int64_t n, const int32_t *rows, const int32_t *rp, const double *v, const int32_t *lo_rp, double *lo_v,
                       hipStream_t s) {
-    hipLaunchKernelGGL(k_lo_values, dim3(grid_rows(n)), dim3(kBlock), 0, s, n, rows, rp, v, lo_rp, lo_v);
+    hipLaunchKernelGGL(k_lo_values, dim3(grid_blocks(n, kAnalysisGrid)), dim3(kBlock), 0, s, n, rows, rp, v, lo_rp, lo_v);
 }
 
 void launch_tril_copy(int64_t n, const int32_t *rp, const int32_t *ci, const double *v, const int32_t *lrp, int32_t *lci,
                       double *lv, hipStream_t s) {
-    hipLaunchKernelGGL(k_tril_copy, dim3(grid_rows(n)), dim3(kBlock), 0, s, n, rp, ci, v, lrp, lci, lv);
+    hipLaunchKernelGGL(k_tril_copy, dim3(grid_blocks(n, kAnalysisGrid)), dim3(kBlock), 0, s, n, rp, ci, v, lrp, lci, lv);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -807,7 +730,7 @@ __global__ __launch_bounds__(kBlock) void k_colnorm1(int64_t n, const int32_t *_
 }
 
 void launch_colnorm1(int64_t n, const int32_t *rp, const int32_t *ci, const double *v, double *c, hipStream_t s) {
-    hipLaunchKernelGGL(k_colnorm1, dim3(grid_rows(n)), dim3(kBlock), 0, s, n, rp, ci, v, c);
+    hipLaunchKernelGGL(k_colnorm1, dim3(grid_blocks(n, kAnalysisGrid)), dim3(kBlock), 0, s, n, rp, ci, v, c);
 }
 
 // Pattern of row i with level-1 fill: tril(A)_i plus every j < i that shares a neighbour k < j with i.  One thread per
@@ -881,9 +804,9 @@ __global__ __launch_bounds__(kBlock) void k_ict_pattern(int64_t n, const int32_t
 void launch_ict_pattern(bool write, int64_t n, const int32_t *rp, const int32_t *ci, const double *v, int fill, int32_t *cnt,
                         const int32_t *lrp, int32_t *lci, double *lv, int *flags, hipStream_t s) {
     if (write)
-        hipLaunchKernelGGL(k_ict_pattern<true>, dim3(grid_rows(n + 1)), dim3(kBlock), 0, s, n, rp, ci, v, fill, cnt, lrp, lci, lv, flags);
+        hipLaunchKernelGGL(k_ict_pattern<true>, dim3(grid_blocks(n + 1, kAnalysisGrid)), dim3(kBlock), 0, s, n, rp, ci, v, fill, cnt, lrp, lci, lv, flags);
     else
-        hipLaunchKernelGGL(k_ict_pattern<false>, dim3(grid_rows(n + 1)), dim3(kBlock), 0, s, n, rp, ci, v, fill, cnt, lrp, lci, lv, flags);
+        hipLaunchKernelGGL(k_ict_pattern<false>, dim3(grid_blocks(n + 1, kAnalysisGrid)), dim3(kBlock), 0, s, n, rp, ci, v, fill, cnt, lrp, lci, lv, flags);
 }
 
 // compaction after the numeric phase: dropped entries are stored zeros; the diagonal always stays
@@ -914,11 +837,11 @@ __global__ __launch_bounds__(kBlock) void k_copy_kept(int64_t n, const int32_t *
 }
 
 void launch_count_kept(int64_t n, const int32_t *rp, const int32_t *ci, const double *v, int32_t *cnt, hipStream_t s) {
-    hipLaunchKernelGGL(k_count_kept, dim3(grid_rows(n + 1)), dim3(kBlock), 0, s, n, rp, ci, v, cnt);
+    hipLaunchKernelGGL(k_count_kept, dim3(grid_blocks(n + 1, kAnalysisGrid)), dim3(kBlock), 0, s, n, rp, ci, v, cnt);
 }
 void launch_copy_kept(int64_t n, const int32_t *rp, const int32_t *ci, const double *v, const int32_t *orp, int32_t *oci,
                       double *ov, hipStream_t s) {
-    hipLaunchKernelGGL(k_copy_kept, dim3(grid_rows(n)), dim3(kBlock), 0, s, n, rp, ci, v, orp, oci, ov);
+    hipLaunchKernelGGL(k_copy_kept, dim3(grid_blocks(n, kAnalysisGrid)), dim3(kBlock), 0, s, n, rp, ci, v, orp, oci, ov);
 }
 
 }  // namespace dpcg

@@ -13,6 +13,7 @@
 // on the handle across dpcg_update_values; the next attach with the same ids computes only values.
 #include <climits>
 #include <cstring>
+#include <memory>
 
 #include "dpcg_host.h"
 #include "dpcg_prims.h"
@@ -20,6 +21,7 @@
 namespace dpcg {
 constexpr int kBicMaxRows = 4096;      // rows of a block: its slice of the vector is one LDS array of doubles (32 KiB)
 constexpr int kBicSetupThreads = 256;  // workgroup of the setup kernels (levels, values)
+constexpr int kBicGrid = 4096;         // most workgroups of a setup kernel that strides over rows
 
 struct BicSide {                       // one triangular factor as the solve kernel reads it
     int32_t *nlev = nullptr;           // [nblocks] levels of a block
@@ -48,21 +50,6 @@ struct BlockIc {
 }  // namespace dpcg
 
 namespace {
-template <typename T>
-struct Buf {
-    T *p = nullptr;
-    Buf() = default;
-    Buf(const Buf &) = delete;
-    Buf &operator=(const Buf &) = delete;
-    ~Buf() { dev_free(p); }
-    int alloc(int64_t count) { dev_free(p); return dev_alloc(&p, count); }
-};
-
-int rows_grid(int64_t count) {
-    const int64_t g = (count + kBlock - 1) / kBlock;
-    return (int)std::min<int64_t>(std::max<int64_t>(g, 1), 4096);
-}
-
 void free_side(BicSide &s) {
     dev_free(s.nlev); dev_free(s.lvl_ptr); dev_free(s.row); dev_free(s.e_ptr); dev_free(s.e_col); dev_free(s.e_src); dev_free(s.d_src);
     dev_free(s.e_val); dev_free(s.diag);
@@ -79,12 +66,6 @@ __global__ __launch_bounds__(kBlock) void k_bic_check_ids(int64_t n, const int32
     const int64_t stride = (int64_t)gridDim.x * kBlock;
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride)
         if (ids[i] < 0) atomicMin(flags, (int)i);
-}
-
-__global__ __launch_bounds__(kBlock) void k_bic_ids_differ(int64_t n, const int32_t *__restrict__ a, const int32_t *__restrict__ b, int *flag) {
-    const int64_t stride = (int64_t)gridDim.x * kBlock;
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride)
-        if (a[i] != b[i]) *flag = 1;
 }
 
 // head[k] = 1 where a new block begins at sorted position k > 0 (the inclusive scan of it is the block's index)
@@ -140,12 +121,6 @@ __global__ __launch_bounds__(kBlock) void k_bic_tril(int64_t n, const int32_t *_
             if (!diag) atomicMin(flags + 1, i);
         }
     }
-}
-
-__global__ __launch_bounds__(kBlock) void k_bic_transpose_cols(int64_t nnz, const int32_t *__restrict__ order, const int32_t *__restrict__ row_of,
-                                                               int32_t *__restrict__ tci) {
-    const int64_t stride = (int64_t)gridDim.x * kBlock;
-    for (int64_t d = (int64_t)blockIdx.x * kBlock + threadIdx.x; d < nnz; d += stride) tci[d] = row_of[order[d]];
 }
 
 // The level sets of one block of a triangular factor and its level-ordered copy: one workgroup per block.  Round t gives level t to
@@ -312,12 +287,6 @@ __global__ __launch_bounds__(kBicSetupThreads) void k_bic_dic(const int32_t *__r
     }
 }
 
-__global__ __launch_bounds__(kBlock) void k_bic_gather(int64_t count, const int32_t *__restrict__ src, const double *__restrict__ in,
-                                                       double *__restrict__ out) {
-    const int64_t stride = (int64_t)gridDim.x * kBlock;
-    for (int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x; k < count; k += stride) out[k] = in[src[k]];
-}
-
 // ---- the apply ---------------------------------------------------------------------------------------------------------------------
 struct BicApply {
     const int32_t *blk_ptr, *hperm;
@@ -431,127 +400,119 @@ int bic_handle_map(dpcg_system *h, BlockIc *c, hipStream_t s) {
 // The symbolic phase: numbering, tril(A_B) and its transpose, level sets and level-ordered copies.  ids: on the device, taken over.
 int bic_symbolic(dpcg_system *h, const CsrDev &A, int32_t *ids_dev, BlockIc **out, hipStream_t s) {
     const int64_t n = A.n;
-    BlockIc *c = new BlockIc();
+    std::unique_ptr<BlockIc, void (*)(BlockIc *)> c(new BlockIc(), free_bic);
     c->n = n;
     c->ids = ids_dev;
-    auto fail = [&](int st) { free_bic(c); return st; };
-    int st = DPCG_OK;
-    Buf<int> flags;
-    Buf<int32_t> iota, head, pos, cnt;
-    Buf<uint32_t> keys_sorted;
-    if ((st = flags.alloc(8)) < 0 || (st = iota.alloc(n)) < 0 || (st = head.alloc(n)) < 0 || (st = pos.alloc(n)) < 0 ||
-        (st = cnt.alloc(n + 1)) < 0 || (st = keys_sorted.alloc(n)) < 0 || (st = dev_alloc(&c->perm_c, n)) < 0)
-        return fail(st);
+    DevBuf<int> flags;
+    DevBuf<int32_t> iota, head, pos, cnt;
+    DevBuf<uint32_t> keys_sorted;
+    DPCG_TRY(flags.alloc(8));
+    DPCG_TRY(iota.alloc(n));
+    DPCG_TRY(head.alloc(n));
+    DPCG_TRY(pos.alloc(n));
+    DPCG_TRY(cnt.alloc(n + 1));
+    DPCG_TRY(keys_sorted.alloc(n));
+    DPCG_TRY(dev_alloc(&c->perm_c, n));
     int h_flags[8];
     for (int q = 0; q < 8; ++q) h_flags[q] = INT_MAX;
     h_flags[2] = 0;                                            // [0] negative id, [1] --, [2] largest block, [3] first oversized block
-    if (hipMemcpyAsync(flags.p, h_flags, sizeof(h_flags), hipMemcpyHostToDevice, s) != hipSuccess) return fail(DPCG_ERR_HIP);
-    hipLaunchKernelGGL(k_bic_check_ids, dim3(rows_grid(n)), dim3(kBlock), 0, s, n, c->ids, flags.p);
-    if (hipMemcpyAsync(h_flags, flags.p, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-        return fail(DPCG_ERR_HIP);
+    DPCG_HIP(hipMemcpyAsync(flags.p, h_flags, sizeof(h_flags), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_bic_check_ids, dim3(grid_blocks(n, kBicGrid)), dim3(kBlock), 0, s, n, c->ids, flags.p);
+    DPCG_TRY(fetch(h_flags, flags.p, 1, s));
     if (h_flags[0] != INT_MAX) {
         set_error("block IC: negative block id at row " + std::to_string(h_flags[0]));
-        return fail(DPCG_ERR_INVALID);
+        return DPCG_ERR_INVALID;
     }
     // rows sorted stably by block id; blocks = the maximal runs of equal id
     launch_iota(n, iota.p, s);
-    if ((st = sort_pairs_u32_i32(reinterpret_cast<const uint32_t *>(c->ids), keys_sorted.p, iota.p, c->perm_c, n, 31, s)) < 0) return fail(st);
-    hipLaunchKernelGGL(k_bic_block_heads, dim3(rows_grid(n)), dim3(kBlock), 0, s, n, keys_sorted.p, head.p);
-    if ((st = inclusive_scan_i32(head.p, head.p, n, s)) < 0) return fail(st);
+    DPCG_TRY(sort_pairs_u32_i32(reinterpret_cast<const uint32_t *>(c->ids), keys_sorted.p, iota.p, c->perm_c, n, 31, s));
+    hipLaunchKernelGGL(k_bic_block_heads, dim3(grid_blocks(n, kBicGrid)), dim3(kBlock), 0, s, n, keys_sorted.p, head.p);
+    DPCG_TRY(inclusive_scan_i32(head.p, head.p, n, s));
     int32_t last = 0;
-    if (hipMemcpyAsync(&last, head.p + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-        return fail(DPCG_ERR_HIP);
+    DPCG_TRY(fetch(&last, head.p + (n - 1), 1, s));
     c->nblocks = last + 1;
-    if ((st = dev_alloc(&c->blk_ptr, c->nblocks + 1)) < 0) return fail(st);
+    DPCG_TRY(dev_alloc(&c->blk_ptr, c->nblocks + 1));
     launch_group_offsets(n, reinterpret_cast<const uint32_t *>(head.p), c->nblocks, c->blk_ptr, s);
-    hipLaunchKernelGGL(k_bic_block_sizes, dim3(rows_grid(c->nblocks)), dim3(kBlock), 0, s, c->nblocks, c->blk_ptr, flags.p + 2);
-    if (hipMemcpyAsync(h_flags + 2, flags.p + 2, 2 * sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-        return fail(DPCG_ERR_HIP);
+    hipLaunchKernelGGL(k_bic_block_sizes, dim3(grid_blocks(c->nblocks, kBicGrid)), dim3(kBlock), 0, s, c->nblocks, c->blk_ptr, flags.p + 2);
+    DPCG_TRY(fetch(h_flags + 2, flags.p + 2, 2, s));
     c->max_block = h_flags[2];
     if (h_flags[3] != INT_MAX) {
         int32_t bp[2] = {0, 0};
         uint32_t id = 0;
-        if (hipMemcpy(bp, c->blk_ptr + h_flags[3], 2 * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess ||
-            hipMemcpy(&id, keys_sorted.p + bp[0], sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)
-            return fail(DPCG_ERR_HIP);
+        DPCG_TRY(fetch(bp, c->blk_ptr + h_flags[3], 2, s));
+        DPCG_TRY(fetch(&id, keys_sorted.p + bp[0], 1, s));
         set_error("block IC: block id " + std::to_string(id) + " holds " + std::to_string(bp[1] - bp[0]) + " rows (at most " +
                   std::to_string(kBicMaxRows) + ")");
-        return fail(DPCG_ERR_INVALID);
+        return DPCG_ERR_INVALID;
     }
     // tril(A_B) in the factor numbering
     launch_invert_positions(n, c->perm_c, pos.p, s);
     h_flags[4] = h_flags[5] = INT_MAX;
-    if (hipMemcpyAsync(flags.p + 4, h_flags + 4, 2 * sizeof(int), hipMemcpyHostToDevice, s) != hipSuccess ||
-        hipMemsetAsync(cnt.p + n, 0, sizeof(int32_t), s) != hipSuccess)
-        return fail(DPCG_ERR_HIP);
-    hipLaunchKernelGGL(k_bic_tril<false>, dim3(rows_grid(n)), dim3(kBlock), 0, s, n, c->perm_c, pos.p, c->ids, A.rowptr, A.col, cnt.p, nullptr,
-                       nullptr, nullptr, flags.p + 4);
-    if ((st = dev_alloc(&c->rp, n + 1)) < 0 || (st = exclusive_scan_i32(cnt.p, c->rp, n + 1, s)) < 0) return fail(st);
+    DPCG_HIP(hipMemcpyAsync(flags.p + 4, h_flags + 4, 2 * sizeof(int), hipMemcpyHostToDevice, s));
+    DPCG_HIP(hipMemsetAsync(cnt.p + n, 0, sizeof(int32_t), s));
+    hipLaunchKernelGGL(k_bic_tril<false>, dim3(grid_blocks(n, kBicGrid)), dim3(kBlock), 0, s, n, c->perm_c, pos.p, c->ids, A.rowptr, A.col, cnt.p,
+                       nullptr, nullptr, nullptr, flags.p + 4);
+    DPCG_TRY(dev_alloc(&c->rp, n + 1));
+    DPCG_TRY(exclusive_scan_i32(cnt.p, c->rp, n + 1, s));
     int32_t lnnz = 0;
-    if (hipMemcpyAsync(h_flags + 4, flags.p + 4, 2 * sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipMemcpyAsync(&lnnz, c->rp + n, sizeof(int32_t), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-        return fail(DPCG_ERR_HIP);
+    DPCG_HIP(hipMemcpyAsync(h_flags + 4, flags.p + 4, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
+    DPCG_TRY(fetch(&lnnz, c->rp + n, 1, s));
     if (h_flags[4] != INT_MAX) {
         set_error("block IC: the columns of row " + std::to_string(h_flags[4]) + " are not strictly ascending");
-        return fail(DPCG_ERR_INVALID);
+        return DPCG_ERR_INVALID;
     }
     if (h_flags[5] != INT_MAX) {
         set_error("block IC: missing diagonal entry at row " + std::to_string(h_flags[5]));
-        return fail(DPCG_ERR_INVALID);
+        return DPCG_ERR_INVALID;
     }
     c->nnz = lnnz;
-    if ((st = dev_alloc(&c->ci, c->nnz)) < 0 || (st = dev_alloc(&c->map_al, c->nnz)) < 0 || (st = dev_alloc(&c->val, c->nnz)) < 0) return fail(st);
-    hipLaunchKernelGGL(k_bic_tril<true>, dim3(rows_grid(n)), dim3(kBlock), 0, s, n, c->perm_c, pos.p, c->ids, A.rowptr, A.col, nullptr, c->rp, c->ci,
-                       c->map_al, nullptr);
-    // L^T's pattern: a stable sort of L's entries by column (the rows of a column come out ascending, the diagonal first)
-    Buf<int32_t> row_of, order_in, order, trp, tci;
-    Buf<uint32_t> cols_sorted;
-    if ((st = row_of.alloc(c->nnz)) < 0 || (st = order_in.alloc(c->nnz)) < 0 || (st = order.alloc(c->nnz)) < 0 || (st = trp.alloc(n + 1)) < 0 ||
-        (st = tci.alloc(c->nnz)) < 0 || (st = cols_sorted.alloc(c->nnz)) < 0)
-        return fail(st);
-    launch_row_of(n, c->rp, row_of.p, s);
-    launch_iota(c->nnz, order_in.p, s);
-    if ((st = sort_pairs_u32_i32(reinterpret_cast<const uint32_t *>(c->ci), cols_sorted.p, order_in.p, order.p, c->nnz, bits_for((uint64_t)(n - 1)), s)) < 0)
-        return fail(st);
-    launch_group_offsets(c->nnz, cols_sorted.p, (int)n, trp.p, s);
-    hipLaunchKernelGGL(k_bic_transpose_cols, dim3(rows_grid(c->nnz)), dim3(kBlock), 0, s, c->nnz, order.p, row_of.p, tci.p);
+    DPCG_TRY(dev_alloc(&c->ci, c->nnz));
+    DPCG_TRY(dev_alloc(&c->map_al, c->nnz));
+    DPCG_TRY(dev_alloc(&c->val, c->nnz));
+    hipLaunchKernelGGL(k_bic_tril<true>, dim3(grid_blocks(n, kBicGrid)), dim3(kBlock), 0, s, n, c->perm_c, pos.p, c->ids, A.rowptr, A.col, nullptr,
+                       c->rp, c->ci, c->map_al, nullptr);
+    // L^T's pattern (the rows of a column come out ascending, the diagonal first)
+    DevBuf<int32_t> order, trp, tci;
+    DPCG_TRY(order.alloc(c->nnz));
+    DPCG_TRY(trp.alloc(n + 1));
+    DPCG_TRY(tci.alloc(c->nnz));
+    DPCG_TRY(transpose_csr(n, n, c->nnz, c->rp, c->ci, nullptr, trp.p, tci.p, nullptr, order.p, s));
     // level sets and level-ordered copies, block by block
-    if ((st = alloc_side(c->lo, n, c->nnz, c->nblocks)) < 0 || (st = alloc_side(c->up, n, c->nnz, c->nblocks)) < 0) return fail(st);
-    if (hipMemsetAsync(flags.p, 0, 3 * sizeof(int), s) != hipSuccess) return fail(DPCG_ERR_HIP);
+    DPCG_TRY(alloc_side(c->lo, n, c->nnz, c->nblocks));
+    DPCG_TRY(alloc_side(c->up, n, c->nnz, c->nblocks));
+    DPCG_HIP(hipMemsetAsync(flags.p, 0, 3 * sizeof(int), s));
     hipLaunchKernelGGL(k_bic_levels<false>, dim3(c->nblocks), dim3(kBicSetupThreads), 0, s, (int)n, c->blk_ptr, c->rp, c->ci, nullptr, c->lo.nlev,
                        c->lo.lvl_ptr, c->lo.row, c->lo.e_ptr, c->lo.e_col, c->lo.e_src, c->lo.d_src, flags.p);
     hipLaunchKernelGGL(k_bic_levels<true>, dim3(c->nblocks), dim3(kBicSetupThreads), 0, s, (int)n, c->blk_ptr, trp.p, tci.p, order.p, c->up.nlev,
                        c->up.lvl_ptr, c->up.row, c->up.e_ptr, c->up.e_col, c->up.e_src, c->up.d_src, flags.p);
-    if (hipMemcpyAsync(h_flags, flags.p, 3 * sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess ||
-        hipGetLastError() != hipSuccess)
-        return fail(DPCG_ERR_HIP);
+    DPCG_TRY(fetch(h_flags, flags.p, 3, s));
+    DPCG_CHECK_LAUNCH();
     if (h_flags[2]) {
         set_error("block IC: the level analysis of a block did not finish");
-        return fail(DPCG_ERR_STATE);
+        return DPCG_ERR_STATE;
     }
     c->lo.max_levels = h_flags[0];
     c->up.max_levels = h_flags[1];
     c->threads = bic_threads(c->max_block);
-    if ((st = bic_handle_map(h, c, s)) < 0) return fail(st);
-    *out = c;
+    DPCG_TRY(bic_handle_map(h, c.get(), s));
+    *out = c.release();
     return DPCG_OK;
 }
 
 // The values of the factor from the matrix's current values into `val` (nnz doubles); DPCG_ERR_PIVOT names the caller's row.
 int bic_numeric(const BlockIc *c, const CsrDev &A, int variant, double *val, hipStream_t s) {
-    Buf<int> bad;
+    DevBuf<int> bad;
     DPCG_TRY(bad.alloc(1));
     int h_bad = INT_MAX;
     DPCG_HIP(hipMemcpyAsync(bad.p, &h_bad, sizeof(int), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_bic_gather, dim3(rows_grid(c->nnz)), dim3(kBlock), 0, s, c->nnz, c->map_al, A.val, val);
+    launch_gather_f64(c->nnz, c->map_al, A.val, val, s);
     if (variant == DPCG_BLOCK_IC_DIC)
         hipLaunchKernelGGL(k_bic_dic, dim3(c->nblocks), dim3(kBicSetupThreads), 0, s, c->blk_ptr, c->lo.nlev, c->lo.lvl_ptr, c->lo.row, c->rp, c->ci, val,
                            bad.p);
     else
         hipLaunchKernelGGL(k_bic_ic0, dim3(c->nblocks), dim3(kBicSetupThreads), 0, s, c->blk_ptr, c->lo.nlev, c->lo.lvl_ptr, c->lo.row, c->rp, c->ci, val,
                            bad.p);
-    DPCG_HIP(hipMemcpyAsync(&h_bad, bad.p, sizeof(int), hipMemcpyDeviceToHost, s));
-    DPCG_HIP(hipStreamSynchronize(s));
+    DPCG_TRY(fetch(&h_bad, bad.p, 1, s));
     DPCG_CHECK_LAUNCH();
     if (h_bad != INT_MAX) {
         int32_t row = 0;
@@ -566,8 +527,8 @@ int bic_numeric(const BlockIc *c, const CsrDev &A, int variant, double *val, hip
 void bic_load_values(BlockIc *c, hipStream_t s) {
     const int64_t off = c->nnz - c->n;
     for (BicSide *sd : {&c->lo, &c->up}) {
-        hipLaunchKernelGGL(k_bic_gather, dim3(rows_grid(off)), dim3(kBlock), 0, s, off, sd->e_src, c->val, sd->e_val);
-        hipLaunchKernelGGL(k_bic_gather, dim3(rows_grid(c->n)), dim3(kBlock), 0, s, c->n, sd->d_src, c->val, sd->diag);
+        launch_gather_f64(off, sd->e_src, c->val, sd->e_val, s);
+        launch_gather_f64(c->n, sd->d_src, c->val, sd->diag, s);
     }
 }
 }  // namespace
@@ -630,44 +591,33 @@ extern "C" int dpcg_set_precond_block_ic(dpcg_handle_t h, int variant, int block
     SetupScope scope(s, true);          // (the preconditioner being replaced may be in use on another stream)
     const CsrDev &A = h->perm ? h->A_user : h->A;      // blocks and factor are the caller's: a reordered handle gives the same bits
     const int64_t n = A.n;
-    int32_t *ids = nullptr;
-    DPCG_TRY(dev_alloc(&ids, n));
+    DevBuf<int32_t> ids;
+    DPCG_TRY(ids.alloc(n));
     if (block_of_row) {
-        const hipError_t e = hipMemcpyAsync(ids, block_of_row, (size_t)n * sizeof(int32_t),
+        const hipError_t e = hipMemcpyAsync(ids.p, block_of_row, (size_t)n * sizeof(int32_t),
                                             memspace == DPCG_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s);
-        if (e != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
-            dev_free(ids);
+        if (e != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
             return hip_fail(e != hipSuccess ? e : hipGetLastError(), "block IC: block ids", __FILE__, __LINE__);
-        }
     } else {
-        hipLaunchKernelGGL(k_bic_contiguous_ids, dim3(rows_grid(n)), dim3(kBlock), 0, s, n, block_rows, ids);
+        hipLaunchKernelGGL(k_bic_contiguous_ids, dim3(grid_blocks(n, kBicGrid)), dim3(kBlock), 0, s, n, block_rows, ids.p);
     }
     // the same ids as the symbolic phase on the handle was built for: only the values are computed
     BlockIc *c = h->bic;
     bool reuse = false;
     if (c && c->n == n) {
-        Buf<int> differ;
+        DevBuf<int> differ;
         int h_differ = 1;
-        int st = differ.alloc(1);
-        if (st >= 0 && hipMemsetAsync(differ.p, 0, sizeof(int), s) != hipSuccess) st = DPCG_ERR_HIP;
-        if (st >= 0) {
-            hipLaunchKernelGGL(k_bic_ids_differ, dim3(rows_grid(n)), dim3(kBlock), 0, s, n, ids, c->ids, differ.p);
-            if (hipMemcpyAsync(&h_differ, differ.p, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-                st = DPCG_ERR_HIP;
-        }
-        if (st < 0) {
-            dev_free(ids);
-            return st;
-        }
+        DPCG_TRY(differ.alloc(1));
+        DPCG_HIP(hipMemsetAsync(differ.p, 0, sizeof(int), s));
+        launch_same_i32(n, ids.p, c->ids, differ.p, s);
+        DPCG_TRY(fetch(&h_differ, differ.p, 1, s));
         reuse = h_differ == 0;
     }
-    if (reuse) {
-        dev_free(ids);
-    } else {
+    if (!reuse) {
         c = nullptr;
-        DPCG_TRY(bic_symbolic(h, A, ids, &c, s));          // (takes ids over, on failure too)
+        DPCG_TRY(bic_symbolic(h, A, ids.release(), &c, s));          // (takes ids over, on failure too)
     }
-    Buf<double> val;
+    DevBuf<double> val;
     int st = val.alloc(c->nnz);
     if (st >= 0) st = bic_numeric(c, A, variant, val.p, s);
     if (st < 0) {                                            // the previous preconditioner -- this very factor perhaps -- stays as it was

@@ -384,7 +384,7 @@ static int build_plan(dpcg_convnet_plan *p, int batch, int64_t height, int64_t w
     PLAN_TRY(plan_alloc(p, reinterpret_cast<char **>(&scan_ws), (int64_t)scan_bytes));
     PLAN_TRY(plan_alloc(p, &len, max_rows));
     PLAN_HIP(hipMemsetAsync(d_bad, 0, sizeof(int), s));
-    hipLaunchKernelGGL(k_sites_to_csr, dim3(grid_rows(nnz)), dim3(kBlock), 0, s, nnz, indices, batch, height, width, p->rowptr0,
+    hipLaunchKernelGGL(k_sites_to_csr, dim3(grid_blocks(nnz, kConvGrid)), dim3(kBlock), 0, s, nnz, indices, batch, height, width, p->rowptr0,
                        p->col0, d_bad);
     int bad = 0;
     PLAN_HIP(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s));
@@ -415,7 +415,7 @@ static int build_plan(dpcg_convnet_plan *p, int batch, int64_t height, int64_t w
             const int64_t rows_out = (int64_t)batch * L.h_out;
             const ConvGeom g{L.kh, L.kw, L.ph, L.pw, batch, h, w, L.h_out, L.w_out};
             PLAN_TRY(plan_alloc(p, &L.rowptr, rows_out + 1));
-            hipLaunchKernelGGL(k_conv_rows<false>, dim3(grid_rows(rows_out + 1)), dim3(kBlock), 0, s, g, rp_in, col_in, len,
+            hipLaunchKernelGGL(k_conv_rows<false>, dim3(grid_blocks(rows_out + 1, kConvGrid)), dim3(kBlock), 0, s, g, rp_in, col_in, len,
                                (const int32_t *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr);
             PLAN_TRY(exclusive_scan_i32_ws(len, L.rowptr, rows_out + 1, scan_ws, scan_bytes, s));
             int32_t total = 0;
@@ -428,7 +428,7 @@ static int build_plan(dpcg_convnet_plan *p, int batch, int64_t height, int64_t w
             L.sites = total;
             PLAN_TRY(plan_alloc(p, &L.col, L.sites));
             PLAN_TRY(plan_alloc(p, &L.nbr, L.sites * L.kh * L.kw));
-            hipLaunchKernelGGL(k_conv_rows<true>, dim3(grid_rows(rows_out + 1)), dim3(kBlock), 0, s, g, rp_in, col_in,
+            hipLaunchKernelGGL(k_conv_rows<true>, dim3(grid_blocks(rows_out + 1, kConvGrid)), dim3(kBlock), 0, s, g, rp_in, col_in,
                                (int32_t *)nullptr, (const int32_t *)L.rowptr, L.col, L.nbr);
         }
         rp_in = L.rowptr;
@@ -445,7 +445,7 @@ static int build_plan(dpcg_convnet_plan *p, int batch, int64_t height, int64_t w
         PLAN_TRY(plan_alloc(p, &p->site_batch, L.sites));
         PLAN_TRY(plan_alloc(p, &p->lower_rowptr, rows + 1));
         PLAN_TRY(plan_alloc(p, &p->lower_pos, L.sites));
-        hipLaunchKernelGGL(k_lower_count, dim3(grid_rows(rows + 1)), dim3(kBlock), 0, s, rows, L.h_out, L.rowptr, L.col, len,
+        hipLaunchKernelGGL(k_lower_count, dim3(grid_blocks(rows + 1, kConvGrid)), dim3(kBlock), 0, s, rows, L.h_out, L.rowptr, L.col, len,
                            p->site_row, p->site_batch);
         PLAN_TRY(exclusive_scan_i32_ws(len, p->lower_rowptr, rows + 1, scan_ws, scan_bytes, s));
         int32_t total = 0;
@@ -453,7 +453,7 @@ static int build_plan(dpcg_convnet_plan *p, int batch, int64_t height, int64_t w
         PLAN_HIP(hipStreamSynchronize(s));
         p->nnz_lower = total;
         PLAN_TRY(plan_alloc(p, &p->lower_col, p->nnz_lower));
-        hipLaunchKernelGGL(k_lower_fill, dim3(grid_rows(rows)), dim3(kBlock), 0, s, rows, L.h_out, L.rowptr, L.col,
+        hipLaunchKernelGGL(k_lower_fill, dim3(grid_blocks(rows, kConvGrid)), dim3(kBlock), 0, s, rows, L.h_out, L.rowptr, L.col,
                            p->lower_rowptr, p->lower_col, p->lower_pos);
     }
     PLAN_HIP(hipStreamSynchronize(s));
@@ -503,7 +503,7 @@ extern "C" int dpcg_convnet_plan_output(dpcg_convnet_plan_t p, int32_t *indices_
     hipStream_t s = (hipStream_t)stream;
     const LayerPlan &L = p->layers[p->n_layers - 1];
     if (indices_out)
-        hipLaunchKernelGGL(k_out_indices, dim3(grid_rows(L.sites)), dim3(kBlock), 0, s, L.sites, p->site_batch, p->site_row, L.col,
+        hipLaunchKernelGGL(k_out_indices, dim3(grid_blocks(L.sites, kConvGrid)), dim3(kBlock), 0, s, L.sites, p->site_batch, p->site_row, L.col,
                            indices_out);
     if (lower_rowptr)
         DPCG_HIP(hipMemcpyAsync(lower_rowptr, p->lower_rowptr, (size_t)((int64_t)p->batch * L.h_out + 1) * sizeof(int32_t),
@@ -549,7 +549,7 @@ extern "C" int dpcg_convnet_forward(dpcg_convnet_plan_t p, const int32_t *channe
         const int cin = channels[l], cout = channels[l + 1], taps = L.kh * L.kw;
         const bool is_last = l == n - 1;
         if (is_last && fused_final) {
-            const int g = grid_rows(L.sites, 2048);
+            const int g = grid_blocks(L.sites, 2048);
 #define DPCG_FINAL(CI)                                                                                                  \
     hipLaunchKernelGGL((k_sconv_final<CI>), dim3(g), dim3(kBlock), 0, s, L.sites, in, weights[l], biases[l], p->site_row, \
                        L.col, p->lower_pos, lower_softplus, features_out, lower_val)
@@ -563,7 +563,7 @@ extern "C" int dpcg_convnet_forward(dpcg_convnet_plan_t p, const int32_t *channe
         const bool mfma = taps == 4 && L.kh == 2 && L.nbr &&
                           try_mfma(cin, cout, L.sites, L.nbr, in, weights[l], biases[l], prelu[l], dst, s);
         if (!mfma) {
-            const int g = grid_rows(L.sites * cout, 4096);
+            const int g = grid_blocks(L.sites * cout, kConvGrid);
             if (prelu[l])
                 hipLaunchKernelGGL((k_sconv_generic<true>), dim3(g), dim3(kBlock), 0, s, L.sites, taps, (const int32_t *)L.nbr, cin,
                                    cout, in, weights[l], biases[l], prelu[l], dst);

@@ -51,18 +51,7 @@ namespace {
 constexpr int kFsaiMaxM = 64;
 constexpr int kNoColumn = 0x7fffffff;
 
-template <typename T>
-struct Buf {
-    T *p = nullptr;
-    Buf() = default;
-    Buf(const Buf &) = delete;
-    Buf &operator=(const Buf &) = delete;
-    ~Buf() { dev_free(p); }
-    int alloc(int64_t count) { dev_free(p); return dev_alloc(&p, count); }
-    T *release() { T *q = p; p = nullptr; return q; }
-};
-
-inline unsigned grid_of(int64_t count) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((count + kBlock - 1) / kBlock, 65535)); }
+constexpr int kFsaiGrid = 65535;      // most workgroups of a setup kernel
 
 __host__ __device__ inline int width_class(int m) { return m <= 4 ? 0 : m <= 8 ? 1 : m <= 16 ? 2 : m <= 32 ? 3 : 4; }
 
@@ -166,13 +155,6 @@ __global__ __launch_bounds__(kBlock) void k_check_pattern(int64_t n, int64_t nnz
         }
     }
     if (bad) atomicOr(flags, bad);
-}
-
-__global__ __launch_bounds__(kBlock) void k_same_i32(int64_t count, const int32_t *__restrict__ a, const int32_t *__restrict__ b, int *differ) {
-    const int64_t stride = (int64_t)gridDim.x * kBlock;
-    bool d = false;
-    for (int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x; k < count; k += stride) d |= a[k] != b[k];
-    if (d) *differ = 1;      // (every writer stores the same value)
 }
 
 // m_i, its width class as a sort key, the first column wider than the cap
@@ -379,46 +361,20 @@ __global__ __launch_bounds__(kBlock) void k_fsai_wide(int s0, int nb, const int3
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------
-int read_i32(const int32_t *dev, int32_t *host, hipStream_t s) {
-    DPCG_HIP(hipMemcpyAsync(host, dev, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    DPCG_HIP(hipStreamSynchronize(s));
-    return DPCG_OK;
-}
-
-// (out_rp, out_ci) = the transpose of the pattern (rp, ci), rows ascending inside every output row; order: output entry -> input entry
-int transpose_pattern(int64_t n, int64_t nnz, const int32_t *rp, const int32_t *ci, int32_t *out_rp, int32_t *out_ci, int32_t *order,
-                      hipStream_t s) {
-    Buf<int32_t> row_of, iota;
-    Buf<uint32_t> sorted;
-    DPCG_TRY(row_of.alloc(nnz));
-    DPCG_TRY(iota.alloc(nnz));
-    DPCG_TRY(sorted.alloc(nnz));
-    launch_row_of(n, rp, row_of.p, s);
-    launch_iota(nnz, iota.p, s);
-    DPCG_TRY(sort_pairs_u32_i32(reinterpret_cast<const uint32_t *>(ci), sorted.p, iota.p, order, nnz, bits_for((uint64_t)(n - 1)), s));
-    launch_group_offsets(nnz, sorted.p, (int)n, out_rp, s);
-    DPCG_HIP(hipMemcpyAsync(out_ci, order, (size_t)nnz * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-    launch_relabel(nnz, row_of.p, out_ci, s);
-    DPCG_HIP(hipStreamSynchronize(s));
-    DPCG_CHECK_LAUNCH();
-    return DPCG_OK;
-}
-
 // One step X -> pattern(X A) (columns >= row only when `upper`): owned (rp, ci) and the entry count
-int power_step(int64_t n, const int32_t *xrp, const int32_t *xci, const CsrDev &A, bool upper, Buf<int32_t> &out_rp, Buf<int32_t> &out_ci,
+int power_step(int64_t n, const int32_t *xrp, const int32_t *xci, const CsrDev &A, bool upper, DevBuf<int32_t> &out_rp, DevBuf<int32_t> &out_ci,
                int64_t *out_nnz, hipStream_t s) {
-    Buf<int32_t> cnt, off, head, pos, vin, vout;
-    Buf<unsigned long long> total;
-    Buf<uint64_t> key, key_sorted;
-    Buf<uint32_t> rows;
+    DevBuf<int32_t> cnt, off, head, pos, vin, vout;
+    DevBuf<unsigned long long> total;
+    DevBuf<uint64_t> key, key_sorted;
+    DevBuf<uint32_t> rows;
     DPCG_TRY(cnt.alloc(n + 1));
     DPCG_TRY(off.alloc(n + 1));
     DPCG_TRY(total.alloc(1));
     DPCG_HIP(hipMemsetAsync(total.p, 0, sizeof(unsigned long long), s));
-    hipLaunchKernelGGL(k_expand_count, dim3(grid_of(n + 1)), dim3(kBlock), 0, s, n, xrp, xci, A.rowptr, A.col, upper ? 1 : 0, cnt.p, total.p);
+    hipLaunchKernelGGL(k_expand_count, dim3(grid_blocks(n + 1, kFsaiGrid)), dim3(kBlock), 0, s, n, xrp, xci, A.rowptr, A.col, upper ? 1 : 0, cnt.p, total.p);
     unsigned long long h_total = 0;
-    DPCG_HIP(hipMemcpyAsync(&h_total, total.p, sizeof(h_total), hipMemcpyDeviceToHost, s));
-    DPCG_HIP(hipStreamSynchronize(s));
+    DPCG_TRY(fetch(&h_total, total.p, 1, s));
     if (h_total >= 0x7fffffffull) return invalid("dpcg_set_precond_fsai: the pattern of A^k expands to more than 2^31 products");
     const int64_t count = (int64_t)h_total;
     DPCG_TRY(exclusive_scan_i32(cnt.p, off.p, n + 1, s));
@@ -426,19 +382,19 @@ int power_step(int64_t n, const int32_t *xrp, const int32_t *xci, const CsrDev &
     DPCG_TRY(key_sorted.alloc(count));
     DPCG_TRY(vin.alloc(count));
     DPCG_TRY(vout.alloc(count));
-    hipLaunchKernelGGL(k_expand_fill, dim3(grid_of(n)), dim3(kBlock), 0, s, n, xrp, xci, A.rowptr, A.col, upper ? 1 : 0, off.p, key.p);
+    hipLaunchKernelGGL(k_expand_fill, dim3(grid_blocks(n, kFsaiGrid)), dim3(kBlock), 0, s, n, xrp, xci, A.rowptr, A.col, upper ? 1 : 0, off.p, key.p);
     launch_iota(count, vin.p, s);
     DPCG_TRY(sort_pairs_u64_i32(key.p, key_sorted.p, vin.p, vout.p, count, 32 + bits_for((uint64_t)(n - 1)), s));
     DPCG_TRY(head.alloc(count + 1));
     DPCG_TRY(pos.alloc(count + 1));
-    hipLaunchKernelGGL(k_heads, dim3(grid_of(count + 1)), dim3(kBlock), 0, s, count, key_sorted.p, head.p);
+    hipLaunchKernelGGL(k_heads, dim3(grid_blocks(count + 1, kFsaiGrid)), dim3(kBlock), 0, s, count, key_sorted.p, head.p);
     DPCG_TRY(exclusive_scan_i32(head.p, pos.p, count + 1, s));
     int32_t uniq = 0;
-    DPCG_TRY(read_i32(pos.p + count, &uniq, s));
+    DPCG_TRY(fetch(&uniq, pos.p + count, 1, s));
     DPCG_TRY(rows.alloc(uniq));
     DPCG_TRY(out_rp.alloc(n + 1));
     DPCG_TRY(out_ci.alloc(uniq));
-    hipLaunchKernelGGL(k_compact, dim3(grid_of(count)), dim3(kBlock), 0, s, count, key_sorted.p, head.p, pos.p, rows.p, out_ci.p);
+    hipLaunchKernelGGL(k_compact, dim3(grid_blocks(count, kFsaiGrid)), dim3(kBlock), 0, s, count, key_sorted.p, head.p, pos.p, rows.p, out_ci.p);
     launch_group_offsets(uniq, rows.p, (int)n, out_rp.p, s);
     DPCG_HIP(hipStreamSynchronize(s));
     DPCG_CHECK_LAUNCH();
@@ -455,10 +411,10 @@ void free_cache_arrays(FsaiCache &c) {
 int symbolic_rest(FsaiCache &c, const CsrDev &A, hipStream_t s) {
     const int64_t n = c.n, nnz = c.nnz;
     // widths, the cap, the classes
-    Buf<int32_t> m, iota, tri;
-    Buf<uint32_t> cls, cls_sorted;
-    Buf<int> first;
-    Buf<int32_t> binp;
+    DevBuf<int32_t> m, iota, tri;
+    DevBuf<uint32_t> cls, cls_sorted;
+    DevBuf<int> first;
+    DevBuf<int32_t> binp;
     DPCG_TRY(m.alloc(n));
     DPCG_TRY(cls.alloc(n));
     DPCG_TRY(cls_sorted.alloc(n));
@@ -467,57 +423,54 @@ int symbolic_rest(FsaiCache &c, const CsrDev &A, hipStream_t s) {
     DPCG_TRY(binp.alloc(6));
     const int none = kNoColumn;
     DPCG_HIP(hipMemcpyAsync(first.p, &none, sizeof(int), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_widths, dim3(grid_of(n)), dim3(kBlock), 0, s, n, c.hrp, m.p, cls.p, first.p);
+    hipLaunchKernelGGL(k_widths, dim3(grid_blocks(n, kFsaiGrid)), dim3(kBlock), 0, s, n, c.hrp, m.p, cls.p, first.p);
     int h_first = kNoColumn;
-    DPCG_HIP(hipMemcpyAsync(&h_first, first.p, sizeof(int), hipMemcpyDeviceToHost, s));
-    DPCG_HIP(hipStreamSynchronize(s));
+    DPCG_TRY(fetch(&h_first, first.p, 1, s));
     if (h_first != kNoColumn) {
         int32_t wm = 0;
-        DPCG_TRY(read_i32(m.p + h_first, &wm, s));
+        DPCG_TRY(fetch(&wm, m.p + h_first, 1, s));
         set_error("fsai: column " + std::to_string(h_first) + " has m = " + std::to_string(wm) + " > " + std::to_string(kFsaiMaxM) +
                   " entries in its local system");
         return DPCG_ERR_INVALID;
     }
-    Buf<int32_t> mmax;
+    DevBuf<int32_t> mmax;
     DPCG_TRY(mmax.alloc(1));
     DPCG_TRY(reduce_max_i32(m.p, mmax.p, n, s));
     int32_t h_mmax = 0;
-    DPCG_TRY(read_i32(mmax.p, &h_mmax, s));
+    DPCG_TRY(fetch(&h_mmax, mmax.p, 1, s));
     c.max_m = h_mmax;
     DPCG_TRY(dev_alloc(&c.order, n));
     launch_iota(n, iota.p, s);
     DPCG_TRY(sort_pairs_u32_i32(cls.p, cls_sorted.p, iota.p, c.order, n, 3, s));
     launch_group_offsets(n, cls_sorted.p, 5, binp.p, s);
     int32_t h_bin[6];
-    DPCG_HIP(hipMemcpyAsync(h_bin, binp.p, sizeof(h_bin), hipMemcpyDeviceToHost, s));
-    DPCG_HIP(hipStreamSynchronize(s));
+    DPCG_TRY(fetch(h_bin, binp.p, 6, s));
     for (int b = 0; b < 6; ++b) c.bin_ptr[b] = h_bin[b];
     // the gather map
     const int64_t wide_bound = (int64_t)(n - c.bin_ptr[2]) * (kFsaiMaxM * (kFsaiMaxM + 1) / 2);
     DPCG_TRY(tri.alloc(n + 1));
     DPCG_TRY(dev_alloc(&c.moff, n + 1));
-    hipLaunchKernelGGL(k_tri_sizes, dim3(grid_of(n + 1)), dim3(kBlock), 0, s, n, c.order, m.p, c.bin_ptr[2], tri.p);
+    hipLaunchKernelGGL(k_tri_sizes, dim3(grid_blocks(n + 1, kFsaiGrid)), dim3(kBlock), 0, s, n, c.order, m.p, c.bin_ptr[2], tri.p);
     if (wide_bound >= 0x7fffffffll) {                        // (only then can the int32 scan wrap: sum the sizes in 64 bits first)
         std::vector<int32_t> h_tri((size_t)n + 1);
-        DPCG_HIP(hipMemcpyAsync(h_tri.data(), tri.p, (size_t)(n + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        DPCG_HIP(hipStreamSynchronize(s));
+        DPCG_TRY(fetch(h_tri.data(), tri.p, n + 1, s));
         int64_t sum = 0;
         for (int32_t v : h_tri) sum += v;
         if (sum >= 0x7fffffffll) return invalid("fsai: the gather map of this pattern needs more than 2^31 entries");
     }
     DPCG_TRY(exclusive_scan_i32(tri.p, c.moff, n + 1, s));
     int32_t wide_len = 0;
-    DPCG_TRY(read_i32(c.moff + n, &wide_len, s));
+    DPCG_TRY(fetch(&wide_len, c.moff + n, 1, s));
     const int64_t nb0 = c.bin_ptr[1] - c.bin_ptr[0], nb1 = c.bin_ptr[2] - c.bin_ptr[1];
     c.reg_base[0] = wide_len;
     c.reg_base[1] = c.reg_base[0] + 10 * nb0;
     const int64_t map_len = c.reg_base[1] + 36 * nb1;
     DPCG_TRY(dev_alloc(&c.map, map_len));
     if (nb0 > 0)
-        hipLaunchKernelGGL(k_map_reg, dim3(grid_of(nb0)), dim3(kBlock), 0, s, (int)nb0, 4, c.order + c.bin_ptr[0], c.hrp, c.hci, A.rowptr, A.col,
+        hipLaunchKernelGGL(k_map_reg, dim3(grid_blocks(nb0, kFsaiGrid)), dim3(kBlock), 0, s, (int)nb0, 4, c.order + c.bin_ptr[0], c.hrp, c.hci, A.rowptr, A.col,
                            c.map + c.reg_base[0]);
     if (nb1 > 0)
-        hipLaunchKernelGGL(k_map_reg, dim3(grid_of(nb1)), dim3(kBlock), 0, s, (int)nb1, 8, c.order + c.bin_ptr[1], c.hrp, c.hci, A.rowptr, A.col,
+        hipLaunchKernelGGL(k_map_reg, dim3(grid_blocks(nb1, kFsaiGrid)), dim3(kBlock), 0, s, (int)nb1, 8, c.order + c.bin_ptr[1], c.hrp, c.hci, A.rowptr, A.col,
                            c.map + c.reg_base[1]);
     for (int b = 2; b < 5; ++b) {
         const int nb = c.bin_ptr[b + 1] - c.bin_ptr[b], W = 16 << (b - 2);
@@ -530,7 +483,9 @@ int symbolic_rest(FsaiCache &c, const CsrDev &A, hipStream_t s) {
     DPCG_TRY(dev_alloc(&c.lrp, n + 1));
     DPCG_TRY(dev_alloc(&c.lci, nnz));
     DPCG_TRY(dev_alloc(&c.t_order, nnz));
-    DPCG_TRY(transpose_pattern(n, nnz, c.hrp, c.hci, c.lrp, c.lci, c.t_order, s));
+    DPCG_TRY(transpose_csr(n, n, nnz, c.hrp, c.hci, nullptr, c.lrp, c.lci, nullptr, c.t_order, s));
+    DPCG_HIP(hipStreamSynchronize(s));
+    DPCG_CHECK_LAUNCH();
     return DPCG_OK;
 }
 
@@ -538,14 +493,13 @@ int symbolic(FsaiCache &c, const CsrDev &A, hipStream_t s) {
     const int64_t n = A.n;
     c.n = n;
     {
-        Buf<int> first;
+        DevBuf<int> first;
         DPCG_TRY(first.alloc(2));
         const int none[2] = {kNoColumn, kNoColumn};
         DPCG_HIP(hipMemcpyAsync(first.p, none, sizeof(none), hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_check_rows, dim3(grid_of(n)), dim3(kBlock), 0, s, n, A.rowptr, A.col, first.p, first.p + 1);
+        hipLaunchKernelGGL(k_check_rows, dim3(grid_blocks(n, kFsaiGrid)), dim3(kBlock), 0, s, n, A.rowptr, A.col, first.p, first.p + 1);
         int h_first[2] = {kNoColumn, kNoColumn};
-        DPCG_HIP(hipMemcpyAsync(h_first, first.p, sizeof(h_first), hipMemcpyDeviceToHost, s));
-        DPCG_HIP(hipStreamSynchronize(s));
+        DPCG_TRY(fetch(h_first, first.p, 2, s));
         if (h_first[1] != kNoColumn) {
             set_error("fsai: the matrix must have strictly ascending columns in every row (row " + std::to_string(h_first[1]) + " has not)");
             return DPCG_ERR_INVALID;
@@ -556,13 +510,13 @@ int symbolic(FsaiCache &c, const CsrDev &A, hipStream_t s) {
         }
     }
     if (c.level > 0) {
-        Buf<int32_t> xrp, xci;
+        DevBuf<int32_t> xrp, xci;
         DPCG_TRY(xrp.alloc(n + 1));
         DPCG_TRY(xci.alloc(n));
-        hipLaunchKernelGGL(k_identity, dim3(grid_of(n + 1)), dim3(kBlock), 0, s, n, xrp.p, xci.p);
+        hipLaunchKernelGGL(k_identity, dim3(grid_blocks(n + 1, kFsaiGrid)), dim3(kBlock), 0, s, n, xrp.p, xci.p);
         int64_t xnnz = n;
         for (int step = 1; step <= c.level; ++step) {
-            Buf<int32_t> yrp, yci;
+            DevBuf<int32_t> yrp, yci;
             DPCG_TRY(power_step(n, xrp.p, xci.p, A, step == c.level, yrp, yci, &xnnz, s));
             std::swap(xrp.p, yrp.p);
             std::swap(xci.p, yci.p);
@@ -572,11 +526,13 @@ int symbolic(FsaiCache &c, const CsrDev &A, hipStream_t s) {
         c.nnz = xnnz;
     } else {
         c.nnz = c.pat_nnz;
-        Buf<int32_t> order;
+        DevBuf<int32_t> order;
         DPCG_TRY(order.alloc(c.nnz));
         DPCG_TRY(dev_alloc(&c.hrp, n + 1));
         DPCG_TRY(dev_alloc(&c.hci, c.nnz));
-        DPCG_TRY(transpose_pattern(n, c.nnz, c.pat_rp, c.pat_ci, c.hrp, c.hci, order.p, s));
+        DPCG_TRY(transpose_csr(n, n, c.nnz, c.pat_rp, c.pat_ci, nullptr, c.hrp, c.hci, nullptr, order.p, s));
+        DPCG_HIP(hipStreamSynchronize(s));
+        DPCG_CHECK_LAUNCH();
     }
     return symbolic_rest(c, A, s);
 }
@@ -584,8 +540,8 @@ int symbolic(FsaiCache &c, const CsrDev &A, hipStream_t s) {
 // The values of H for the handle's current matrix values, gathered into Lf (owned; the pattern copied from the cache)
 int numeric(const FsaiCache &c, const CsrDev &A, CsrDev &Lf, hipStream_t s) {
     const int64_t n = c.n, nnz = c.nnz;
-    Buf<double> hv;
-    Buf<int> bad;
+    DevBuf<double> hv;
+    DevBuf<int> bad;
     DPCG_TRY(hv.alloc(nnz));
     DPCG_TRY(bad.alloc(1));
     const int none = kNoColumn;
@@ -609,8 +565,7 @@ int numeric(const FsaiCache &c, const CsrDev &A, CsrDev &Lf, hipStream_t s) {
                            hv.p, bad.p);
     int h_bad = kNoColumn;
     DPCG_HIP(hipGetLastError());
-    DPCG_HIP(hipMemcpyAsync(&h_bad, bad.p, sizeof(int), hipMemcpyDeviceToHost, s));
-    DPCG_HIP(hipStreamSynchronize(s));
+    DPCG_TRY(fetch(&h_bad, bad.p, 1, s));
     if (h_bad != kNoColumn) {
         set_error("fsai: non-positive or non-finite pivot in the local system of column " + std::to_string(h_bad));
         return DPCG_ERR_PIVOT;
@@ -674,8 +629,8 @@ int fsai_factor(dpcg_system *h, int level, int64_t pat_nnz, int32_t *pat_rp, int
             hipError_t e = hipSuccess;
             if (st >= 0) {
                 e = hipMemsetAsync(differ, 0, sizeof(int), s);
-                hipLaunchKernelGGL(k_same_i32, dim3(grid_of(A.n + 1)), dim3(kBlock), 0, s, A.n + 1, c->pat_rp, pat_rp, differ);
-                hipLaunchKernelGGL(k_same_i32, dim3(grid_of(pat_nnz)), dim3(kBlock), 0, s, pat_nnz, c->pat_ci, pat_ci, differ);
+                launch_same_i32(A.n + 1, c->pat_rp, pat_rp, differ, s);
+                launch_same_i32(pat_nnz, c->pat_ci, pat_ci, differ, s);
                 if (e == hipSuccess) e = hipMemcpyAsync(&h_differ, differ, sizeof(int), hipMemcpyDeviceToHost, s);
                 if (e == hipSuccess) e = hipStreamSynchronize(s);
             }
@@ -742,7 +697,7 @@ int fsai_upload_pattern(int64_t n, int64_t nnz, const int32_t *rowptr, const int
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) return done(hip_fail(e, "fsai: pattern upload", __FILE__, __LINE__));
     if (h_last != nnz) return done(invalid("dpcg_set_precond_fsai_pattern: rowptr[n] != nnz"));
-    hipLaunchKernelGGL(k_check_pattern, dim3(grid_of(n)), dim3(kBlock), 0, s, n, nnz, rp, ci, flags);
+    hipLaunchKernelGGL(k_check_pattern, dim3(grid_blocks(n, kFsaiGrid)), dim3(kBlock), 0, s, n, nnz, rp, ci, flags);
     e = hipMemcpyAsync(&h_flags, flags, sizeof(int), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) return done(hip_fail(e, "fsai: pattern check", __FILE__, __LINE__));

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "dpcg_internal.h"
+#include "dpcg_prims.h"
 
 using namespace dpcg;
 
@@ -66,6 +67,32 @@ template <typename T>
 inline void dev_free(T *&p) {
     if (p) cached_free(p);
     p = nullptr;
+}
+
+// scoped device allocation for the setup routines
+template <typename T>
+struct DevBuf {
+    T *p = nullptr;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { dev_free(p); }
+    int alloc(int64_t count) { dev_free(p); return dev_alloc(&p, count); }
+    T *release() { T *q = p; p = nullptr; return q; }
+};
+
+// host[0 .. count) = dev[0 .. count), complete on return
+template <typename T>
+inline int fetch(T *host, const T *dev, int64_t count, hipStream_t s) {
+    DPCG_HIP(hipMemcpyAsync(host, dev, (size_t)count * sizeof(T), hipMemcpyDeviceToHost, s));
+    DPCG_HIP(hipStreamSynchronize(s));
+    return DPCG_OK;
+}
+
+// ---- launch geometry of the setup kernels: workgroups of per_block items that stride over `count` items, at most `cap` of them
+inline int grid_blocks(int64_t count, int cap, int per_block = kBlock) {
+    const int64_t g = (count + per_block - 1) / per_block;
+    return (int)std::min<int64_t>(std::max<int64_t>(g, 1), cap);
 }
 
 void free_csr(CsrDev &c);

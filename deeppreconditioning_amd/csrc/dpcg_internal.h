@@ -479,8 +479,6 @@ void launch_strip_factor_scatter(int64_t n, const int32_t *frow, const int32_t *
 // done: optional device flag (Scalars::done); when set the kernels return at once
 void launch_sptrsv(const CsrDev &T, const Levels &lv, bool upper, const double *rhs, double *out, hipStream_t s,
                    const int *done = nullptr, SptrsvIo *io = nullptr);
-void launch_invert_positions(int64_t n, const int32_t *rows, int32_t *pos, hipStream_t s);          // pos[rows[j]] = j
-void launch_compose_positions(int64_t n, const int32_t *rows, const int32_t *pos, int32_t *out, hipStream_t s);   // out[j] = pos[rows[j]]
 
 // Builds the x-tile plan of A on the device; *ok = 1 when every block is tileable, *max_chunks its widest tile.
 void launch_sweep_tile_plan(int j0, int count, const int32_t *lo_rowptr, const int32_t *lo_cpos, int32_t *chunks, int32_t *nchunks,
@@ -639,11 +637,6 @@ void launch_copy_kept(int64_t n, const int32_t *rp, const int32_t *ci, const dou
                       double *ov, hipStream_t s);
 void launch_block_nnz_max(const CsrDev &A, int rows_per_block, int *out_max_dev, hipStream_t s);
 // ---- reordering (dpcg_reorder.hip) ----
-void launch_gather_f64(int64_t n, const int32_t *perm, const double *in, double *out, hipStream_t s);    // out[r] = in[perm[r]]
-void launch_scatter_f64(int64_t n, const int32_t *perm, const double *in, double *out, hipStream_t s);   // out[perm[r]] = in[r]
-void launch_gather_f32(int64_t n, const int32_t *perm, const float *in, float *out, hipStream_t s);
-void launch_scatter_f32(int64_t n, const int32_t *perm, const float *in, float *out, hipStream_t s);
-void launch_relabel(int64_t count, const int32_t *map, int32_t *idx, hipStream_t s);                    // idx[k] = map[idx[k]]
 int gather_line_ratio(const CsrDev &A, double *ratio, hipStream_t s);
 int permute_csr(const CsrDev &A, const int32_t *perm, const int32_t *iperm, CsrDev &B, hipStream_t s);
 int rcm_order(const CsrDev &A, int32_t **perm_out, int32_t **iperm_out, int *n_components, hipStream_t s);
@@ -655,11 +648,6 @@ int region_order(const CsrDev &A, int regions, int32_t **perm_out, int32_t **ipe
 int region_order_default_regions(int64_t n);
 // ---- structural analysis of triangular factors on the device (dpcg_analysis.hip) ----
 void launch_check_lower(const CsrDev &L, int *flags, hipStream_t s);
-void launch_row_of(int64_t n, const int32_t *rp, int32_t *row_of, hipStream_t s);
-void launch_iota(int64_t count, int32_t *out, hipStream_t s);
-void launch_group_offsets(int64_t count, const uint32_t *keys_sorted, int groups, int32_t *ptr, hipStream_t s);
-void launch_transpose_gather(int64_t nnz, const int32_t *perm, const int32_t *row_of, const double *val, int32_t *tcol,
-                             double *tval, hipStream_t s);
 // Which strip of the strip-pipelined solve a row belongs to (idx = the row index, counted from the END for an upper factor).
 // Slabs of `rows` consecutive indices (a multiple of the band: whole planes / grid lines); parts > 1 cuts every slab once more
 // by the position inside the band, (idx % band) / sub_w -- for a grid: pencils instead of slabs, so that the longest
@@ -736,6 +724,5 @@ __device__ __forceinline__ double wave_sum(double v) {
     v += dpp_move<0x143, 0xc>(v);   // row_bcast:31 into rows 2 and 3 -> lane 63 holds the wave sum
     return v;
 }
-
 
 }  // namespace dpcg

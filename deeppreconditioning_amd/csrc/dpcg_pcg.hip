@@ -2,6 +2,7 @@
 // Compiled with -ffp-contract=off so that a*b+c is two roundings, as in the CPU reference path (scipy/ATen CSR row
 // sums, unfused torch mul+add at cg.py:79-83); in-order sums then reproduce the oracle bit for bit.
 #include "dpcg_device.h"
+#include "dpcg_host.h"
 
 namespace dpcg {
 
@@ -653,15 +654,12 @@ __global__ __launch_bounds__(kBlock) void k_convert(int64_t n, const TI *__restr
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) out[i] = (TO)in[i];
 }
 
-static int conv_grid(int64_t n) {
-    int64_t g = (n + kBlock - 1) / kBlock;
-    return (int)(g > 4096 ? 4096 : (g < 1 ? 1 : g));
-}
+constexpr int kConvertGrid = 4096;
 void launch_f64_to_f32(int64_t n, const double *in, float *out, hipStream_t s) {
-    hipLaunchKernelGGL((k_convert<double, float>), dim3(conv_grid(n)), dim3(kBlock), 0, s, n, in, out);
+    hipLaunchKernelGGL((k_convert<double, float>), dim3(grid_blocks(n, kConvertGrid)), dim3(kBlock), 0, s, n, in, out);
 }
 void launch_f32_to_f64(int64_t n, const float *in, double *out, hipStream_t s) {
-    hipLaunchKernelGGL((k_convert<float, double>), dim3(conv_grid(n)), dim3(kBlock), 0, s, n, in, out);
+    hipLaunchKernelGGL((k_convert<float, double>), dim3(grid_blocks(n, kConvertGrid)), dim3(kBlock), 0, s, n, in, out);
 }
 
 // e = x - x_true (cg.py:27,43): only for conjugate_gradient(..., x_true=...).

@@ -112,17 +112,6 @@ bool syncfree_enabled() {
     return on;
 }
 
-template <typename T>
-struct DevBuf {                       // scoped device allocation for the setup routines
-    T *p = nullptr;
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() { dev_free(p); }
-    int alloc(int64_t count) { dev_free(p); return dev_alloc(&p, count); }
-    T *release() { T *q = p; p = nullptr; return q; }
-};
-
 // rows sorted by (level, row), the level of every sorted position, the level offsets (device and host)
 struct LevelSort {
     DevBuf<int32_t> rows;
@@ -147,8 +136,7 @@ int compute_levels(int64_t n, const int32_t *rp, const int32_t *ci, bool upper, 
     DPCG_CHECK_LAUNCH();
     DPCG_TRY(reduce_max_i32(level.p, ctl.p + 2, n, s));
     int32_t h_ctl[4] = {0, 0, 0, 0};
-    DPCG_HIP(hipMemcpyAsync(h_ctl, ctl.p, sizeof(h_ctl), hipMemcpyDeviceToHost, s));
-    DPCG_HIP(hipStreamSynchronize(s));
+    DPCG_TRY(fetch(h_ctl, ctl.p, 4, s));
     if (h_ctl[1] || h_ctl[2] < 0) {
         set_error("level analysis: the factor's dependency graph is not acyclic in row order");
         return DPCG_ERR_INVALID;
@@ -329,8 +317,7 @@ int build_levels(Levels &lv, LevelSort &ls, int64_t n, int64_t nnz, const int32_
         DPCG_HIP(hipMemsetAsync(d_maxdist.p, 0, (size_t)nseg * sizeof(int32_t), s));
         launch_ring_reach(n, ls.lvl_of_pos.p, d_seg_of_level.p, d_seg_start.p, lv.lo_rowptr, lv.lo_cpos, d_maxdist.p, s);
         std::vector<int32_t> maxdist((size_t)nseg, 0);
-        DPCG_HIP(hipMemcpyAsync(maxdist.data(), d_maxdist.p, maxdist.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        DPCG_HIP(hipStreamSynchronize(s));
+        DPCG_TRY(fetch(maxdist.data(), d_maxdist.p, maxdist.size(), s));
         for (int64_t q = 0; q < nseg; ++q) {
             Levels::Segment &seg = lv.segments[(size_t)merged_index[(size_t)q]];
             int64_t w = 64;
@@ -450,8 +437,7 @@ int build_levels(Levels &lv, LevelSort &ls, int64_t n, int64_t nnz, const int32_
                     launch_sweep_tile_plan(level_ptr[l], level_ptr[l + 1] - level_ptr[l], lv.lo_rowptr, lv.lo_cpos,
                                            lv.sw_chunks + (size_t)lv.sw_blk0[(size_t)l] * kTileMaxChunks, lv.sw_nchunks + lv.sw_blk0[(size_t)l],
                                            lv.sw_lidx, reinterpret_cast<int *>(d_flags.p) + 2 * l, s);
-                DPCG_HIP(hipMemcpyAsync(h_flags.data(), d_flags.p, h_flags.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-                DPCG_HIP(hipStreamSynchronize(s));
+                DPCG_TRY(fetch(h_flags.data(), d_flags.p, h_flags.size(), s));
                 static const int nt_knob = [] { const char *e = getenv("DPCG_SWEEP_NT"); return e ? atoi(e) : -1; }();
                 lv.sweep_nt = nt_knob >= 0 ? nt_knob != 0 : 10.0 * (double)nnz + 40.0 * (double)n >= 256e6;   // (measured: 160^3 -2.4 %, 256^3 -1.7 % per update)
                 lv.sw_max_chunks.assign((size_t)lv.n_levels, 0);
@@ -484,8 +470,7 @@ int build_levels(Levels &lv, LevelSort &ls, int64_t n, int64_t nnz, const int32_
             launch_count_long_rows(n, lv.lo_rowptr, 3, n_long.p, s);
             launch_count_long_rows(n, lv.lo_rowptr, 6, n_long.p + 1, s);
             int32_t h_long[2] = {0, 0};
-            DPCG_HIP(hipMemcpyAsync(h_long, n_long.p, sizeof(h_long), hipMemcpyDeviceToHost, s));
-            DPCG_HIP(hipStreamSynchronize(s));
+            DPCG_TRY(fetch(h_long, n_long.p, 2, s));
             lv.rec_w = (int64_t)h_long[1] * 50 > n ? 14 : ((int64_t)h_long[0] * 50 > n ? 6 : 3);
             const int64_t stride = lv.rec_w == 14 ? 16 : (lv.rec_w == 6 ? 8 : 4);
             DPCG_TRY(dev_alloc(&lv.sf_meta, n * stride));
@@ -524,8 +509,7 @@ int build_levels(Levels &lv, LevelSort &ls, int64_t n, int64_t nnz, const int32_
                 DPCG_HIP(hipMemsetAsync(most.p, 0, sizeof(int32_t), s));
                 launch_sfs_block_max(lv.sfs_blk, nblk, lv.lo_rowptr, reinterpret_cast<int *>(most.p), s);
                 int32_t h_most = 0;
-                DPCG_HIP(hipMemcpyAsync(&h_most, most.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-                DPCG_HIP(hipStreamSynchronize(s));       // (blk is a local)
+                DPCG_TRY(fetch(&h_most, most.p, 1, s));       // (blk is a local)
                 if (h_most > kStreamCap / kBlock * kSfsBlock) dev_free(lv.sfs_blk);      // a block's entries do not fit the product buffer: records
                 else lv.sfs_nblk = nblk;
             }
@@ -582,8 +566,7 @@ int build_strips(Levels &lv, int64_t n, int64_t nnz, const int32_t *rp, const in
     // strip-local level back and not dozens
     launch_max_band(n, rp, ci, upper, reinterpret_cast<int *>(ctl.p + 4), s);
     int32_t bands[2] = {0, 0};
-    DPCG_HIP(hipMemcpyAsync(bands, ctl.p + 4, sizeof(bands), hipMemcpyDeviceToHost, s));
-    DPCG_HIP(hipStreamSynchronize(s));
+    DPCG_TRY(fetch(bands, ctl.p + 4, 2, s));
     const int32_t band = bands[0] < 1 ? 1 : bands[0], inner = bands[1] < 1 ? 1 : bands[1];
     if (!levels_known && (int64_t)band * 32 > n) return DPCG_OK;
     // One attempt at a plan for a given strip map; leaves lv.strips.n_strips = 0 when the plan is not kept.
@@ -593,8 +576,7 @@ int build_strips(Levels &lv, int64_t n, int64_t nnz, const int32_t *rp, const in
         launch_levels_syncfree(n, rp, ci, upper, level.p, reinterpret_cast<unsigned int *>(ctl.p), ctl.p + 1, s, map);
         DPCG_TRY(reduce_max_i32(level.p, ctl.p + 2, n, s));
         int32_t h_ctl[8] = {0};
-        DPCG_HIP(hipMemcpyAsync(h_ctl, ctl.p, sizeof(h_ctl), hipMemcpyDeviceToHost, s));
-        DPCG_HIP(hipStreamSynchronize(s));
+        DPCG_TRY(fetch(h_ctl, ctl.p, 8, s));
         if (h_ctl[1] || h_ctl[2] < 0) return DPCG_OK;            // (cannot happen: the global analysis succeeded)
         const int nlev = h_ctl[2] + 1;
         if ((int64_t)S * nlev > (int64_t)1 << 24) return DPCG_OK;
@@ -617,8 +599,7 @@ int build_strips(Levels &lv, int64_t n, int64_t nnz, const int32_t *rp, const in
         DPCG_TRY(sort_pairs_u32_i32(key.p, key_sorted.p, iota.p, sp.rows, n, bits_for((uint64_t)(S * nlev)), s));
         launch_group_offsets(n, key_sorted.p, (int)(S * nlev), sp.level_ptr_dev, s);
         std::vector<int32_t> lptr((size_t)(S * nlev) + 1);
-        DPCG_HIP(hipMemcpyAsync(lptr.data(), sp.level_ptr_dev, lptr.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        DPCG_HIP(hipStreamSynchronize(s));
+        DPCG_TRY(fetch(lptr.data(), sp.level_ptr_dev, lptr.size(), s));
         int width = 0;
         for (size_t q = 0; q + 1 < lptr.size(); ++q) width = std::max(width, lptr[q + 1] - lptr[q]);
         if (width > 1024) {
@@ -647,8 +628,7 @@ int build_strips(Levels &lv, int64_t n, int64_t nnz, const int32_t *rp, const in
         DPCG_HIP(hipMemsetAsync(exported.p, 0, (size_t)n * sizeof(int32_t), s));
         launch_strip_records(n, key_sorted.p, nlev, sp.level_ptr_dev, sp.rows, sp.lo_rowptr, sp.lo_col, sp.lo_cpos, sp.lo_val, upper,
                              kRingReach, sp.meta, sp.val, exported.p, reinterpret_cast<int *>(ctl.p), s);
-        DPCG_HIP(hipMemcpyAsync(h_ctl, ctl.p, sizeof(h_ctl), hipMemcpyDeviceToHost, s));
-        DPCG_HIP(hipStreamSynchronize(s));
+        DPCG_TRY(fetch(h_ctl, ctl.p, 8, s));
         DPCG_CHECK_LAUNCH();
         const int64_t reach = h_ctl[0], external = h_ctl[1], offdiag = nnz - n;
         if (h_ctl[3] > 0) {                                       // an entry in a LATER strip: tickets could not guarantee progress
@@ -689,8 +669,7 @@ int build_strips(Levels &lv, int64_t n, int64_t nnz, const int32_t *rp, const in
     if (two_way && band >= 128 && want >= 8) {
         DPCG_HIP(hipMemsetAsync(ctl.p + 6, 0, sizeof(int32_t), s));
         launch_points_along_band(n, rp, ci, upper, band, reinterpret_cast<int *>(ctl.p + 6), s);
-        DPCG_HIP(hipMemcpyAsync(&along, ctl.p + 6, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        DPCG_HIP(hipStreamSynchronize(s));
+        DPCG_TRY(fetch(&along, ctl.p + 6, 1, s));
     }
     if (two_way && band >= 128 && want >= 8 && !along) {
         int parts = (int)std::llround(std::sqrt((double)want));
@@ -730,15 +709,11 @@ int build_strips(Levels &lv, int64_t n, int64_t nnz, const int32_t *rp, const in
     return DPCG_OK;
 }
 
-// L^T as CSR (columns ascending, diagonal first): stable sort of the entries by column.
+// L^T as an owned CSR (columns ascending, diagonal first)
 int transpose_lower(const CsrDev &L, CsrDev &Lt, hipStream_t s) {
     const int64_t n = L.n, nnz = L.nnz;
-    DevBuf<int32_t> row_of, order_in, order;
-    DevBuf<uint32_t> cols_sorted;
-    DPCG_TRY(row_of.alloc(nnz));
-    DPCG_TRY(order_in.alloc(nnz));
+    DevBuf<int32_t> order;
     DPCG_TRY(order.alloc(nnz));
-    DPCG_TRY(cols_sorted.alloc(nnz));
     Lt = CsrDev();
     Lt.n = n;
     Lt.nnz = nnz;
@@ -746,12 +721,7 @@ int transpose_lower(const CsrDev &L, CsrDev &Lt, hipStream_t s) {
     DPCG_TRY(dev_alloc(&Lt.rowptr, n + 1));
     DPCG_TRY(dev_alloc(&Lt.col, nnz));
     DPCG_TRY(dev_alloc(&Lt.val, nnz));
-    launch_row_of(n, L.rowptr, row_of.p, s);
-    launch_iota(nnz, order_in.p, s);
-    DPCG_TRY(sort_pairs_u32_i32(reinterpret_cast<const uint32_t *>(L.col), cols_sorted.p, order_in.p, order.p, nnz,
-                                bits_for((uint64_t)(n - 1)), s));
-    launch_group_offsets(nnz, cols_sorted.p, (int)n, Lt.rowptr, s);
-    launch_transpose_gather(nnz, order.p, row_of.p, L.val, Lt.col, Lt.val, s);
+    DPCG_TRY(transpose_csr(n, n, nnz, L.rowptr, L.col, L.val, Lt.rowptr, Lt.col, Lt.val, order.p, s));
     DPCG_HIP(hipStreamSynchronize(s));
     DPCG_CHECK_LAUNCH();
     return DPCG_OK;
@@ -769,8 +739,7 @@ int schedule_factor(int64_t n, Levels &lv, LevelSort &ls, const CsrDev &F, bool 
     DPCG_HIP(hipMemsetAsync(n_long.p, 0, sizeof(int32_t), s));
     launch_count_long_rows(n, F.rowptr, 3, n_long.p, s);
     int32_t h_long = 0;
-    DPCG_HIP(hipMemcpyAsync(&h_long, n_long.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    DPCG_HIP(hipStreamSynchronize(s));
+    DPCG_TRY(fetch(&h_long, n_long.p, 1, s));
     // (DPCG_LONG_ROW_PCT: development knob for that share, in per cent)
     static const int64_t pct = [] { const char *e = getenv("DPCG_LONG_ROW_PCT"); return e ? (int64_t)atoll(e) : (int64_t)2; }();
     const bool long_rows = (int64_t)h_long * 100 > n * pct;
@@ -1015,8 +984,7 @@ int refresh_parked_ic0(dpcg_system *h, hipStream_t s) {
     launch_lo_values(n, P.rows_u, P.Lt.rowptr, P.Lt.val, P.lvlU.lo_rowptr, P.lvlU.lo_val, s);
     if (P.lvlL.ride_diag) launch_scatter_f64(lp[1], P.lvlL.rows, P.lvlL.lo_val, P.lvlL.ride_diag, s);
     int32_t h_bad = 0;
-    DPCG_HIP(hipMemcpyAsync(&h_bad, bad.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    DPCG_HIP(hipStreamSynchronize(s));
+    DPCG_TRY(fetch(&h_bad, bad.p, 1, s));
     DPCG_CHECK_LAUNCH();
     pt.mark("refresh: values");
     if (h_bad) {

@@ -1,6 +1,10 @@
-// Device-wide sort / scan primitives used by the setup routines (COO -> CSR, transpose, level sets, reordering).
-// Thin, non-template entry points over rocPRIM, compiled once in dpcg_prims.hip; every call allocates its own scratch
-// (setup paths only -- nothing here runs inside the PCG iteration).  All return a dpcg_status.
+// Building blocks of the setup routines (COO -> CSR, transpose, level sets, reordering, every preconditioner setup), compiled once in
+// dpcg_prims.hip:
+//   * device-wide sort / scan / reduce: thin, non-template entry points over rocPRIM; every call allocates its own scratch;
+//   * the generic index kernels (iota, row of an entry, group offsets, inverse and composed maps, relabel, gather / scatter);
+//   * transpose_csr, the CSR transpose every factor and prolongation goes through.
+// Setup paths only -- nothing here runs inside the PCG iteration except the gathers / scatters of a reordered handle's vectors.
+// The routines that can fail return a dpcg_status.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -27,5 +31,30 @@ inline int bits_for(uint64_t max_value) {
     while (b < 64 && (max_value >> b) != 0) ++b;
     return b;
 }
+
+// ---- index kernels -----------------------------------------------------------------------------------------------------------
+void launch_iota(int64_t count, int32_t *out, hipStream_t s);                                           // out[k] = k
+void launch_row_of(int64_t n, const int32_t *rp, int32_t *row_of, hipStream_t s);                       // row_of[k] = the row of entry k
+// ptr[g] = first position with key >= g in a SORTED key array, g = 0 .. groups (ptr[groups] = count)
+void launch_group_offsets(int64_t count, const uint32_t *keys_sorted, int groups, int32_t *ptr, hipStream_t s);
+// tcol[d] = row_of[perm[d]], tval[d] = val[perm[d]]
+void launch_transpose_gather(int64_t nnz, const int32_t *perm, const int32_t *row_of, const double *val, int32_t *tcol,
+                             double *tval, hipStream_t s);
+void launch_invert_positions(int64_t n, const int32_t *rows, int32_t *pos, hipStream_t s);          // pos[rows[j]] = j
+void launch_compose_positions(int64_t n, const int32_t *rows, const int32_t *pos, int32_t *out, hipStream_t s);   // out[j] = pos[rows[j]]
+void launch_relabel(int64_t count, const int32_t *map, int32_t *idx, hipStream_t s);                    // idx[k] = map[idx[k]]
+void launch_same_i32(int64_t count, const int32_t *a, const int32_t *b, int *differ_flag, hipStream_t s);   // *differ_flag = 1 where a[k] != b[k]
+void launch_gather_f64(int64_t n, const int32_t *perm, const double *in, double *out, hipStream_t s);    // out[r] = in[perm[r]]
+void launch_scatter_f64(int64_t n, const int32_t *perm, const double *in, double *out, hipStream_t s);   // out[perm[r]] = in[r]
+void launch_gather_f32(int64_t n, const int32_t *perm, const float *in, float *out, hipStream_t s);
+void launch_scatter_f32(int64_t n, const int32_t *perm, const float *in, float *out, hipStream_t s);
+
+// B = A^T as CSR by a stable sort of A's entries by column: the rows of A ascend inside every row of B (for a lower factor with
+// the diagonal last, B has it first).  A: rows x cols, nnz entries.  order[d] = the entry of A that entry d of B is (always written).
+// out_val / val may both be null: pattern only.  Enqueues on s, does not synchronise.  Its temporaries are freed on return, while
+// the last kernels may still read them: a freed block is reused only by the same SetupScope on the same stream, and outside a
+// scope a free waits for the device (dpcg_mem.hip).
+int transpose_csr(int64_t rows, int64_t cols, int64_t nnz, const int32_t *rp, const int32_t *ci, const double *val,
+                  int32_t *out_rp, int32_t *out_ci, double *out_val, int32_t *order, hipStream_t s);
 
 }  // namespace dpcg

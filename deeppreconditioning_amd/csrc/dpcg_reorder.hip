@@ -25,11 +25,7 @@ namespace {
 constexpr int kMaxComponents = 64;
 constexpr int kBfsGrid = 512;        // persistent-style grid of a frontier step
 constexpr int kBfsBatch = 64;        // frontier steps enqueued between two looks at the frontier sizes
-
-inline int rows_grid(int64_t n, int cap = 8192) {
-    int64_t g = (n + kBlock - 1) / kBlock;
-    return (int)(g < 1 ? 1 : (g > cap ? cap : g));
-}
+constexpr int kReorderGrid = 8192;   // most workgroups of a kernel over rows (the ones that use atomics or walk neighbours pass less)
 
 __global__ __launch_bounds__(kBlock) void k_degrees(int64_t n, const int32_t *__restrict__ rp, int32_t *__restrict__ deg) {
     const int64_t stride = (int64_t)gridDim.x * kBlock;
@@ -439,25 +435,6 @@ __global__ __launch_bounds__(kBlock) void k_perm_rows(int64_t n, const int32_t *
     }
 }
 
-template <typename T>
-__global__ __launch_bounds__(kBlock) void k_gather_vec(int64_t n, const int32_t *__restrict__ perm, const T *__restrict__ in,
-                                                       T *__restrict__ out) {
-    const int64_t stride = (int64_t)gridDim.x * kBlock;
-    for (int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x; r < n; r += stride) out[r] = in[perm[r]];
-}
-
-template <typename T>
-__global__ __launch_bounds__(kBlock) void k_scatter_vec(int64_t n, const int32_t *__restrict__ perm, const T *__restrict__ in,
-                                                        T *__restrict__ out) {
-    const int64_t stride = (int64_t)gridDim.x * kBlock;
-    for (int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x; r < n; r += stride) out[perm[r]] = in[r];
-}
-
-__global__ __launch_bounds__(kBlock) void k_relabel(int64_t count, const int32_t *__restrict__ map, int32_t *__restrict__ idx) {
-    const int64_t stride = (int64_t)gridDim.x * kBlock;
-    for (int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x; k < count; k += stride) idx[k] = map[idx[k]];
-}
-
 // Locality of the x gather: distinct 128-byte lines of x (16 doubles) that the columns of each 256-row block touch,
 // summed over the blocks.  One workgroup per block, an open-addressing set in LDS.
 constexpr int kLineSetSlots = 8192;
@@ -493,48 +470,21 @@ __global__ __launch_bounds__(kBlock) void k_block_lines(int64_t n, const int32_t
     }
 }
 
-template <typename T>
-struct Buf {
-    T *p = nullptr;
-    Buf() = default;
-    Buf(const Buf &) = delete;
-    Buf &operator=(const Buf &) = delete;
-    ~Buf() { dev_free(p); }
-    int alloc(int64_t count) { dev_free(p); return dev_alloc(&p, count); }
-    T *release() { T *q = p; p = nullptr; return q; }
-};
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------------------------
-void launch_gather_f64(int64_t n, const int32_t *perm, const double *in, double *out, hipStream_t s) {
-    hipLaunchKernelGGL(k_gather_vec<double>, dim3(rows_grid(n, 2048)), dim3(kBlock), 0, s, n, perm, in, out);
-}
-void launch_scatter_f64(int64_t n, const int32_t *perm, const double *in, double *out, hipStream_t s) {
-    hipLaunchKernelGGL(k_scatter_vec<double>, dim3(rows_grid(n, 2048)), dim3(kBlock), 0, s, n, perm, in, out);
-}
-void launch_gather_f32(int64_t n, const int32_t *perm, const float *in, float *out, hipStream_t s) {
-    hipLaunchKernelGGL(k_gather_vec<float>, dim3(rows_grid(n, 2048)), dim3(kBlock), 0, s, n, perm, in, out);
-}
-void launch_scatter_f32(int64_t n, const int32_t *perm, const float *in, float *out, hipStream_t s) {
-    hipLaunchKernelGGL(k_scatter_vec<float>, dim3(rows_grid(n, 2048)), dim3(kBlock), 0, s, n, perm, in, out);
-}
-void launch_relabel(int64_t count, const int32_t *map, int32_t *idx, hipStream_t s) {
-    hipLaunchKernelGGL(k_relabel, dim3(rows_grid(count)), dim3(kBlock), 0, s, count, map, idx);
-}
-
 // lines * 128 bytes fetched for the x gather per byte of x values used: ~1 for banded blocks, 16 when every column is
 // its own line
 int gather_line_ratio(const CsrDev &A, double *ratio, hipStream_t s) {
     *ratio = 0.0;
     if (A.nnz <= 0) return DPCG_OK;
-    Buf<unsigned long long> total;
+    DevBuf<unsigned long long> total;
     DPCG_TRY(total.alloc(1));
     DPCG_HIP(hipMemsetAsync(total.p, 0, sizeof(unsigned long long), s));
     const int nrb = (int)((A.n + kStreamRows - 1) / kStreamRows);
     hipLaunchKernelGGL(k_block_lines, dim3(nrb < 4096 ? nrb : 4096), dim3(kBlock), 0, s, A.n, A.rowptr, A.col, nrb, total.p);
     unsigned long long h = 0;
-    DPCG_HIP(hipMemcpyAsync(&h, total.p, sizeof(h), hipMemcpyDeviceToHost, s));
-    DPCG_HIP(hipStreamSynchronize(s));
+    DPCG_TRY(fetch(&h, total.p, 1, s));
     DPCG_CHECK_LAUNCH();
     *ratio = (double)h * 128.0 / ((double)A.nnz * 8.0);
     return DPCG_OK;
@@ -547,14 +497,14 @@ int permute_csr(const CsrDev &A, const int32_t *perm, const int32_t *iperm, CsrD
     B.n = n;
     B.nnz = A.nnz;
     B.owned = true;
-    Buf<int32_t> len;
+    DevBuf<int32_t> len;
     DPCG_TRY(len.alloc(n + 1));
     DPCG_TRY(dev_alloc(&B.rowptr, n + 1));
     DPCG_TRY(dev_alloc(&B.col, A.nnz));
     DPCG_TRY(dev_alloc(&B.val, A.nnz));
-    hipLaunchKernelGGL(k_perm_lengths, dim3(rows_grid(n + 1)), dim3(kBlock), 0, s, n, perm, A.rowptr, len.p);
+    hipLaunchKernelGGL(k_perm_lengths, dim3(grid_blocks(n + 1, kReorderGrid)), dim3(kBlock), 0, s, n, perm, A.rowptr, len.p);
     DPCG_TRY(exclusive_scan_i32(len.p, B.rowptr, n + 1, s));
-    hipLaunchKernelGGL(k_perm_rows, dim3(rows_grid(n)), dim3(kBlock), 0, s, n, perm, iperm, A.rowptr, A.col, A.val, B.rowptr,
+    hipLaunchKernelGGL(k_perm_rows, dim3(grid_blocks(n, kReorderGrid)), dim3(kBlock), 0, s, n, perm, iperm, A.rowptr, A.col, A.val, B.rowptr,
                        B.col, B.val);
     DPCG_HIP(hipStreamSynchronize(s));
     DPCG_CHECK_LAUNCH();
@@ -568,7 +518,7 @@ int bfs(const CsrDev &A, int root, int L0, int at, int32_t *level, int32_t *orde
         std::vector<int32_t> &h_start, std::vector<int32_t> &h_count, int *n_levels, hipStream_t s) {
     hipLaunchKernelGGL(k_bfs_seed, dim3(1), dim3(64), 0, s, root, L0, at, level, order, start, count);
     static const bool narrow_on = [] { const char *e = getenv("DPCG_RCM_NARROW"); return !(e && e[0] == '0'); }();   // development knob
-    Buf<int> where;
+    DevBuf<int> where;
     DPCG_TRY(where.alloc(2));
     int L = L0;
     int32_t last = 1;                                      // width of level L (the seed)
@@ -580,8 +530,7 @@ int bfs(const CsrDev &A, int root, int L0, int at, int32_t *level, int32_t *orde
             hipLaunchKernelGGL(k_bfs_narrow, dim3(1), dim3(1024), 0, s, A.rowptr, A.col, level, order, start, count, L, (int)A.n + 1, cap,
                                where.p);
             int h_where[2] = {0, 0};
-            DPCG_HIP(hipMemcpyAsync(h_where, where.p, sizeof(h_where), hipMemcpyDeviceToHost, s));
-            DPCG_HIP(hipStreamSynchronize(s));
+            DPCG_TRY(fetch(h_where, where.p, 2, s));
             L = h_where[0];
             last = h_where[1];
             if (last == 0 || (int64_t)L >= A.n + 1) break;
@@ -589,8 +538,7 @@ int bfs(const CsrDev &A, int root, int L0, int at, int32_t *level, int32_t *orde
         for (int b = 0; b < kBfsBatch; ++b)
             hipLaunchKernelGGL(k_bfs_step, dim3(kBfsGrid), dim3(kBlock), 0, s, A.rowptr, A.col, level, order, start, count, L + b);
         L += kBfsBatch;
-        DPCG_HIP(hipMemcpyAsync(&last, count + L, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        DPCG_HIP(hipStreamSynchronize(s));
+        DPCG_TRY(fetch(&last, count + L, 1, s));
         if (last == 0 || (int64_t)L >= A.n + 1) break;
     }
     const int span = L - L0 + 1;
@@ -611,9 +559,9 @@ int bfs(const CsrDev &A, int root, int L0, int at, int32_t *level, int32_t *orde
 int rcm_order(const CsrDev &A, int32_t **perm_out, int32_t **iperm_out, int *n_components, hipStream_t s) {
     const int64_t n = A.n;
     if (n + 2 + kBfsBatch > 2147483000LL) return invalid("reordering: system too large");
-    Buf<int32_t> deg, level, order, start, count, pos, vertex_at, key, child, base, perm, iperm;
-    Buf<unsigned long long> best;
-    Buf<int> err;
+    DevBuf<int32_t> deg, level, order, start, count, pos, vertex_at, key, child, base, perm, iperm;
+    DevBuf<unsigned long long> best;
+    DevBuf<int> err;
     DPCG_TRY(err.alloc(1));
     DPCG_HIP(hipMemsetAsync(err.p, 0, sizeof(int), s));
     const int64_t nlv = n + 2 + 2 * kBfsBatch;
@@ -621,18 +569,17 @@ int rcm_order(const CsrDev &A, int32_t **perm_out, int32_t **iperm_out, int *n_c
     DPCG_TRY(count.alloc(nlv)); DPCG_TRY(pos.alloc(n)); DPCG_TRY(vertex_at.alloc(n + 1)); DPCG_TRY(key.alloc(n));
     DPCG_TRY(child.alloc(n + 1)); DPCG_TRY(base.alloc(n + 1)); DPCG_TRY(perm.alloc(n)); DPCG_TRY(iperm.alloc(n));
     DPCG_TRY(best.alloc(1));
-    hipLaunchKernelGGL(k_degrees, dim3(rows_grid(n)), dim3(kBlock), 0, s, n, A.rowptr, deg.p);
+    hipLaunchKernelGGL(k_degrees, dim3(grid_blocks(n, kReorderGrid)), dim3(kBlock), 0, s, n, A.rowptr, deg.p);
     DPCG_HIP(hipMemsetAsync(level.p, 0xff, (size_t)n * sizeof(int32_t), s));
     DPCG_HIP(hipMemsetAsync(count.p, 0, (size_t)nlv * sizeof(int32_t), s));
     DPCG_HIP(hipMemsetAsync(child.p, 0, (size_t)(n + 1) * sizeof(int32_t), s));
     DPCG_HIP(hipMemsetAsync(pos.p, 0xff, (size_t)n * sizeof(int32_t), s));      // -1: not placed
     auto min_degree = [&](const int32_t *list, int64_t lo, int64_t hi, int only_unvisited, int *v) -> int {
         DPCG_HIP(hipMemsetAsync(best.p, 0xff, sizeof(unsigned long long), s));
-        hipLaunchKernelGGL(k_min_degree, dim3(rows_grid(hi - lo, 1024)), dim3(kBlock), 0, s, list, lo, hi, deg.p, level.p,
+        hipLaunchKernelGGL(k_min_degree, dim3(grid_blocks(hi - lo, 1024)), dim3(kBlock), 0, s, list, lo, hi, deg.p, level.p,
                            only_unvisited, best.p);
         unsigned long long h = 0;
-        DPCG_HIP(hipMemcpyAsync(&h, best.p, sizeof(h), hipMemcpyDeviceToHost, s));
-        DPCG_HIP(hipStreamSynchronize(s));
+        DPCG_TRY(fetch(&h, best.p, 1, s));
         *v = h == ~0ull ? -1 : (int)(h & 0xffffffffu);
         return DPCG_OK;
     };
@@ -709,7 +656,7 @@ int rcm_order(const CsrDev &A, int32_t **perm_out, int32_t **iperm_out, int *n_c
             }
             const int L = c.L0 + l, s1 = c.start[(size_t)l], c1 = c.count[(size_t)l];
             const int s0 = c.start[(size_t)l - 1], c0 = c.count[(size_t)l - 1];
-            const int g = rows_grid(c1, 1024);
+            const int g = grid_blocks(c1, 1024);
             hipLaunchKernelGGL(k_cm_keys, dim3(g), dim3(kBlock), 0, s, A.rowptr, A.col, level.p, order.p, pos.p, key.p, child.p,
                                s1, c1, L, err.p);
             hipLaunchKernelGGL(k_scan_range, dim3(1), dim3(1024), 0, s, child.p, base.p, s0, c0);
@@ -719,23 +666,22 @@ int rcm_order(const CsrDev &A, int32_t **perm_out, int32_t **iperm_out, int *n_c
     }
     pt.mark("  RCM: positions");
     if (visited < n) {   // more components than searches: the rest keeps its relative order at the end
-        Buf<int32_t> flag, offs;
+        DevBuf<int32_t> flag, offs;
         DPCG_TRY(flag.alloc(n));
         DPCG_TRY(offs.alloc(n));
-        hipLaunchKernelGGL(k_flag_unvisited, dim3(rows_grid(n)), dim3(kBlock), 0, s, n, level.p, flag.p);
+        hipLaunchKernelGGL(k_flag_unvisited, dim3(grid_blocks(n, kReorderGrid)), dim3(kBlock), 0, s, n, level.p, flag.p);
         DPCG_TRY(exclusive_scan_i32(flag.p, offs.p, n, s));
-        hipLaunchKernelGGL(k_place_unvisited, dim3(rows_grid(n)), dim3(kBlock), 0, s, n, level.p, offs.p, visited, pos.p);
+        hipLaunchKernelGGL(k_place_unvisited, dim3(grid_blocks(n, kReorderGrid)), dim3(kBlock), 0, s, n, level.p, offs.p, visited, pos.p);
     }
     // pos[] of a vertex that was never placed is whatever the allocation held: start from an invalid value
     DPCG_HIP(hipMemsetAsync(perm.p, 0xff, (size_t)n * sizeof(int32_t), s));
     DPCG_HIP(hipMemsetAsync(iperm.p, 0xff, (size_t)n * sizeof(int32_t), s));
-    hipLaunchKernelGGL(k_finish_perm, dim3(rows_grid(n)), dim3(kBlock), 0, s, n, pos.p, perm.p, iperm.p, err.p);
+    hipLaunchKernelGGL(k_finish_perm, dim3(grid_blocks(n, kReorderGrid)), dim3(kBlock), 0, s, n, pos.p, perm.p, iperm.p, err.p);
     // The construction yields a permutation for a structurally symmetric pattern without duplicate entries; it is CHECKED,
     // not assumed: a one-sided entry leaves a vertex without a parent, a duplicated column ranks two siblings alike.
-    hipLaunchKernelGGL(k_check_perm, dim3(rows_grid(n)), dim3(kBlock), 0, s, n, perm.p, iperm.p, err.p);
+    hipLaunchKernelGGL(k_check_perm, dim3(grid_blocks(n, kReorderGrid)), dim3(kBlock), 0, s, n, perm.p, iperm.p, err.p);
     int bad = 0;
-    DPCG_HIP(hipMemcpyAsync(&bad, err.p, sizeof(int), hipMemcpyDeviceToHost, s));
-    DPCG_HIP(hipStreamSynchronize(s));
+    DPCG_TRY(fetch(&bad, err.p, 1, s));
     DPCG_CHECK_LAUNCH();
     if (bad)
         return invalid("reordering: the sparsity pattern is not structurally symmetric or has duplicate entries "
@@ -1215,11 +1161,6 @@ __global__ __launch_bounds__(kBlock) void k_mark_conflicts(int64_t n, const int3
     }
     if (mine) atomicAdd(marked, mine);
 }
-
-__global__ __launch_bounds__(kBlock) void k_invert_perm(int64_t n, const int32_t *__restrict__ perm, int32_t *__restrict__ iperm) {
-    const int64_t stride = (int64_t)gridDim.x * kBlock;
-    for (int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x; r < n; r += stride) iperm[perm[r]] = (int32_t)r;
-}
 }  // namespace
 
 // Two colours through regions (see k_region_seed).  *colored = true when `color` holds a proper 2-colouring in which the vertex
@@ -1239,27 +1180,27 @@ static int two_colors_by_regions(const CsrDev &A, int32_t *color, int *flags, bo
     bool odd_cycle = false;
     if (n < 4 * kRegions) return DPCG_OK;
     struct View { int32_t *p; } step{scratch[0]}, state{scratch[1]}, deg{scratch[2]}, mask{scratch[3]};   // (hipMalloc of 4 x 67 MB at 256^3: ~8 ms)
-    Buf<int32_t> d_small;
-    Buf<unsigned int> rel;
-    Buf<unsigned long long> best;
+    DevBuf<int32_t> d_small;
+    DevBuf<unsigned int> rel;
+    DevBuf<unsigned long long> best;
     DPCG_TRY(d_small.alloc(2 * kRegions)); DPCG_TRY(rel.alloc(2 * (int64_t)kRegions * kRegions)); DPCG_TRY(best.alloc(1));
     PhaseTimer pt(s);
     DPCG_HIP(hipMemsetAsync(step.p, 0xff, (size_t)n * sizeof(int32_t), s));
     DPCG_HIP(hipMemsetAsync(flags, 0, 4 * sizeof(int), s));
     // during the growth: cand in `deg`, the two fronts in `mask` and in `color` (all three are written afresh afterwards)
     int32_t *const cand = deg.p, *const front[2] = {mask.p, color};
-    Buf<int> front_n;
+    DevBuf<int> front_n;
     DPCG_TRY(front_n.alloc(4));
     DPCG_HIP(hipMemsetAsync(front_n.p, 0, 4 * sizeof(int), s));
     DPCG_HIP(hipMemsetAsync(cand, 0x7f, (size_t)n * sizeof(int32_t), s));
     hipLaunchKernelGGL(k_region_seed, dim3((kRegions + 63) / 64), dim3(64), 0, s, n, step.p, state.p, flags, kRegions, front[0], front_n.p);
     int visited = 0, cur = 0;
-    const int grow_grid = rows_grid(n / 4 + 1, 2048);
+    const int grow_grid = grid_blocks(n / 4 + 1, 2048);
     const bool from_front = n >= (1 << 21);       // (the same regions either way: measured 256^2 0.39 -> 0.57 ms from the front, 256^3 12.5 -> 8.2)
     for (;;) {
         for (int b = 0; b < kRegionBatch; ++b, ++cur) {
             if (!from_front) {
-                hipLaunchKernelGGL(k_region_grow, dim3(rows_grid(n, 2048)), dim3(kBlock), 0, s, n, A.rowptr, A.col, skip, step.p, state.p, cur,
+                hipLaunchKernelGGL(k_region_grow, dim3(grid_blocks(n, 2048)), dim3(kBlock), 0, s, n, A.rowptr, A.col, skip, step.p, state.p, cur,
                                    flags);
                 continue;
             }
@@ -1269,8 +1210,7 @@ static int two_colors_by_regions(const CsrDev &A, int32_t *color, int *flags, bo
                                flags);
         }
         int now = 0;
-        DPCG_HIP(hipMemcpyAsync(&now, flags, sizeof(int), hipMemcpyDeviceToHost, s));
-        DPCG_HIP(hipStreamSynchronize(s));
+        DPCG_TRY(fetch(&now, flags, 1, s));
         if (now == n) break;
         if (now == visited) {                        // a component without a seed
             if (skip && nearly && (int64_t)(n - now) * 8 <= n) break;     // (skipped edges: a few unreachable vertices are repaired later)
@@ -1281,16 +1221,15 @@ static int two_colors_by_regions(const CsrDev &A, int32_t *color, int *flags, bo
     }
     pt.mark("  regions: growth");
     DPCG_HIP(hipMemsetAsync(rel.p, 0, 2 * (size_t)kRegions * kRegions * sizeof(unsigned int), s));
-    hipLaunchKernelGGL(k_region_relations, dim3(rows_grid(n, 2048)), dim3(kBlock), 0, s, n, A.rowptr, A.col, skip, step.p, state.p, rel.p, kRegions);
-    Buf<int4> pairs;
-    Buf<int> n_pairs;
+    hipLaunchKernelGGL(k_region_relations, dim3(grid_blocks(n, 2048)), dim3(kBlock), 0, s, n, A.rowptr, A.col, skip, step.p, state.p, rel.p, kRegions);
+    DevBuf<int4> pairs;
+    DevBuf<int> n_pairs;
     DPCG_TRY(pairs.alloc((int64_t)kRegions * kRegions / 2));
     DPCG_TRY(n_pairs.alloc(1));
     DPCG_HIP(hipMemsetAsync(n_pairs.p, 0, sizeof(int), s));
-    hipLaunchKernelGGL(k_region_pairs, dim3(rows_grid((int64_t)kRegions * kRegions, 1024)), dim3(kBlock), 0, s, rel.p, kRegions, pairs.p, n_pairs.p);
+    hipLaunchKernelGGL(k_region_pairs, dim3(grid_blocks((int64_t)kRegions * kRegions, 1024)), dim3(kBlock), 0, s, rel.p, kRegions, pairs.p, n_pairs.p);
     int h_n_pairs = 0;
-    DPCG_HIP(hipMemcpyAsync(&h_n_pairs, n_pairs.p, sizeof(int), hipMemcpyDeviceToHost, s));
-    DPCG_HIP(hipStreamSynchronize(s));
+    DPCG_TRY(fetch(&h_n_pairs, n_pairs.p, 1, s));
     std::vector<int4> h_pairs((size_t)h_n_pairs);
     if (h_n_pairs) DPCG_HIP(hipMemcpyAsync(h_pairs.data(), pairs.p, h_pairs.size() * sizeof(int4), hipMemcpyDeviceToHost, s));
     DPCG_HIP(hipStreamSynchronize(s));
@@ -1338,36 +1277,33 @@ static int two_colors_by_regions(const CsrDev &A, int32_t *color, int *flags, bo
     std::vector<int32_t> h_small((size_t)2 * kRegions);
     for (int r = 0; r < kRegions; ++r) h_small[(size_t)r] = comp[(size_t)r];
     DPCG_HIP(hipMemcpyAsync(d_small.p, h_small.data(), kRegions * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_degrees, dim3(rows_grid(n)), dim3(kBlock), 0, s, n, A.rowptr, deg.p);
+    hipLaunchKernelGGL(k_degrees, dim3(grid_blocks(n, kReorderGrid)), dim3(kBlock), 0, s, n, A.rowptr, deg.p);
     int real_comps = 0;
     for (int c = 0; c < n_comp; ++c) {
         // the component's vertex of smallest (degree, index) gets colour 0
         DPCG_HIP(hipMemsetAsync(best.p, 0xff, sizeof(unsigned long long), s));
-        hipLaunchKernelGGL(k_region_mask, dim3(rows_grid(n)), dim3(kBlock), 0, s, n, step.p, state.p, d_small.p, c, mask.p);
-        hipLaunchKernelGGL(k_min_degree, dim3(rows_grid(n, 1024)), dim3(kBlock), 0, s, (const int32_t *)nullptr, (int64_t)0, n, deg.p, mask.p, 1,
+        hipLaunchKernelGGL(k_region_mask, dim3(grid_blocks(n, kReorderGrid)), dim3(kBlock), 0, s, n, step.p, state.p, d_small.p, c, mask.p);
+        hipLaunchKernelGGL(k_min_degree, dim3(grid_blocks(n, 1024)), dim3(kBlock), 0, s, (const int32_t *)nullptr, (int64_t)0, n, deg.p, mask.p, 1,
                            best.p);
         unsigned long long hb = 0;
-        DPCG_HIP(hipMemcpyAsync(&hb, best.p, sizeof(hb), hipMemcpyDeviceToHost, s));
-        DPCG_HIP(hipStreamSynchronize(s));
+        DPCG_TRY(fetch(&hb, best.p, 1, s));
         if (hb == ~0ull) continue;                                                 // an empty region
         if (++real_comps > 8) {                                                    // many components: the searches below handle them
             if (pt.on) fprintf(stderr, "[dpcg setup]   regions: more than 8 components\n");
             return DPCG_OK;
         }
         int32_t sv = 0;
-        DPCG_HIP(hipMemcpyAsync(&sv, state.p + (hb & 0xffffffffu), sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        DPCG_HIP(hipStreamSynchronize(s));
+        DPCG_TRY(fetch(&sv, state.p + (hb & 0xffffffffu), 1, s));
         if (((sv & 1) ^ flip[(size_t)(sv >> 1)]) != 0)
             for (int r = 0; r < kRegions; ++r)
                 if (comp[(size_t)r] == c) flip[(size_t)r] ^= 1;
     }
     DPCG_HIP(hipMemcpyAsync(d_small.p + kRegions, flip.data(), kRegions * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_region_colors, dim3(rows_grid(n)), dim3(kBlock), 0, s, n, step.p, state.p, d_small.p + kRegions, color);
+    hipLaunchKernelGGL(k_region_colors, dim3(grid_blocks(n, kReorderGrid)), dim3(kBlock), 0, s, n, step.p, state.p, d_small.p + kRegions, color);
     DPCG_HIP(hipMemsetAsync(flags, 0, 4 * sizeof(int), s));
-    hipLaunchKernelGGL(k_check_coloring, dim3(rows_grid(n)), dim3(kBlock), 0, s, n, A.rowptr, A.col, color, flags);
+    hipLaunchKernelGGL(k_check_coloring, dim3(grid_blocks(n, kReorderGrid)), dim3(kBlock), 0, s, n, A.rowptr, A.col, color, flags);
     int bad = 0;
-    DPCG_HIP(hipMemcpyAsync(&bad, flags, sizeof(int), hipMemcpyDeviceToHost, s));
-    DPCG_HIP(hipStreamSynchronize(s));
+    DPCG_TRY(fetch(&bad, flags, 1, s));
     *colored = bad == 0;
     if (nearly) *nearly = bad != 0;
     if (pt.on) fprintf(stderr, "[dpcg setup]   regions: %d components, odd cycle %d, proper %d\n", real_comps, (int)odd_cycle, (int)*colored);
@@ -1425,9 +1361,9 @@ int region_order(const CsrDev &A, int regions, int32_t **perm_out, int32_t **ipe
     const int64_t n = A.n;
     if (regions < 1 || regions > 4096 || n < regions) return invalid("region_order: 1 .. 4096 regions, not more than rows");
     PhaseTimer pt(s);
-    Buf<int32_t> step, state, cand, front0, front1, rank, vertex, perm, iperm;
-    Buf<uint32_t> key, key_sorted;
-    Buf<int> flags, front_n;
+    DevBuf<int32_t> step, state, cand, front0, front1, rank, vertex, perm, iperm;
+    DevBuf<uint32_t> key, key_sorted;
+    DevBuf<int> flags, front_n;
     DPCG_TRY(step.alloc(n)); DPCG_TRY(state.alloc(n)); DPCG_TRY(flags.alloc(4)); DPCG_TRY(front_n.alloc(4)); DPCG_TRY(rank.alloc(regions));
     DPCG_HIP(hipMemsetAsync(step.p, 0xff, (size_t)n * sizeof(int32_t), s));
     DPCG_HIP(hipMemsetAsync(flags.p, 0, 4 * sizeof(int), s));
@@ -1441,12 +1377,12 @@ int region_order(const CsrDev &A, int regions, int32_t **perm_out, int32_t **ipe
     DPCG_HIP(hipMemsetAsync(state.p, 0x7f, (size_t)n * sizeof(int32_t), s));
     hipLaunchKernelGGL(k_region_seed_min, dim3((regions + 63) / 64), dim3(64), 0, s, n, step.p, state.p, flags.p, regions, front0.p, front_n.p);
     int32_t *const front[2] = {front0.p, front1.p};
-    const int grow_grid = rows_grid(n / 4 + 1, 2048);
+    const int grow_grid = grid_blocks(n / 4 + 1, 2048);
     int visited = 0, cur = 0;
     for (;;) {
         for (int b = 0; b < kRegionBatch; ++b, ++cur) {
             if (!from_front) {
-                hipLaunchKernelGGL(k_region_grow, dim3(rows_grid(n, 2048)), dim3(kBlock), 0, s, n, A.rowptr, A.col, (const uint8_t *)nullptr,
+                hipLaunchKernelGGL(k_region_grow, dim3(grid_blocks(n, 2048)), dim3(kBlock), 0, s, n, A.rowptr, A.col, (const uint8_t *)nullptr,
                                    step.p, state.p, cur, flags.p);
                 continue;
             }
@@ -1456,8 +1392,7 @@ int region_order(const CsrDev &A, int regions, int32_t **perm_out, int32_t **ipe
                                cur, flags.p);
         }
         int now = 0;
-        DPCG_HIP(hipMemcpyAsync(&now, flags.p, sizeof(int), hipMemcpyDeviceToHost, s));
-        DPCG_HIP(hipStreamSynchronize(s));
+        DPCG_TRY(fetch(&now, flags.p, 1, s));
         if (now == n || now == visited) { visited = now; break; }     // (stalled: components without a seed stay at the end)
         visited = now;
     }
@@ -1465,19 +1400,18 @@ int region_order(const CsrDev &A, int regions, int32_t **perm_out, int32_t **ipe
     // the graph of regions, and its breadth-first order (neighbours ascending: the same from run to run)
     std::vector<int32_t> h_rank((size_t)regions, -1);
     {
-        Buf<unsigned int> rel;
-        Buf<int4> pairs;
-        Buf<int> n_pairs;
+        DevBuf<unsigned int> rel;
+        DevBuf<int4> pairs;
+        DevBuf<int> n_pairs;
         DPCG_TRY(rel.alloc(2 * (int64_t)regions * regions)); DPCG_TRY(pairs.alloc((int64_t)regions * regions / 2 + 1)); DPCG_TRY(n_pairs.alloc(1));
         DPCG_HIP(hipMemsetAsync(rel.p, 0, 2 * (size_t)regions * regions * sizeof(unsigned int), s));
         DPCG_HIP(hipMemsetAsync(n_pairs.p, 0, sizeof(int), s));
-        hipLaunchKernelGGL(k_region_relations, dim3(rows_grid(n, 2048)), dim3(kBlock), 0, s, n, A.rowptr, A.col, (const uint8_t *)nullptr, step.p,
+        hipLaunchKernelGGL(k_region_relations, dim3(grid_blocks(n, 2048)), dim3(kBlock), 0, s, n, A.rowptr, A.col, (const uint8_t *)nullptr, step.p,
                            state.p, rel.p, regions);
-        hipLaunchKernelGGL(k_region_pairs, dim3(rows_grid((int64_t)regions * regions, 1024)), dim3(kBlock), 0, s, rel.p, regions, pairs.p,
+        hipLaunchKernelGGL(k_region_pairs, dim3(grid_blocks((int64_t)regions * regions, 1024)), dim3(kBlock), 0, s, rel.p, regions, pairs.p,
                            n_pairs.p);
         int h_n_pairs = 0;
-        DPCG_HIP(hipMemcpyAsync(&h_n_pairs, n_pairs.p, sizeof(int), hipMemcpyDeviceToHost, s));
-        DPCG_HIP(hipStreamSynchronize(s));
+        DPCG_TRY(fetch(&h_n_pairs, n_pairs.p, 1, s));
         std::vector<int4> h_pairs((size_t)h_n_pairs);
         if (h_n_pairs) DPCG_HIP(hipMemcpyAsync(h_pairs.data(), pairs.p, h_pairs.size() * sizeof(int4), hipMemcpyDeviceToHost, s));
         DPCG_HIP(hipStreamSynchronize(s));
@@ -1504,11 +1438,11 @@ int region_order(const CsrDev &A, int regions, int32_t **perm_out, int32_t **ipe
     DPCG_HIP(hipMemcpyAsync(rank.p, h_rank.data(), (size_t)regions * sizeof(int32_t), hipMemcpyHostToDevice, s));
     pt.mark("  regions: graph of regions");
     DPCG_TRY(key.alloc(n)); DPCG_TRY(key_sorted.alloc(n)); DPCG_TRY(vertex.alloc(n)); DPCG_TRY(perm.alloc(n)); DPCG_TRY(iperm.alloc(n));
-    hipLaunchKernelGGL(k_region_keys, dim3(rows_grid(n, 2048)), dim3(kBlock), 0, s, n, step.p, state.p, rank.p, regions, key.p, vertex.p);
+    hipLaunchKernelGGL(k_region_keys, dim3(grid_blocks(n, 2048)), dim3(kBlock), 0, s, n, step.p, state.p, rank.p, regions, key.p, vertex.p);
     int bits = 9;
     while ((1 << (bits - 8)) <= regions) ++bits;
     DPCG_TRY(sort_pairs_u32_i32(key.p, key_sorted.p, vertex.p, perm.p, n, bits, s));      // (returns with the stream idle: h_rank may go)
-    hipLaunchKernelGGL(k_invert_perm, dim3(rows_grid(n, 2048)), dim3(kBlock), 0, s, n, perm.p, iperm.p);
+    launch_invert_positions(n, perm.p, iperm.p, s);
     DPCG_CHECK_LAUNCH();
     pt.mark("  regions: keys, sort");
     if (pt.on) fprintf(stderr, "[dpcg setup]   regions: %d regions, %d growth steps, %lld of %lld vertices reached\n", regions, cur, (long long)visited, (long long)n);
@@ -1521,9 +1455,9 @@ int multicolor_order(const CsrDev &A, int32_t **perm_out, int32_t **iperm_out, i
                      std::vector<int32_t> *offsets) {
     const int64_t n = A.n;
     if (n + 2 + kBfsBatch > 2147483000LL) return invalid("multicolour ordering: system too large");
-    Buf<int32_t> color, perm, iperm, iota;
-    Buf<uint32_t> key_sorted;
-    Buf<int> flags;
+    DevBuf<int32_t> color, perm, iperm, iota;
+    DevBuf<uint32_t> key_sorted;
+    DevBuf<int> flags;
     DPCG_TRY(color.alloc(n)); DPCG_TRY(perm.alloc(n)); DPCG_TRY(iperm.alloc(n)); DPCG_TRY(iota.alloc(n));
     DPCG_TRY(key_sorted.alloc(n)); DPCG_TRY(flags.alloc(4));
     bool colored = false;
@@ -1541,11 +1475,10 @@ int multicolor_order(const CsrDev &A, int32_t **perm_out, int32_t **iperm_out, i
     if (regions_on) {
         const int64_t stride_rows = n >= 4096 ? 64 : 1;
         DPCG_HIP(hipMemsetAsync(flags.p, 0, 4 * sizeof(int), s));
-        hipLaunchKernelGGL(k_triangle_sample, dim3(rows_grid((n + stride_rows - 1) / stride_rows, 256)), dim3(kBlock), 0, s, n, stride_rows,
+        hipLaunchKernelGGL(k_triangle_sample, dim3(grid_blocks((n + stride_rows - 1) / stride_rows, 256)), dim3(kBlock), 0, s, n, stride_rows,
                            A.rowptr, A.col, flags.p);
         int h_tri[2] = {0, 0};
-        DPCG_HIP(hipMemcpyAsync(h_tri, flags.p, sizeof(h_tri), hipMemcpyDeviceToHost, s));
-        DPCG_HIP(hipStreamSynchronize(s));
+        DPCG_TRY(fetch(h_tri, flags.p, 2, s));
         some = h_tri[1] > 0;
         far = (int64_t)h_tri[1] * 8 > (int64_t)h_tri[0];
         if (pt.on) fprintf(stderr, "[dpcg setup]   %d of %d sampled vertices on a triangle\n", h_tri[1], h_tri[0]);
@@ -1559,19 +1492,18 @@ int multicolor_order(const CsrDev &A, int32_t **perm_out, int32_t **iperm_out, i
         // 0b. nearly bipartite (odd cycles, but few): the regions once more without the edges that lie on triangles -- breadth-first
         // parity follows every shortcut, an extra coupling would flip the cone of vertices behind it -- then the two big classes stay
         // and the few vertices on conflicting edges are recoloured
-        Buf<uint8_t> skip;
+        DevBuf<uint8_t> skip;
         DPCG_TRY(skip.alloc(A.nnz));
-        hipLaunchKernelGGL(k_triangle_edges, dim3(rows_grid(n, 2048)), dim3(kBlock), 0, s, n, A.rowptr, A.col, skip.p);
+        hipLaunchKernelGGL(k_triangle_edges, dim3(grid_blocks(n, 2048)), dim3(kBlock), 0, s, n, A.rowptr, A.col, skip.p);
         nearly = false;
         DPCG_TRY(two_colors_by_regions(A, color.p, flags.p, &colored, &nearly, skip.p, s, scratch));
         pt.mark("  regions without triangle edges");
     }
     if (!colored && nearly) {
         DPCG_HIP(hipMemsetAsync(flags.p, 0, 4 * sizeof(int), s));
-        hipLaunchKernelGGL(k_mark_conflicts, dim3(rows_grid(n, 2048)), dim3(kBlock), 0, s, n, A.rowptr, A.col, color.p, iota.p, flags.p + 2);
+        hipLaunchKernelGGL(k_mark_conflicts, dim3(grid_blocks(n, 2048)), dim3(kBlock), 0, s, n, A.rowptr, A.col, color.p, iota.p, flags.p + 2);
         int marked = 0;
-        DPCG_HIP(hipMemcpyAsync(&marked, flags.p + 2, sizeof(int), hipMemcpyDeviceToHost, s));
-        DPCG_HIP(hipStreamSynchronize(s));
+        DPCG_TRY(fetch(&marked, flags.p + 2, 1, s));
         if (pt.on) fprintf(stderr, "[dpcg setup]   nearly two-coloured: %d of %lld vertices on conflicting edges\n", marked, (long long)n);
         if ((int64_t)marked * 8 <= n) {
             DPCG_HIP(hipMemcpyAsync(color.p, iota.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
@@ -1579,23 +1511,22 @@ int multicolor_order(const CsrDev &A, int32_t **perm_out, int32_t **iperm_out, i
         }
     }
     if (!colored && !repaired && !odd_proven) {   // 1. breadth-first parity, component by component (pointless once an odd cycle is known)
-        Buf<int32_t> deg, level, order, start, count;
-        Buf<unsigned long long> best;
+        DevBuf<int32_t> deg, level, order, start, count;
+        DevBuf<unsigned long long> best;
         const int64_t nlv = n + 2 + 2 * kBfsBatch;
         DPCG_TRY(deg.alloc(n)); DPCG_TRY(level.alloc(n)); DPCG_TRY(order.alloc(n + 1)); DPCG_TRY(start.alloc(nlv));
         DPCG_TRY(count.alloc(nlv)); DPCG_TRY(best.alloc(1));
-        hipLaunchKernelGGL(k_degrees, dim3(rows_grid(n)), dim3(kBlock), 0, s, n, A.rowptr, deg.p);
+        hipLaunchKernelGGL(k_degrees, dim3(grid_blocks(n, kReorderGrid)), dim3(kBlock), 0, s, n, A.rowptr, deg.p);
         DPCG_HIP(hipMemsetAsync(level.p, 0xff, (size_t)n * sizeof(int32_t), s));
         DPCG_HIP(hipMemsetAsync(count.p, 0, (size_t)nlv * sizeof(int32_t), s));
         std::vector<int32_t> h_start, h_count;
         int visited = 0, next_level = 0, searches = 0;
         while (visited < n && searches < kMaxComponents) {
             DPCG_HIP(hipMemsetAsync(best.p, 0xff, sizeof(unsigned long long), s));
-            hipLaunchKernelGGL(k_min_degree, dim3(rows_grid(n, 1024)), dim3(kBlock), 0, s, (const int32_t *)nullptr, (int64_t)0, n,
+            hipLaunchKernelGGL(k_min_degree, dim3(grid_blocks(n, 1024)), dim3(kBlock), 0, s, (const int32_t *)nullptr, (int64_t)0, n,
                                deg.p, level.p, 1, best.p);
             unsigned long long hb = 0;
-            DPCG_HIP(hipMemcpyAsync(&hb, best.p, sizeof(hb), hipMemcpyDeviceToHost, s));
-            DPCG_HIP(hipStreamSynchronize(s));
+            DPCG_TRY(fetch(&hb, best.p, 1, s));
             if (hb == ~0ull) break;
             int nl = 0;
             // every search starts at an EVEN level number, so that parity means the same in every component
@@ -1606,12 +1537,11 @@ int multicolor_order(const CsrDev &A, int32_t **perm_out, int32_t **iperm_out, i
             ++searches;
         }
         if (visited == n) {
-            hipLaunchKernelGGL(k_parity_colors, dim3(rows_grid(n)), dim3(kBlock), 0, s, n, level.p, color.p);
+            hipLaunchKernelGGL(k_parity_colors, dim3(grid_blocks(n, kReorderGrid)), dim3(kBlock), 0, s, n, level.p, color.p);
             DPCG_HIP(hipMemsetAsync(flags.p, 0, 4 * sizeof(int), s));
-            hipLaunchKernelGGL(k_check_coloring, dim3(rows_grid(n)), dim3(kBlock), 0, s, n, A.rowptr, A.col, color.p, flags.p);
+            hipLaunchKernelGGL(k_check_coloring, dim3(grid_blocks(n, kReorderGrid)), dim3(kBlock), 0, s, n, A.rowptr, A.col, color.p, flags.p);
             int bad = 0;
-            DPCG_HIP(hipMemcpyAsync(&bad, flags.p, sizeof(int), hipMemcpyDeviceToHost, s));
-            DPCG_HIP(hipStreamSynchronize(s));
+            DPCG_TRY(fetch(&bad, flags.p, 1, s));
             colored = bad == 0;
         }
         pt.mark("  breadth-first parity");
@@ -1620,8 +1550,8 @@ int multicolor_order(const CsrDev &A, int32_t **perm_out, int32_t **iperm_out, i
         if (!repaired) DPCG_HIP(hipMemsetAsync(color.p, 0xff, (size_t)n * sizeof(int32_t), s));
         DPCG_HIP(hipMemsetAsync(flags.p, 0, 4 * sizeof(int), s));
         // peel ranks for the greedy order (DPCG_COLOR_PEEL=0: the hashed order alone, as in round 3; changes the ORDERING)
-        Buf<int32_t> prank, pdeg;
-        Buf<int> pctl;
+        DevBuf<int32_t> prank, pdeg;
+        DevBuf<int> pctl;
         static const int peel_rounds = [] { const char *e = getenv("DPCG_COLOR_PEEL"); return e ? atoi(e) : 24; }();
         const int32_t *rank_dev = nullptr;
         if (!repaired && peel_rounds > 0) {
@@ -1630,11 +1560,11 @@ int multicolor_order(const CsrDev &A, int32_t **perm_out, int32_t **iperm_out, i
             DPCG_TRY(pctl.alloc(1));
             const int T = std::max(2, (int)(((A.nnz - n) + n / 2) / std::max<int64_t>(n, 1)) - 2);      // average degree (rounded) - 2
             DPCG_HIP(hipMemsetAsync(pctl.p, 0x7f, sizeof(int), s));
-            hipLaunchKernelGGL(k_peel_init, dim3(rows_grid(n, 1024)), dim3(kBlock), 0, s, n, A.rowptr, A.col, prank.p, pdeg.p, peel_rounds, pctl.p);
+            hipLaunchKernelGGL(k_peel_init, dim3(grid_blocks(n, 1024)), dim3(kBlock), 0, s, n, A.rowptr, A.col, prank.p, pdeg.p, peel_rounds, pctl.p);
             for (int r = 0; r < peel_rounds; ++r) {
-                hipLaunchKernelGGL(k_peel_mark, dim3(rows_grid(n, 1024)), dim3(kBlock), 0, s, n, pdeg.p, prank.p, r, peel_rounds, T, pctl.p);
+                hipLaunchKernelGGL(k_peel_mark, dim3(grid_blocks(n, 1024)), dim3(kBlock), 0, s, n, pdeg.p, prank.p, r, peel_rounds, T, pctl.p);
                 DPCG_HIP(hipMemsetAsync(pctl.p, 0x7f, sizeof(int), s));
-                hipLaunchKernelGGL(k_peel_degrees, dim3(rows_grid(n, 1024)), dim3(kBlock), 0, s, n, A.rowptr, A.col, prank.p, peel_rounds, pdeg.p, pctl.p);
+                hipLaunchKernelGGL(k_peel_degrees, dim3(grid_blocks(n, 1024)), dim3(kBlock), 0, s, n, A.rowptr, A.col, prank.p, peel_rounds, pdeg.p, pctl.p);
             }
             rank_dev = prank.p;
             pt.mark("  peel ranks");
@@ -1644,20 +1574,18 @@ int multicolor_order(const CsrDev &A, int32_t **perm_out, int32_t **iperm_out, i
             int h[2] = {0, 0};
             for (int b = 0; b < 4; ++b) {
                 DPCG_HIP(hipMemsetAsync(flags.p, 0, sizeof(int), s));            // [0] remaining after this round, [1] error
-                hipLaunchKernelGGL(k_jp_round, dim3(rows_grid(n, 2048)), dim3(kBlock), 0, s, n, A.rowptr, A.col, color.p, flags.p,
+                hipLaunchKernelGGL(k_jp_round, dim3(grid_blocks(n, 2048)), dim3(kBlock), 0, s, n, A.rowptr, A.col, color.p, flags.p,
                                    flags.p + 1, rank_dev);
                 ++rounds;
             }
-            DPCG_HIP(hipMemcpyAsync(h, flags.p, sizeof(h), hipMemcpyDeviceToHost, s));
-            DPCG_HIP(hipStreamSynchronize(s));
+            DPCG_TRY(fetch(h, flags.p, 2, s));
             if (h[1]) return invalid("multicolour ordering: a vertex needs more than 63 colours");
             if (h[0] == 0) break;
             if (rounds > 4096) return invalid("multicolour ordering: the colouring did not finish");
         }
-        hipLaunchKernelGGL(k_check_coloring, dim3(rows_grid(n)), dim3(kBlock), 0, s, n, A.rowptr, A.col, color.p, flags.p + 2);
+        hipLaunchKernelGGL(k_check_coloring, dim3(grid_blocks(n, kReorderGrid)), dim3(kBlock), 0, s, n, A.rowptr, A.col, color.p, flags.p + 2);
         int bad = 0;
-        DPCG_HIP(hipMemcpyAsync(&bad, flags.p + 2, sizeof(int), hipMemcpyDeviceToHost, s));
-        DPCG_HIP(hipStreamSynchronize(s));
+        DPCG_TRY(fetch(&bad, flags.p + 2, 1, s));
         if (bad) return invalid("multicolour ordering: improper colouring (is the pattern structurally symmetric?)");
         if (pt.on) fprintf(stderr, "[dpcg setup]   greedy colouring: %d rounds\n", rounds);
         pt.mark("  greedy rounds");
@@ -1665,69 +1593,65 @@ int multicolor_order(const CsrDev &A, int32_t **perm_out, int32_t **iperm_out, i
         // (not after a repair: the two big classes are what the repair is for)
         static const int passes_knob = [] { const char *e = getenv("DPCG_RECOLOR_PASSES"); return e ? atoi(e) : 3; }();
         const int passes = repaired ? 1 : passes_knob;
-        Buf<int> hist;
-        Buf<int32_t> map;
+        DevBuf<int> hist;
+        DevBuf<int32_t> map;
         DPCG_TRY(hist.alloc(64));
         DPCG_TRY(map.alloc(64));
         for (int pass = 0; pass < passes; ++pass) {
             DPCG_HIP(hipMemsetAsync(hist.p, 0, 64 * sizeof(int), s));
-            hipLaunchKernelGGL(k_color_histogram, dim3(rows_grid(n, 1024)), dim3(kBlock), 0, s, n, color.p, hist.p);
+            hipLaunchKernelGGL(k_color_histogram, dim3(grid_blocks(n, 1024)), dim3(kBlock), 0, s, n, color.p, hist.p);
             int h_hist[64];
-            DPCG_HIP(hipMemcpyAsync(h_hist, hist.p, sizeof(h_hist), hipMemcpyDeviceToHost, s));
-            DPCG_HIP(hipStreamSynchronize(s));
+            DPCG_TRY(fetch(h_hist, hist.p, 64, s));
             // empty classes are squeezed out, the others keep their order
             int32_t h_map[64];
             int used = 0;
             for (int c = 0; c < 64; ++c) h_map[c] = h_hist[c] > 0 ? used++ : 0;
             DPCG_HIP(hipMemcpyAsync(map.p, h_map, sizeof(h_map), hipMemcpyHostToDevice, s));
-            hipLaunchKernelGGL(k_remap_colors, dim3(rows_grid(n)), dim3(kBlock), 0, s, n, color.p, map.p);
+            hipLaunchKernelGGL(k_remap_colors, dim3(grid_blocks(n, kReorderGrid)), dim3(kBlock), 0, s, n, color.p, map.p);
             DPCG_HIP(hipStreamSynchronize(s));      // (h_map is on the stack)
             if (used <= 2 || pass == passes - 1) {
                 // a last class of a handful of vertices is folded into the others where a local move does (never more colours)
                 static const bool fold_on = [] { const char *e = getenv("DPCG_COLOR_FOLD"); return !(e && e[0] == '0'); }();
                 if (fold_on && used > 2 && h_hist_last_nonempty(h_hist) <= kFoldMax) {
-                    Buf<int> members;
+                    DevBuf<int> members;
                     DPCG_TRY(members.alloc(kFoldMax + 2));
                     DPCG_HIP(hipMemsetAsync(members.p, 0, sizeof(int), s));
-                    hipLaunchKernelGGL(k_collect_class, dim3(rows_grid(n, 1024)), dim3(kBlock), 0, s, n, color.p, used - 1, members.p, members.p + 1);
+                    hipLaunchKernelGGL(k_collect_class, dim3(grid_blocks(n, 1024)), dim3(kBlock), 0, s, n, color.p, used - 1, members.p, members.p + 1);
                     hipLaunchKernelGGL(k_fold_tiny_class, dim3(1), dim3(64), 0, s, n, A.rowptr, A.col, color.p, used - 1, members.p,
                                        members.p + 1, members.p + kFoldMax + 1);
                     DPCG_HIP(hipMemsetAsync(flags.p + 2, 0, sizeof(int), s));
-                    hipLaunchKernelGGL(k_check_coloring, dim3(rows_grid(n)), dim3(kBlock), 0, s, n, A.rowptr, A.col, color.p, flags.p + 2);
+                    hipLaunchKernelGGL(k_check_coloring, dim3(grid_blocks(n, kReorderGrid)), dim3(kBlock), 0, s, n, A.rowptr, A.col, color.p, flags.p + 2);
                     int bad_fold = 0;
-                    DPCG_HIP(hipMemcpyAsync(&bad_fold, flags.p + 2, sizeof(int), hipMemcpyDeviceToHost, s));
-                    DPCG_HIP(hipStreamSynchronize(s));
+                    DPCG_TRY(fetch(&bad_fold, flags.p + 2, 1, s));
                     if (bad_fold) return invalid("multicolour ordering: folding the last class left an improper colouring");
                 }
                 break;
             }
             DPCG_HIP(hipMemsetAsync(iota.p, 0xff, (size_t)n * sizeof(int32_t), s));          // (iota: free until the sort below)
             for (int c = used - 1; c >= 0; --c)
-                hipLaunchKernelGGL(k_recolor_class, dim3(rows_grid(n, 2048)), dim3(kBlock), 0, s, n, A.rowptr, A.col, color.p, iota.p, c);
+                hipLaunchKernelGGL(k_recolor_class, dim3(grid_blocks(n, 2048)), dim3(kBlock), 0, s, n, A.rowptr, A.col, color.p, iota.p, c);
             DPCG_HIP(hipMemcpyAsync(color.p, iota.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
         }
     }
     int32_t cmax = 0;
     DPCG_TRY(reduce_max_i32(color.p, reinterpret_cast<int32_t *>(flags.p + 3), n, s));
-    DPCG_HIP(hipMemcpyAsync(&cmax, flags.p + 3, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    DPCG_HIP(hipStreamSynchronize(s));
+    DPCG_TRY(fetch(&cmax, flags.p + 3, 1, s));
     pt.mark("  colours");
     launch_iota(n, iota.p, s);
     // stable sort by colour: ascending vertex index inside a colour
     DPCG_TRY(sort_pairs_u32_i32(reinterpret_cast<const uint32_t *>(color.p), key_sorted.p, iota.p, perm.p, n, bits_for((uint64_t)cmax), s));
-    hipLaunchKernelGGL(k_invert_perm, dim3(rows_grid(n)), dim3(kBlock), 0, s, n, perm.p, iperm.p);
+    launch_invert_positions(n, perm.p, iperm.p, s);
     DPCG_HIP(hipStreamSynchronize(s));
     DPCG_CHECK_LAUNCH();
     pt.mark("  sort by colour");
     if (n_colors) *n_colors = cmax + 1;
     if (offsets) {                          // class sizes -> where each class begins in perm
-        Buf<int> hist;
+        DevBuf<int> hist;
         DPCG_TRY(hist.alloc(64));
         DPCG_HIP(hipMemsetAsync(hist.p, 0, 64 * sizeof(int), s));
-        hipLaunchKernelGGL(k_color_histogram, dim3(rows_grid(n, 1024)), dim3(kBlock), 0, s, n, color.p, hist.p);
+        hipLaunchKernelGGL(k_color_histogram, dim3(grid_blocks(n, 1024)), dim3(kBlock), 0, s, n, color.p, hist.p);
         int h_hist[64];
-        DPCG_HIP(hipMemcpyAsync(h_hist, hist.p, sizeof(h_hist), hipMemcpyDeviceToHost, s));
-        DPCG_HIP(hipStreamSynchronize(s));
+        DPCG_TRY(fetch(h_hist, hist.p, 64, s));
         offsets->assign((size_t)cmax + 2, 0);
         for (int c = 0; c <= cmax; ++c) (*offsets)[c + 1] = (*offsets)[c] + h_hist[c];
     }

@@ -45,10 +45,7 @@ int plan_alloc(P *p, T **out, int64_t count) {
     return DPCG_OK;
 }
 
-inline int grid_rows(int64_t n, int cap = 4096) {
-    int64_t g = (n + kBlock - 1) / kBlock;
-    return (int)(g < 1 ? 1 : (g > cap ? cap : g));
-}
+constexpr int kConvGrid = 4096;       // most workgroups of a kernel of the sparse-convolution forward passes
 
 // Input sites (nnz, 3) = (batch, row, col), sorted by (batch, row, col): row pointers over batch * H rows, the column
 // array, and a check of the order.  Thread i owns site i and fills the row pointers of the rows that START at or before

@@ -410,7 +410,7 @@ void unet_conv(int cin, int cout, int64_t n_out, const int32_t *nbr, const float
     DPCG_UNET_CASE(32, 16) DPCG_UNET_CASE(32, 32) DPCG_UNET_CASE(32, 64)
     DPCG_UNET_CASE(64, 16) DPCG_UNET_CASE(64, 32) DPCG_UNET_CASE(64, 64)
 #undef DPCG_UNET_CASE
-    const int g = grid_rows(n_out * cout, 4096);
+    const int g = grid_blocks(n_out * cout, kConvGrid);
     if (skip)
         hipLaunchKernelGGL((k_unet_conv_generic<true>), dim3(g), dim3(kBlock), 0, s, n_out, nbr, cin, cout, in, w, bias, slope,
                            skip, out);
@@ -474,7 +474,7 @@ static int build_unet_plan(dpcg_unet_plan *p, int batch, int64_t height, int64_t
     PLAN_TRY(plan_alloc(p, reinterpret_cast<char **>(&scan_ws), (int64_t)scan_bytes));
     PLAN_TRY(plan_alloc(p, &len, max_rows));
     PLAN_HIP(hipMemsetAsync(d_bad, 0, sizeof(int), s));
-    hipLaunchKernelGGL(k_sites_to_csr, dim3(grid_rows(nnz)), dim3(kBlock), 0, s, nnz, indices, batch, height, width, L0.rowptr,
+    hipLaunchKernelGGL(k_sites_to_csr, dim3(grid_blocks(nnz, kConvGrid)), dim3(kBlock), 0, s, nnz, indices, batch, height, width, L0.rowptr,
                        L0.col, d_bad);
     int bad = 0;
     PLAN_HIP(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s));
@@ -491,12 +491,12 @@ static int build_unet_plan(dpcg_unet_plan *p, int batch, int64_t height, int64_t
         const int64_t rows_a = (int64_t)batch * A.h, rows_b = (int64_t)batch * B.h;
         // submanifold rulebook of level l (enc and dec share it)
         PLAN_TRY(plan_alloc(p, &A.subm, A.sites * kTaps));
-        hipLaunchKernelGGL(k_subm_rows, dim3(grid_rows(rows_a)), dim3(kBlock), 0, s, batch, A.h, (const int32_t *)A.rowptr,
+        hipLaunchKernelGGL(k_subm_rows, dim3(grid_blocks(rows_a, kConvGrid)), dim3(kBlock), 0, s, batch, A.h, (const int32_t *)A.rowptr,
                            (const int32_t *)A.col, A.subm);
         // S_l+1 and the stride-2 rulebook in both forms
         const DownGeom g{batch, A.h, A.w, B.h, B.w};
         PLAN_TRY(plan_alloc(p, &B.rowptr, rows_b + 1));
-        hipLaunchKernelGGL(k_down_rows<false>, dim3(grid_rows(rows_b + 1)), dim3(kBlock), 0, s, g, (const int32_t *)A.rowptr,
+        hipLaunchKernelGGL(k_down_rows<false>, dim3(grid_blocks(rows_b + 1, kConvGrid)), dim3(kBlock), 0, s, g, (const int32_t *)A.rowptr,
                            (const int32_t *)A.col, len, (const int32_t *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr,
                            (int32_t *)nullptr);
         PLAN_TRY(exclusive_scan_i32_ws(len, B.rowptr, rows_b + 1, scan_ws, scan_bytes, s));
@@ -512,7 +512,7 @@ static int build_unet_plan(dpcg_unet_plan *p, int batch, int64_t height, int64_t
         PLAN_TRY(plan_alloc(p, &B.down, B.sites * kTaps));
         PLAN_TRY(plan_alloc(p, &A.up, A.sites * kTaps));
         PLAN_HIP(hipMemsetAsync(A.up, 0xff, (size_t)A.sites * kTaps * sizeof(int32_t), s));
-        hipLaunchKernelGGL(k_down_rows<true>, dim3(grid_rows(rows_b + 1)), dim3(kBlock), 0, s, g, (const int32_t *)A.rowptr,
+        hipLaunchKernelGGL(k_down_rows<true>, dim3(grid_blocks(rows_b + 1, kConvGrid)), dim3(kBlock), 0, s, g, (const int32_t *)A.rowptr,
                            (const int32_t *)A.col, (int32_t *)nullptr, (const int32_t *)B.rowptr, B.col, B.down, A.up);
     }
     // rows of the input sites and the lower-triangular CSR the factor is written into
@@ -520,7 +520,7 @@ static int build_unet_plan(dpcg_unet_plan *p, int batch, int64_t height, int64_t
     PLAN_TRY(plan_alloc(p, &p->site_batch, nnz));
     PLAN_TRY(plan_alloc(p, &p->lower_rowptr, rows0 + 1));
     PLAN_TRY(plan_alloc(p, &p->lower_pos, nnz));
-    hipLaunchKernelGGL(k_lower_count, dim3(grid_rows(rows0 + 1)), dim3(kBlock), 0, s, rows0, height, (const int32_t *)L0.rowptr,
+    hipLaunchKernelGGL(k_lower_count, dim3(grid_blocks(rows0 + 1, kConvGrid)), dim3(kBlock), 0, s, rows0, height, (const int32_t *)L0.rowptr,
                        (const int32_t *)L0.col, len, p->site_row, p->site_batch);
     PLAN_TRY(exclusive_scan_i32_ws(len, p->lower_rowptr, rows0 + 1, scan_ws, scan_bytes, s));
     int32_t total = 0;
@@ -528,7 +528,7 @@ static int build_unet_plan(dpcg_unet_plan *p, int batch, int64_t height, int64_t
     PLAN_HIP(hipStreamSynchronize(s));
     p->nnz_lower = total;
     PLAN_TRY(plan_alloc(p, &p->lower_col, p->nnz_lower));
-    hipLaunchKernelGGL(k_lower_fill, dim3(grid_rows(rows0)), dim3(kBlock), 0, s, rows0, height, (const int32_t *)L0.rowptr,
+    hipLaunchKernelGGL(k_lower_fill, dim3(grid_blocks(rows0, kConvGrid)), dim3(kBlock), 0, s, rows0, height, (const int32_t *)L0.rowptr,
                        (const int32_t *)L0.col, (const int32_t *)p->lower_rowptr, p->lower_col, p->lower_pos);
     PLAN_HIP(hipStreamSynchronize(s));
     PLAN_HIP(hipGetLastError());
@@ -575,7 +575,7 @@ extern "C" int dpcg_unet_plan_level_indices(dpcg_unet_plan_t p, int level, int32
         return invalid("dpcg_unet_plan_level_indices: bad plan, level or output");
     const UnetLevel &L = p->lv[level];
     const int64_t rows = (int64_t)p->batch * L.h;
-    hipLaunchKernelGGL(k_level_indices, dim3(grid_rows(rows)), dim3(kBlock), 0, (hipStream_t)stream, rows, L.h,
+    hipLaunchKernelGGL(k_level_indices, dim3(grid_blocks(rows, kConvGrid)), dim3(kBlock), 0, (hipStream_t)stream, rows, L.h,
                        (const int32_t *)L.rowptr, (const int32_t *)L.col, indices_out);
     DPCG_CHECK_LAUNCH();
     return DPCG_OK;
@@ -587,7 +587,7 @@ extern "C" int dpcg_unet_plan_output(dpcg_unet_plan_t p, int32_t *indices_out, i
     hipStream_t s = (hipStream_t)stream;
     const UnetLevel &L = p->lv[0];
     if (indices_out)
-        hipLaunchKernelGGL(k_out_indices, dim3(grid_rows(L.sites)), dim3(kBlock), 0, s, L.sites, (const int32_t *)p->site_batch,
+        hipLaunchKernelGGL(k_out_indices, dim3(grid_blocks(L.sites, kConvGrid)), dim3(kBlock), 0, s, L.sites, (const int32_t *)p->site_batch,
                            (const int32_t *)p->site_row, (const int32_t *)L.col, indices_out);
     if (lower_rowptr)
         DPCG_HIP(hipMemcpyAsync(lower_rowptr, p->lower_rowptr, (size_t)((int64_t)p->batch * L.h + 1) * sizeof(int32_t),
@@ -663,13 +663,13 @@ extern "C" int dpcg_unet_forward(dpcg_unet_plan_t p, const int32_t *channels, co
     const int32_t *srow = p->site_row, *scol = lv[0].col, *spos = p->lower_pos;
     const float *dec0 = T;
 #define DPCG_UNET_OUT(CI)                                                                                                   \
-    hipLaunchKernelGGL((k_unet_out_rows<CI>), dim3(grid_rows(S[0], 4096)), dim3(kBlock), 0, s, S[0], c[5], dec0, weights[16], \
+    hipLaunchKernelGGL((k_unet_out_rows<CI>), dim3(grid_blocks(S[0], kConvGrid)), dim3(kBlock), 0, s, S[0], c[5], dec0, weights[16], \
                        biases[16], srow, scol, spos, features_out, lower_val)
     if (c[1] == 16) DPCG_UNET_OUT(16);
     else if (c[1] == 32) DPCG_UNET_OUT(32);
     else if (c[1] == 64) DPCG_UNET_OUT(64);
     else
-        hipLaunchKernelGGL(k_unet_out, dim3(grid_rows(S[0] * c[5], 4096)), dim3(kBlock), 0, s, S[0], c[1], c[5], dec0, weights[16],
+        hipLaunchKernelGGL(k_unet_out, dim3(grid_blocks(S[0] * c[5], kConvGrid)), dim3(kBlock), 0, s, S[0], c[1], c[5], dec0, weights[16],
                            biases[16], srow, scol, spos, features_out, lower_val);
 #undef DPCG_UNET_OUT
     DPCG_CHECK_LAUNCH();

@@ -77,7 +77,12 @@ CASES = (
     Case("poisson16_band40_pattern", lambda: E.poisson2d(16), None, (4, 4, 8, 16, 224), 41, pattern=band40_pattern,
          hits={**_once(), 41: 216}, all_widths_to=41),
 )
-CASE_BY_NAME = {c.name: c for c in CASES}
+# level 1 at the smallest shapes the transposes of the symbolic phase see: one row; every column of the strictly lower part empty
+DEGENERATE_CASES = (
+    Case("tiny1_l1", lambda: E.tiny(1), 1, (1, 0, 0, 0, 0), 1, hits={1: 1}),
+    Case("diags5_l1", lambda: E.csr(sp.diags(np.arange(1.0, 6.0))), 1, (5, 0, 0, 0, 0), 1, hits={1: 5}),
+)
+CASE_BY_NAME = {c.name: c for c in CASES + DEGENERATE_CASES}
 
 
 def _with(A, entries) -> sp.csr_matrix:

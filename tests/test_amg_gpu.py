@@ -166,6 +166,36 @@ def test_reattach_after_update_values(D, systems, reordered):
     assert h.reused_levels == 0
 
 
+def test_single_aggregate_and_its_values_only_refresh(D):
+    """A complete graph of 12 rows: one MIS(2) root, one aggregate -- P has a single column, P^T a single row, the coarsest level one
+    row.  Built, then re-attached after update_values with another diagonal: the aggregate stays (every row is a neighbour of the
+    root), so only values are computed again -- P^T's through the kept sort order -- while P = T - omega D^-1 A T changes row by row."""
+    n = 12
+    A = _csr(np.diag(n + 1.0 + np.arange(n)) - np.ones((n, n)))
+    A2 = _csr(np.diag((n + 1.0 + np.arange(n)) * np.linspace(1.0, 2.0, n)) - np.ones((n, n)))
+    assert np.array_equal(A2.indices, A.indices)
+    S = _attach(D, A, max_coarse=4)
+    x = np.random.default_rng(5).standard_normal(n)
+    for M, fresh in ((A, None), (A2, lambda: _attach(D, A2, max_coarse=4))):
+        if fresh is not None:
+            S.update_values(M.data)
+            S.set_preconditioner(D.SmoothedAggregation(max_coarse=4))
+        info, H, levels = _device_hierarchy(D, S, M)
+        assert info.levels == 2 and info.rows == [n, 1] and info.reused_levels == (0 if fresh is None else 1)
+        lev, Al = levels[0]
+        Sg = R.strength(Al)
+        assert np.array_equal(lev.aggregates, R.aggregate(Al, Sg, R.mis2(Sg, 0))) and not lev.aggregates.any()
+        P = (R.tentative(lev.aggregates) - sp.diags(info.omega[0] / Al.diagonal()) @ (Al @ R.tentative(lev.aggregates))).tocsr()
+        assert lev.P.shape == (n, 1) and _rel(lev.P, P) <= 1e-12 and _rel(lev.A_next, P.T @ (Al @ P)) <= 1e-12
+        ref = R.vcycle(H, x)                                       # (restricts with scipy's transpose of the device's P)
+        Mx = S.precond_apply(torch.from_numpy(x).cuda()).cpu().numpy()
+        assert np.linalg.norm(Mx - ref) <= 1e-12 * np.linalg.norm(ref)
+        if fresh is not None:
+            F = fresh()
+            assert _same_bits(_level_bits(S), _level_bits(F))
+            assert torch.equal(S.precond_apply(torch.from_numpy(x).cuda()), F.precond_apply(torch.from_numpy(x).cuda()))
+
+
 def test_level_copies_refuse_a_rebuilt_hierarchy(D, systems):
     import ctypes as C
     S = _attach(D, systems["poisson2d_256"])

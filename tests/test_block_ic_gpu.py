@@ -52,13 +52,18 @@ CASES = {
     "poisson2d_12/sparse_ids": lambda: (O.poisson2d(12), np.array([7, 3, 1000000, 12])[np.random.default_rng(5).integers(0, 4, 144)]),
     "poisson2d_12/one_row": lambda: (O.poisson2d(12), 3 * np.arange(144)[::-1].copy()),        # n one-row blocks
 }
+# the smallest shapes the transpose of tril(A_B) sees: one row; a diagonal matrix (every column of the strictly lower part empty)
+DEGENERATE_CASES = {
+    "one_row/1": lambda: (sp.csr_matrix(np.array([[4.0]])), 1),
+    "diagonal_5/2": lambda: (sp.diags(np.arange(1.0, 6.0)), 2),
+}
 COUNT_CASES = {"poisson2d_12/64": 12, "poisson3d_12/2x2x2": 14, "poisson3d_20/3x3x3": 22}
 _SYS, _FAC, _PCG = {}, {}, {}
 
 
 def system(name):
     if name not in _SYS:
-        A, blocks = CASES[name]()
+        A, blocks = (CASES.get(name) or DEGENERATE_CASES[name])()
         A = _csr(A)
         ids = R.contiguous_ids(A.shape[0], blocks) if isinstance(blocks, int) else np.asarray(blocks)
         _SYS[name] = (A, blocks, ids)
@@ -135,6 +140,16 @@ def test_factor_ordering_levels_and_apply(D, name, variant):
     S = attached(D, name, variant)
     assert not S.block_ic_info()["pattern_reused"]
     check_factor_and_apply(S, name, variant)
+    S.close()
+
+
+@pytest.mark.parametrize("variant", VARIANTS)
+@pytest.mark.parametrize("name", list(DEGENERATE_CASES))
+def test_degenerate_shapes(D, name, variant):
+    S = attached(D, name, variant)
+    check_factor_and_apply(S, name, variant)
+    A, _, _ = system(name)
+    assert np.array_equal(_factor(S).data, np.sqrt(A.diagonal()))              # both variants: L = sqrt(D)
     S.close()
 
 

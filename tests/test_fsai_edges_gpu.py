@@ -312,6 +312,22 @@ def test_apply_through_64_wide_rows(D, restated, name):
     T.close()
 
 
+@pytest.mark.parametrize("name", [c.name for c in X.DEGENERATE_CASES])
+def test_factor_and_apply_at_degenerate_shapes(D, restated, name):
+    """One row, and a diagonal matrix: L = L^T is diagonal, so z_i = l_ii (l_ii r_i) in two roundings whatever the order -- the device's
+    L^T (a transpose of one row, of columns whose strictly lower part is empty) must give exactly that."""
+    A, Lr = restated(name)
+    assert Lr.nnz == A.shape[0]
+    r = O.rhs(A.shape[0], 3)
+    S = D.CsrSystem.from_any(A, reorder=None)
+    _attach(D, S, X.CASE_BY_NAME[name])
+    _check_info(S, X.CASE_BY_NAME[name])
+    assert _same_bits(_factor(S), Lr)
+    z = S.precond_apply(_dev(r)).cpu().numpy()
+    assert np.array_equal(_bits(z), _bits(Lr.data * (Lr.data * r)))
+    S.close()
+
+
 def test_solve_through_64_wide_rows(D):
     A = E.banded_spd(1200, 63)
     n = A.shape[0]

@@ -439,6 +439,26 @@ def test_sptrsv_bit_exact_segment_forms(D, make_L):
     assert np.array_equal(z, CO.sptrsv_upper(CO.transpose_csr(Lf), y_ref))
 
 
+@pytest.mark.parametrize("diag", [[4.0], [1.0, 2.0, 3.0, 4.0, 5.0]], ids=["one_row", "diagonal_5"])
+def test_llt_solve_degenerate_factors(D, diag):
+    """The smallest shapes at which the transpose behind L^T can go wrong: a factor of one row, and a diagonal factor (every column of
+    the strictly lower part is empty).  Both solves and the apply against sequential substitution, bit for bit."""
+    Lf = sp.diags(np.array(diag), format="csr")
+    n = Lf.shape[0]
+    S = D.CsrSystem.from_any(sp.identity(n, format="csr"))
+    S.set_preconditioner(D.LLtSolve(Lf))
+    rp, ci, v = S.factor()
+    assert np.array_equal(rp, Lf.indptr) and np.array_equal(ci, Lf.indices) and np.array_equal(v, Lf.data)
+    assert S.info()["levels_lower"] == 1 and S.info()["levels_upper"] == 1
+    r = O.rhs(n, 9)
+    y_ref = CO.sptrsv_lower(Lf, r)
+    z_ref = CO.sptrsv_upper(CO.transpose_csr(Lf), y_ref)
+    assert np.array_equal(S.sptrsv(_dev(r), upper=False).cpu().numpy(), y_ref)
+    assert np.array_equal(S.sptrsv(_dev(y_ref), upper=True).cpu().numpy(), z_ref)
+    assert np.array_equal(S.precond_apply(_dev(r)).cpu().numpy(), z_ref)
+    S.close()
+
+
 def test_pcg_llt_solve_golden(D, golden):
     A = O.poisson2d(64)
     b = _dev(O.rhs(A.shape[0], 0))
