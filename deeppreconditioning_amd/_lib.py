@@ -25,6 +25,7 @@ PRECOND_NONE, PRECOND_JACOBI, PRECOND_CSR, PRECOND_LLT_MULTIPLY, PRECOND_LLT_SOL
 PRECOND_LU_MULTIPLY, PRECOND_LU_SOLVE = 7, 8
 PRECOND_BLOCK_LLT_SOLVE = 9
 BLOCK_IC_IC0, BLOCK_IC_DIC = 0, 1
+ILU_ILU0, ILU_DILU = 0, 1
 PRECOND_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p)   # dpcg_precond_fn
 INIT_CHECK_R, SPMV_F32, NO_GRAPH, NO_SMALL, VAL32_IF_LOSSLESS, NO_FUSE, NO_TEAM, TEAM = 1, 2, 4, 8, 16, 32, 64, 128
 SINGLE_REDUCTION = 256
@@ -71,6 +72,7 @@ SIGNATURES = {
     "dpcg_set_precond_icholt": (_int, [_p, _int, _int, _dbl, _p]),
     "dpcg_get_icholt_info": (_int, [_p, _p]),
     "dpcg_set_precond_ilut": (_int, [_p, _int, _int, _dbl, _p]),
+    "dpcg_set_precond_ilu0": (_int, [_p, _int, _int, _int, _p]),
     "dpcg_set_precond_fsai": (_int, [_p, _int, _p]),
     "dpcg_set_precond_fsai_pattern": (_int, [_p, _i64, _p, _p, _int, _p]),
     "dpcg_get_fsai_info": (_int, [_p, _p]),

@@ -801,7 +801,7 @@ int apply_precond(dpcg_system *h, const double *r, double *z, hipStream_t s, boo
             }
             break;
         case DPCG_PRECOND_LLT_SOLVE:
-        case DPCG_PRECOND_LU_SOLVE: {          // (L U: no level-major hand-over, pairing or riding diagonal is built -- finish_lu)
+        case DPCG_PRECOND_LU_SOLVE: {          // (L U: the level-major hand-over only; no pairing, no riding diagonal -- finish_lu)
             SptrsvIo lower_io, upper_io;
             if (h->lvlL.level_major && h->lvlU.level_major && h->lvlU.lm_from_lower) {
                 lower_io.keep_lm = true;                   // y stays in L's level-major numbering, L^T gathers it from there

@@ -629,6 +629,14 @@ int team_max_row_len();
 int launch_pcg_team(const TeamDesc *descs_dev, int nsys, int max_slabs_per_wg, int max_row_len, hipStream_t s, bool trace = false);
 void launch_ic0_level(const int32_t *rows, int j0, int count, const int32_t *rp, const int32_t *ci, double *lv, int *bad,
                       hipStream_t s, const double *colnorm = nullptr, double tau = 0.0);   // colnorm: ICT drop rule
+// dpcg_ilu0.hip: the pattern of A split into L (strict lower part + a unit diagonal last) and U (diagonal first) -- counts for the
+// scans (*flag = 1: a row without a diagonal), the copy -- and one level of the numeric ILU(0) / DILU (*bad: the atomic maximum of
+// 0x7fffffff - row over the rows whose pivot is zero or not finite)
+void launch_ilu0_count(int64_t n, const int32_t *rp, const int32_t *ci, int32_t *cl, int32_t *cu, int *flag, hipStream_t s);
+void launch_ilu0_split(int64_t n, const int32_t *rp, const int32_t *ci, const double *v, const int32_t *lrp, int32_t *lci, double *lv,
+                       const int32_t *urp, int32_t *uci, double *uv, hipStream_t s);
+void launch_ilu0_level(bool dilu, const int32_t *rows, int j0, int count, const int32_t *lrp, const int32_t *lci, double *lv,
+                       const int32_t *urp, const int32_t *uci, double *uv, int *bad, hipStream_t s);
 void launch_colnorm1(int64_t n, const int32_t *rp, const int32_t *ci, const double *v, double *c, hipStream_t s);
 void launch_ict_pattern(bool write, int64_t n, const int32_t *rp, const int32_t *ci, const double *v, int fill, int32_t *cnt,
                         const int32_t *lrp, int32_t *lci, double *lv, int *flags, hipStream_t s);

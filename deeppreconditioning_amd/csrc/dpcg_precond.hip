@@ -873,10 +873,13 @@ int finish_llt(dpcg_system *h, int mode, hipStream_t s, LevelSort *lower_levels 
 }
 
 // h->L (unit lower, diagonal last) and h->Lt (an upper factor U of its own, diagonal first) hold an L U factor in the caller's
-// numbering: the SpMV plans of both (multiply mode; P L P^T and P U P^T on a reordered handle) or the level schedules of both,
-// each from its OWN pattern (solve mode).  Nothing of finish_llt's U = L^T shortcuts -- the transpose, L's level sets read
-// backwards, the strip plan taking L's level count, the paired colour sweeps, the diagonal riding on K2 -- holds here.
-int finish_lu(dpcg_system *h, int mode, hipStream_t s) {
+// numbering, or in the factor's own (fmap: ILU(0) in multicolour order): the SpMV plans of both (multiply mode; P L P^T and
+// P U P^T on a reordered handle) or the level schedules of both, each from its OWN pattern (solve mode).  Nothing of finish_llt's
+// U = L^T shortcuts -- the transpose, L's level sets read backwards, the strip plan taking L's level count, the paired colour
+// sweeps (the last level of L does not hold the first level of U), the diagonal riding on K2 (it divides by L's diagonal: unit
+// here) -- holds here.  What does: two level-major schedules hand the lower result over by position (lm_from_lower).
+// `lower_levels`: the level sets of L's pattern when the caller already has them (ILU(0) factors along them).
+int finish_lu(dpcg_system *h, int mode, hipStream_t s, LevelSort *lower_levels = nullptr) {
     const int64_t n = h->A.n;
     PhaseTimer pt(s);
     if (mode == DPCG_PRECOND_LU_MULTIPLY) {
@@ -891,14 +894,23 @@ int finish_lu(dpcg_system *h, int mode, hipStream_t s) {
         }
         pt.mark("plans (L, U)");
     } else {
-        const int32_t *fm = h->iperm;                 // factor index -> handle index (null: the handle is not reordered)
-        LevelSort lo, up;
-        DPCG_TRY(compute_levels(n, h->L.rowptr, h->L.col, false, lo, s, fm));
-        DPCG_TRY(schedule_factor(n, h->lvlL, lo, h->L, false, fm, s));
+        // factor index -> handle index: the factor's own numbering (fmap) or the caller's (iperm; null: the handle is not reordered)
+        const int32_t *fm = h->fmap ? h->fmap : h->iperm;
+        LevelSort lo_own, up;
+        if (!lower_levels) {
+            DPCG_TRY(compute_levels(n, h->L.rowptr, h->L.col, false, lo_own, s, fm));
+            lower_levels = &lo_own;
+        }
+        DPCG_TRY(schedule_factor(n, h->lvlL, *lower_levels, h->L, false, fm, s));
         pt.mark("schedule(L)");
         DPCG_TRY(compute_levels(n, h->Lt.rowptr, h->Lt.col, true, up, s, fm));
         DPCG_TRY(schedule_factor(n, h->lvlU, up, h->Lt, true, fm, s));
         pt.mark("schedule(U)");
+        if (h->lvlL.level_major && h->lvlU.level_major) {      // the lower result feeds the upper solve without leaving level-major order
+            DPCG_TRY(dev_alloc(&h->lvlU.lm_from_lower, n));
+            launch_compose_positions(n, h->lvlU.rows, h->lvlL.lm_pos, h->lvlU.lm_from_lower, s);
+            DPCG_CHECK_LAUNCH();
+        }
     }
     h->precond = mode;
     return DPCG_OK;
@@ -926,6 +938,28 @@ extern "C" int dpcg_set_precond_llt(dpcg_handle_t h, int mode, int64_t nnz, cons
 // colouring, the permutation, the level analysis, the transposition, the schedules and their tile plans.  The entry maps are
 // built at the first refresh by sending entry NUMBERS through the very kernels the setup sends values through.
 namespace {
+// The handle's multicolour ordering (mc_perm / mc_iperm / mc_colors / mc_offsets), for IC(0) and ILU(0) in that order.  The colouring
+// looks at the pattern only: computed once per handle numbering (kept across dpcg_update_values).
+int cached_coloring(dpcg_system *h, hipStream_t s) {
+    static const bool keep_coloring = [] { const char *ev = getenv("DPCG_KEEP_COLORING"); return !(ev && ev[0] == '0'); }();
+    if (h->mc_perm && keep_coloring) return DPCG_OK;
+    int32_t *p = nullptr, *ip = nullptr;
+    int nc = 0;
+    std::vector<int32_t> off;
+    DPCG_TRY(multicolor_order(h->A, &p, &ip, &nc, s, &off));
+    if (h->fmap == h->mc_perm) {       // the attached factor keeps the arrays it was built with until it is replaced
+        h->mc_perm = h->mc_iperm = nullptr;
+    } else {
+        dev_free(h->mc_perm);
+        dev_free(h->mc_iperm);
+    }
+    h->mc_perm = p;
+    h->mc_iperm = ip;
+    h->mc_colors = nc;
+    h->mc_offsets.swap(off);
+    return DPCG_OK;
+}
+
 int refresh_parked_ic0(dpcg_system *h, hipStream_t s) {
     dpcg_system::Parked &P = h->parked;
     const int64_t n = h->A.n, nnzl = P.L.nnz;
@@ -1033,24 +1067,7 @@ extern "C" int dpcg_set_precond_ic0_ordered(dpcg_handle_t h, int mode, int order
     int n_colors = 0;
     PhaseTimer pt0(s);
     if (ordering == DPCG_ORDER_MULTICOLOR) {
-        // the colouring looks at the pattern only: computed once per handle numbering (kept across dpcg_update_values)
-        static const bool keep_coloring = [] { const char *ev = getenv("DPCG_KEEP_COLORING"); return !(ev && ev[0] == '0'); }();
-        if (!h->mc_perm || !keep_coloring) {
-            int32_t *p = nullptr, *ip = nullptr;
-            int nc = 0;
-            std::vector<int32_t> off;
-            DPCG_TRY(multicolor_order(h->A, &p, &ip, &nc, s, &off));
-            if (h->fmap == h->mc_perm) {       // the attached factor keeps the arrays it was built with until it is replaced
-                h->mc_perm = h->mc_iperm = nullptr;
-            } else {
-                dev_free(h->mc_perm);
-                dev_free(h->mc_iperm);
-            }
-            h->mc_perm = p;
-            h->mc_iperm = ip;
-            h->mc_colors = nc;
-            h->mc_offsets.swap(off);
-        }
+        DPCG_TRY(cached_coloring(h, s));
         cperm = h->mc_perm;
         ciperm = h->mc_iperm;
         n_colors = h->mc_colors;
@@ -1533,6 +1550,91 @@ extern "C" int dpcg_set_precond_ilut(dpcg_handle_t h, int mode, int add_fill_in,
     h->L = Lf;
     h->Lt = Uf;                         // (the slot of L^T: U is a factor of its own here)
     st = finish_lu(h, mode, s);
+    if (st < 0) free_precond(h);
+    return st;
+}
+
+// ILU(0) / DILU on the pattern of A (contract: tests/ilu0_restatement.py; kernels: dpcg_ilu0.hip): the pattern split into L and U by
+// count / scan / copy, the level sets of L's pattern, the numeric phase one launch per level.  DPCG_ORDER_CALLER factors the
+// caller's matrix; DPCG_ORDER_MULTICOLOR factors Q A Q^T of the handle's, Q = its cached colouring (as IC(0) in that order), and the
+// factors stay in that numbering (fmap).  The handle keeps its previous preconditioner when the factorisation fails.
+extern "C" int dpcg_set_precond_ilu0(dpcg_handle_t h, int mode, int variant, int ordering, dpcg_stream_t stream) {
+    if (!h) return invalid("NULL handle");
+    if (mode != DPCG_PRECOND_LU_MULTIPLY && mode != DPCG_PRECOND_LU_SOLVE) return invalid("bad LU mode");
+    if (variant != DPCG_ILU_ILU0 && variant != DPCG_ILU_DILU) return invalid("dpcg_set_precond_ilu0: bad variant");
+    if (ordering != DPCG_ORDER_CALLER && ordering != DPCG_ORDER_MULTICOLOR) return invalid("dpcg_set_precond_ilu0: bad ordering");
+    if (ordering == DPCG_ORDER_MULTICOLOR && mode != DPCG_PRECOND_LU_SOLVE)
+        return invalid("dpcg_set_precond_ilu0: the multicolour ordering serves the triangular solves (mode LU_SOLVE)");
+    hipStream_t s = (hipStream_t)stream;
+    SetupScope scope(s, true);          // (the preconditioner being replaced may be in use on another stream)
+    const int64_t n = h->A.n;
+    CsrDev Ac, Lf, Uf;
+    auto fail = [&](int st) {
+        free_csr(Lf);
+        free_csr(Uf);
+        free_csr(Ac);
+        return st;
+    };
+    int32_t *cperm = nullptr, *ciperm = nullptr;
+    int n_colors = 0, st = DPCG_OK;
+    PhaseTimer pt(s);
+    if (ordering == DPCG_ORDER_MULTICOLOR) {
+        DPCG_TRY(cached_coloring(h, s));
+        cperm = h->mc_perm;
+        ciperm = h->mc_iperm;
+        n_colors = h->mc_colors;
+        pt.mark("multicolour ordering");
+        if ((st = permute_csr(h->A, cperm, ciperm, Ac, s)) < 0) return fail(st);
+        pt.mark("Q A Q^T");
+    }
+    const CsrDev &Asrc = ordering == DPCG_ORDER_MULTICOLOR ? Ac : (h->perm ? h->A_user : h->A);
+    Lf.n = Uf.n = n;
+    Lf.owned = Uf.owned = true;
+    DevBuf<int32_t> cl, cu, flags;      // flags[0]: a row without a diagonal, flags[1]: 0x7fffffff - the first row with a bad pivot
+    if ((st = cl.alloc(n + 1)) < 0 || (st = cu.alloc(n + 1)) < 0 || (st = flags.alloc(2)) < 0 || (st = dev_alloc(&Lf.rowptr, n + 1)) < 0 ||
+        (st = dev_alloc(&Uf.rowptr, n + 1)) < 0)
+        return fail(st);
+    hipError_t e = hipMemsetAsync(flags.p, 0, 2 * sizeof(int32_t), s);
+    if (e != hipSuccess) return fail(hip_fail(e, "hipMemsetAsync", __FILE__, __LINE__));
+    launch_ilu0_count(n, Asrc.rowptr, Asrc.col, cl.p, cu.p, reinterpret_cast<int *>(flags.p), s);
+    if ((st = exclusive_scan_i32(cl.p, Lf.rowptr, n + 1, s)) < 0 || (st = exclusive_scan_i32(cu.p, Uf.rowptr, n + 1, s)) < 0) return fail(st);
+    int32_t h_flags[2] = {0, 0}, lnnz = 0, unnz = 0;
+    if ((st = fetch(h_flags, flags.p, 2, s)) < 0 || (st = fetch(&lnnz, Lf.rowptr + n, 1, s)) < 0 || (st = fetch(&unnz, Uf.rowptr + n, 1, s)) < 0)
+        return fail(st);
+    if (h_flags[0]) {
+        set_error("ILU(0): missing diagonal entry");
+        return fail(DPCG_ERR_PIVOT);
+    }
+    Lf.nnz = lnnz;
+    Uf.nnz = unnz;
+    if ((st = dev_alloc(&Lf.col, lnnz)) < 0 || (st = dev_alloc(&Lf.val, lnnz)) < 0 || (st = dev_alloc(&Uf.col, unnz)) < 0 ||
+        (st = dev_alloc(&Uf.val, unnz)) < 0)
+        return fail(st);
+    launch_ilu0_split(n, Asrc.rowptr, Asrc.col, Asrc.val, Lf.rowptr, Lf.col, Lf.val, Uf.rowptr, Uf.col, Uf.val, s);
+    pt.mark("ilu0: split A");
+    LevelSort ls;
+    if ((st = compute_levels(n, Lf.rowptr, Lf.col, false, ls, s, cperm ? cperm : h->iperm)) < 0) return fail(st);
+    pt.mark("ilu0: levels(L)");
+    const int nl = (int)ls.level_ptr.size() - 1;
+    for (int l = 0; l < nl; ++l)
+        launch_ilu0_level(variant == DPCG_ILU_DILU, ls.rows.p, ls.level_ptr[(size_t)l], ls.level_ptr[(size_t)l + 1] - ls.level_ptr[(size_t)l], Lf.rowptr,
+                          Lf.col, Lf.val, Uf.rowptr, Uf.col, Uf.val, reinterpret_cast<int *>(flags.p) + 1, s);
+    e = hipGetLastError();
+    if (e != hipSuccess) return fail(hip_fail(e, "ILU(0): numeric factorisation", __FILE__, __LINE__));
+    if ((st = fetch(h_flags, flags.p, 2, s)) < 0) return fail(st);
+    pt.mark("ilu0: numeric");
+    if (h_flags[1]) {
+        set_error("ILU(0): zero or non-finite pivot at row " + std::to_string(0x7fffffff - h_flags[1]));
+        return fail(DPCG_ERR_PIVOT);
+    }
+    free_precond(h);
+    free_csr(Ac);
+    h->L = Lf;
+    h->Lt = Uf;                         // (the slot of L^T: U is a factor of its own here)
+    h->fmap = cperm;                    // factor index -> handle index (null: the caller's numbering)
+    h->fmap_inv = ciperm;
+    h->precond_colors = n_colors;
+    st = finish_lu(h, mode, s, &ls);
     if (st < 0) free_precond(h);
     return st;
 }

@@ -313,6 +313,42 @@ class ILUT(Preconditioner):
         raise TypeError("ILUT needs the system matrix: attach it with CsrSystem.set_preconditioner")
 
 
+class ILU0(Preconditioner):
+    """ILU(0) of A computed at setup: the zero-fill L U factorisation for matrices whose values are not symmetric, the
+    counterpart of `IC0` and the factor OpenFOAM pairs with PBiCGStab.  The factors equal the restatement
+    (tests/ilu0_restatement.py) bit for bit; `CsrSystem.lu_factors()` returns them.
+
+    variant="dilu" is OpenFOAM's DILU: only the diagonal is factored, d_i = a_ii - sum a_ik a_ki / d_k, L = I + strict_lower(A) D^-1,
+    U = D + strict_upper(A); equal to ILU(0) where the pattern holds no triangle (5- / 7-point grids).
+
+    mode="solve" applies z = U^-1 (L^-1 r) by triangular solves, mode="multiply" z = L (U r) as `ILUT`'s.
+
+    ordering="multicolor" (solve mode): the factorisation of the matrix with its unknowns listed colour by colour -- a
+    DIFFERENT preconditioner (another elimination order, more iterations) whose two triangular solves are a handful of wide
+    parallel sweeps instead of hundreds of dependent levels; `CsrSystem.precond_ordering()` returns the ordering and
+    `lu_factors()` the factors in it.  M is not symmetric: `CsrSystem.spectrum_bounds` raises.  See dpcg_set_precond_ilu0 in
+    include/dpcg.h."""
+
+    def __init__(self, mode: str = "solve", ordering: str = "caller", variant: str = "ilu0"):
+        if mode not in ("solve", "multiply"):
+            raise ValueError("mode must be 'solve' or 'multiply'")
+        if ordering not in ("caller", "multicolor"):
+            raise ValueError("ordering must be 'caller' or 'multicolor'")
+        if variant not in ("ilu0", "dilu"):
+            raise ValueError("variant must be 'ilu0' or 'dilu'")
+        if ordering == "multicolor" and mode != "solve":
+            raise ValueError("the multicolour ordering serves the triangular solves: mode='solve'")
+        self.mode = L.PRECOND_LU_SOLVE if mode == "solve" else L.PRECOND_LU_MULTIPLY
+        self.ordering = L.ORDER_MULTICOLOR if ordering == "multicolor" else L.ORDER_CALLER
+        self.variant = L.ILU_DILU if variant == "dilu" else L.ILU_ILU0
+
+    def _attach(self, system):
+        L.check(L.lib().dpcg_set_precond_ilu0(system._h, self.mode, self.variant, self.ordering, _stream()))
+
+    def __matmul__(self, r):
+        raise TypeError("ILU0 needs the system matrix: attach it with CsrSystem.set_preconditioner")
+
+
 class FSAI(Preconditioner):
     """The factorised sparse approximate inverse (Kolotilina & Yeremin 1993): for every column i the dense SPD system
     A[P_i, P_i] y = e_1 on P_i = {j >= i : (j, i) in P} gives L[P_i, i] = y / sqrt(y_1); M = L L^T approximates A^-1 (SPD for every
@@ -1027,8 +1063,9 @@ class CsrSystem:
         return {"form": out[0], "waves": out[1], "retry_column": None if out[2] < 0 else out[2], "pool_cap": out[3]}
 
     def lu_factors(self):
-        """The attached `ILUT` factors (L, U) as scipy CSR in the caller's numbering: L unit lower (diagonal last), U upper
-        (diagonal first).  DpcgError (ERR_STATE) when no L U factor is attached."""
+        """The attached `ILUT` / `ILU0` factors (L, U) as scipy CSR in the factor's numbering (`precond_ordering`: the caller's
+        unless built with ordering="multicolor"): L unit lower (diagonal last), U upper (diagonal first).  DpcgError (ERR_STATE)
+        when no L U factor is attached."""
         import scipy.sparse as sp
         ln, un = C.c_int64(0), C.c_int64(0)
         L.check(L.lib().dpcg_get_lu_factors(self._h, C.byref(ln), C.byref(un), None, None, None, None, None, None))

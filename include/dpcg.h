@@ -174,7 +174,8 @@ int dpcg_set_precond_ic0(dpcg_handle_t h, int mode, dpcg_stream_t stream);
  * order: iteration counts differ, typically +20 % against a natural ordering), offered because on this hardware it is the
  * form in which an incomplete-Cholesky apply beats Jacobi to the solution.  Caller-visible vectors keep the caller's numbering.
  * dpcg_get_factor then returns L in the factor's numbering; dpcg_get_precond_ordering gives that numbering:
- * perm_host[k] = the caller's row at factor position k (int32[n], host; identity for DPCG_ORDER_CALLER), *n_colors. */
+ * perm_host[k] = the caller's row at factor position k (int32[n], host; identity for DPCG_ORDER_CALLER), *n_colors.  The same
+ * for an ILU(0) / DILU factor in multicolour order (dpcg_set_precond_ilu0), whose factors dpcg_get_lu_factors returns. */
 enum dpcg_ordering { DPCG_ORDER_CALLER = 0, DPCG_ORDER_MULTICOLOR = 1 };
 int dpcg_set_precond_ic0_ordered(dpcg_handle_t h, int mode, int ordering, dpcg_stream_t stream);
 int dpcg_get_precond_ordering(dpcg_handle_t h, int *n_colors, int32_t *perm_host);
@@ -236,7 +237,35 @@ int dpcg_get_icholt_info(dpcg_handle_t h, int32_t out[4]);
  * text names the row).  On failure the previous preconditioner stays.  M = L U is not symmetric: dpcg_spectrum returns
  * DPCG_BREAKDOWN for these kinds, and no one-launch form takes them.  add_fill_in >= 0, threshold >= 0. */
 int dpcg_set_precond_ilut(dpcg_handle_t h, int mode, int add_fill_in, double threshold, dpcg_stream_t stream);
-/* The attached L U factor in the caller's numbering (host arrays; any may be NULL: with all NULL only the sizes are reported):
+/* ILU(0) and DILU: the zero-fill L U factorisations, the incomplete factors OpenFOAM pairs with PBiCGStab (its DILU) and the
+ * counterpart of dpcg_set_precond_ic0_ordered for matrices whose values are not symmetric.  Not in the reference.  The factors go
+ * where ILUT's go (L unit lower, diagonal last; U upper, diagonal first; columns ascending) and every consumer of those kinds
+ * serves them.  Contract (tests/ilu0_restatement.py; the device equals it bit for bit), on the pattern of the matrix with sorted
+ * rows, rows i ascending:
+ *   DPCG_ILU_ILU0  for the stored k < i ascending: l_ik = a_ik / u_kk, then for the stored (k, j), j > k ascending, where (i, j) is
+ *                  stored: a_ij = a_ij - l_ik u_kj (one product, one subtraction); what is left of row i at and right of the
+ *                  diagonal is row i of U.
+ *   DPCG_ILU_DILU  OpenFOAM's rule: d_i = a_ii, then for the stored k < i ascending whose (k, i) is stored too: t = a_ik a_ki,
+ *                  t = t / d_k, d_i = d_i - t; L = I + strict_lower(A) D^-1, U = D + strict_upper(A).  A pattern that is not
+ *                  structurally symmetric is accepted (a missing (k, i) contributes nothing).  Equal to ILU(0) where the pattern
+ *                  holds no triangle (5- / 7-point grids).
+ * mode: DPCG_PRECOND_LU_SOLVE (z = U^-1 L^-1 r) or DPCG_PRECOND_LU_MULTIPLY (z = L (U r), as ILUT's).
+ * ordering: DPCG_ORDER_CALLER factors the matrix as the caller numbered it (also on a reordered handle);
+ * DPCG_ORDER_MULTICOLOR (LU_SOLVE only) factors Q A Q^T, the unknowns listed colour by colour -- the handle's colouring, shared
+ * with IC(0) in that order and kept across dpcg_update_values -- so that each triangular solve is as many wide sweeps as there
+ * are colours; the lower result then reaches the upper solve by position, without leaving level order.  A different
+ * preconditioner from the caller-ordered one (more iterations, far shallower applies).  The factorisation itself runs level by
+ * level on the level sets of L's pattern, one row per lane: the level analysis decides what waits for what, not the colouring.
+ * dpcg_get_lu_factors returns the factors in the factor's numbering, dpcg_get_precond_ordering that numbering and the colours.
+ * Refusals (the previous preconditioner stays attached): DPCG_ERR_PIVOT "ILU(0): missing diagonal entry"; DPCG_ERR_PIVOT
+ * "ILU(0): zero or non-finite pivot at row i" (the first such row, in the factor's numbering; both variants); DPCG_ERR_INVALID
+ * for a bad mode, variant or ordering, and for the multicolour ordering in multiply mode.
+ * dpcg_update_values drops the factor like any other: a refresh of the values alone on the kept pattern, as IC(0) in multicolour
+ * order has, is not provided.  M = L U is not symmetric: dpcg_spectrum returns DPCG_BREAKDOWN, no one-launch form takes it. */
+enum dpcg_ilu_variant { DPCG_ILU_ILU0 = 0, DPCG_ILU_DILU = 1 };
+int dpcg_set_precond_ilu0(dpcg_handle_t h, int mode, int variant, int ordering, dpcg_stream_t stream);
+/* The attached L U factor in the factor's numbering -- the caller's, unless the factor was built in multicolour order
+ * (dpcg_get_precond_ordering) -- as host arrays (any may be NULL: with all NULL only the sizes are reported):
  * L unit lower (diagonal last), U upper (diagonal first), columns ascending.  DPCG_ERR_STATE when no L U factor is set. */
 int dpcg_get_lu_factors(dpcg_handle_t h, int64_t *l_nnz, int64_t *u_nnz, int32_t *l_rowptr, int32_t *l_col, double *l_val,
                         int32_t *u_rowptr, int32_t *u_col, double *u_val);
