@@ -16,7 +16,9 @@
 //                     r = s - omega t;  partials of <rhat,r> and <r,r>                               reads x, ph, sh, s, t, rhat, writes x, r
 // M = I: ph is p and sh is s (nothing stored twice).  Any other M: the handle's apply (apply_precond, in the loop) after P and after S.
 // The passes move two doubles a lane in 16-byte accesses, the next pair requested before the current one is consumed; an odd n leaves one
-// entry to one lane of workgroup 0.  No float atomics: wave tree, four wave sums in LDS, the partials in a fixed order (block_sum_n,
+// entry to one lane of workgroup 0.  The grid is grid_for(n) = ceil(n / 256) workgroups, 1024 at the most, so a lane takes a second pair
+// -- the hand-over of the pipelined loops -- only from n > 2 x 256 x 1024 = 524 288 on (tests/test_bicgstab_edges_gpu.py runs 525 625
+// rows, and small systems on 1 and 3 workgroups).  No float atomics: wave tree, four wave sums in LDS, the partials in a fixed order (block_sum_n,
 // reduce_slots of dpcg_projected.h).
 // Control.  The scalars rho, alpha, omega live in a device record (BiRec); the decisions -- the test on r, the half-step exit, the
 // breakdowns -- are derived by EVERY workgroup from the same partials, so all of them agree without a hand-off; workgroup 0 writes them

@@ -74,7 +74,7 @@ struct EarlyPartials {
 // pins a scalar the head has loaded in front of the `done` branch (the compiler would otherwise sink the load behind it)
 __device__ __forceinline__ void pin_scalar(double &x) { asm volatile("" : "+s"(x)); }
 constexpr int kSpmvPartSlots = kMaxSpmvGrid / kBlock;   // 8
-constexpr int kVecPartSlots = kMaxGrid / kBlock;        // 2
+constexpr int kVecPartSlots = kMaxGrid / kBlock;        // 4
 
 // Blocks b and b+8 share an XCD (round-robin dispatch): give each XCD one contiguous slab of the
 // work so the x-vector halo of neighbouring row-blocks is shared in that XCD's 4 MiB L2.
